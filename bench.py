@@ -7,8 +7,14 @@ of every particle (4 velocity evaluations each: time search, 3 x 1-D cell search
 interpolation).  Fields and particles are resident in HBM when the timed region starts.
 
     python bench.py --gpus 1 --steps 24 --warmup 2
+    python bench.py --gpus 1 --steps 24 --warmup 2 --full                  (also every side measurement below)
+    python bench.py --gpus 1 --steps 24 --warmup 2 --dump-outputs DIR      (also the particle columns of the timed path, DIR/<name>.npy)
     python bench.py --gpus N ...          (without a launcher: starts its own N ranks under torch.distributed.run, 127.0.0.1 rendezvous)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+When W + K steps exceed the 552 the 24 daily levels hold, the timed steps go BOUNCE_STEPS forward from step W, as many backward,
+forward again, ... (the particles' dt takes the sign of each launch, like ParticleSet.execute with a negative dt): every timed step is
+still one RK4 step of 1 h of every particle through the same resident levels, and --steps is the number of them at any size.
 
 Multi-GPU (weak scaling, 1e7 particles per GPU): ONE id space of N x 1e7 particles, generated in shard-independent blocks and
 sharded by id (parcels_amd.distributed.shard_slice), fields replicated, NO collective on the data path, so the timed K steps
@@ -16,7 +22,15 @@ contain none.  The only exchange of the path -- the periodic trajectory write-ou
 columns (t, z, y, x, particle_id) over xGMI -- is executed once after the timed steps and reported separately
 (`writeout_allgather_ms`, and `value_incl_writeout` = throughput if a write-out followed every K steps).
 
-Prints ONE JSON line (rank 0).  What the objects mean:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the headline steps and prints `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (wall milliseconds of one timed step), `timed_reps`, `config`, `device`, `host_boundary`,
+`value_end_to_end` and `legs_wall_s`.  Everything else below is measured only with `--full`.
+
+`--dump-outputs DIR` -- after the timed steps, the particle columns a caller of the timed path receives (x, y, z, t, dt, state, ei,
+  particle_id; float64) for a fixed, seeded sample of DUMP_SAMPLE particle ids (rank 0's shard), one DIR/<name>.npy each.  The inputs
+  are seeded, so two builds run with the same arguments can be compared output for output.
+
+With `--full`, what the objects mean:
 
 `roofline` -- the advection kernel is bound by fp64-rate VALU issue, not by HBM (its gathers are served by L2 / Infinity Cache):
   bound     "valu_fp64"
@@ -75,6 +89,24 @@ FP64_VECTOR_PEAK_TFLOPS = 78.6  # MI355X_MICROARCH.md: 256 CUs x 4 SIMDs x 16 la
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md
 N_SIMD, PEAK_CLOCK_GHZ = 1024, 2.4  # 256 CUs x 4 SIMDs; one fp64-rate VALU instruction occupies a SIMD for 4 cycles
 POS_BLOCK = 1 << 20  # particles per generator block (positions do not depend on how the id space is sharded)
+DUMP_SAMPLE, DUMP_SEED = 1 << 19, 20240917  # --dump-outputs: particle ids written (8 columns x 4 MiB in float64)
+BOUNCE_STEPS = 24   # --steps beyond the time interval: legs of one day of steps, alternately forward and backward in time
+REPS_BUDGET_S = 5.0  # timed repetitions after the first one are run only while all of them together stay within this many seconds
+
+
+def timed_legs(W: int, K: int, fit: int):
+    """The timed K steps after W warm-up steps as launches (first step, last step), in steps of dt from t = 0.  When W + K steps fit into
+    the `fit` steps of the time interval: ONE forward launch.  Otherwise the particles go BOUNCE_STEPS forward from step W, the same
+    number backward, forward again, ... until K steps are done: every timed step is still one RK4 step of |dt| through the same levels."""
+    if W + K <= fit:
+        return [(W, W + K)]
+    span = min(BOUNCE_STEPS, fit - W)
+    out, a, d, left = [], W, 1, K
+    while left > 0:
+        n = min(span, left)
+        out.append((a, a + d * n))
+        a, d, left = a + d * n, -d, left - n
+    return out
 
 
 def c2_positions(seed: int, lo: int, hi: int):
@@ -133,15 +165,18 @@ def cpu_baseline(case, steps: int, sample: int):
                       f"the checker oracle) on {best[1]} of {cores} hardware threads ({best[2]:.1f} s)"}
 
 
-def check_headline(case, data, n_check: int, endtime: float):
+def check_headline(case, data, n_check: int, path):
     """The first `n_check` particle ids (of this rank's shard) after the timed steps against oracle/parcels_oracle.c run on those particles
-    alone -- the checker, not the thing measured."""
+    alone -- the checker, not the thing measured.  `path`: the timed launches, (first step, last step) each; the oracle
+    runs the warm-up and the first timed launch as one execute() call and every later (bounced) launch as a call of its own."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from case_utils import compare, run_oracle
 
+    dt = case["dt"]
     sub = dict(case)
     sub["x"], sub["y"], sub["z"] = case["x"][:n_check], case["y"][:n_check], case["z"][:n_check]
-    sub["runtime"] = endtime
+    sub["runtime"] = path[0][1] * dt
+    sub["more_calls"] = [{"dt": dt if b > a else -dt, "runtime": abs(b - a) * dt} for a, b in path[1:]]
     t0 = time.perf_counter()
     ref, err, _ = run_oracle(sub, nthreads=os.cpu_count() or 1)
     oracle_s = time.perf_counter() - t0
@@ -154,7 +189,7 @@ def check_headline(case, data, n_check: int, endtime: float):
     got["particle_id"] = got["particle_id"] - lo
     rep = compare(got, ref, rtol=1e-12, check_state="all", label="headline subset vs oracle", skip=())
     return {"passed": True, "n_check": int(n_check), "max_rel_diff": rep, "tolerance": "1e-12 relative on x, y, z; state, ei, t, ids exact",
-            "steps": int(round(endtime / case["dt"])), "oracle_s": oracle_s}
+            "steps": int(path[0][1] + sum(abs(b - a) for a, b in path[1:])), "oracle_s": oracle_s}
 
 
 def self_launch(n: int, argv):
@@ -444,14 +479,30 @@ def counters_stale(key, entry):
     return entry.get("source_hash") != kernel_source_hash()
 
 
+def dump_outputs(out_dir: str, data, lo: int, n: int):
+    """--dump-outputs: the columns of a fixed, seeded sample of the particle ids lo..lo+n-1 (sorted by id), float64, as out_dir/<name>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    ids = np.asarray(data["particle_id"])
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(DUMP_SAMPLE, n), replace=False)) + lo
+    if len(ids) == n and ids[0] == lo and np.array_equal(ids[pick - lo], pick):  # host rows in id order (the usual case)
+        rows = pick - lo
+    else:
+        order = np.argsort(ids, kind="stable")
+        rows = order[np.searchsorted(ids, pick, sorter=order)]
+        assert np.array_equal(ids[rows], pick), "dump: particle ids missing from the host columns"
+    for name in ("x", "y", "z", "t", "dt", "state", "ei", "particle_id"):
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(np.asarray(data[name])[rows], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=7,
-                    help="the timed region (barrier, EXACTLY --steps steps, barrier) is repeated this many times, each from the device checkpoint taken "
-                         "after the warm-up; `value`, `ms_per_step` and `roofline` use the MEDIAN repetition, min / max are reported next to it")
+                    help="the timed region (barrier, EXACTLY --steps steps, barrier) is repeated up to this many times (as many as fit into "
+                         "REPS_BUDGET_S), each from the device checkpoint taken after the warm-up; `value`, `ms_per_step` and `roofline` use the "
+                         "MEDIAN repetition, min / max are reported next to it")
     ap.add_argument("--long-run", type=int, default=552,
                     help="N = 1 only: also run the headline workload over ALL its time levels (this many steps, one launch) as `long_run`; 0 = off")
     ap.add_argument("--repeat-execute", type=int, default=10,
@@ -478,7 +529,14 @@ def main():
     ap.add_argument("--secondary-check", type=float, default=1e5, help="particle ids of every secondary run re-run through the oracle")
     ap.add_argument("--secondary-scale", type=float, default=1.0, help="shrinks nx, ny of the secondary grid (1.0 = BASELINE size)")
     ap.add_argument("--secondary-particles", type=float, default=1e7)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figure: copy bandwidth, clock probe and `roofline`, the oracle `check`, "
+                         "the CPU baselines, long_run, repeat_execute, with_output, secondary, user_kernels and (N > 1) the write-out exchange and "
+                         "batch agreements; the options above that switch those legs off act only with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the particle columns of a fixed, seeded sample of the particle ids as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    full = bool(args.full)
 
     if launch_command_world(args.gpus, os.environ)[1]:  # --gpus N without a launcher: start the N ranks here
         raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
@@ -519,8 +577,11 @@ def main():
     shard = shard_slice(world * npart, rank, world)  # one id space, sharded by id
     case = c2_case(seed=1, lo=shard.start, hi=shard.stop)
     nt = len(case["time_s"])
-    if (K + W) * case["dt"] > case["time_s"][-1]:
-        raise SystemExit(f"steps+warmup must stay within the {nt}-level time interval")
+    fit = int(case["time_s"][-1] // case["dt"])  # RK4 steps of dt the levels hold (552)
+    if W + 1 > fit:
+        raise SystemExit(f"warmup must stay within the {nt}-level time interval ({fit} steps)")
+    path = timed_legs(W, K, fit)  # the timed launches: (first step, last step) each
+    t_end = path[-1][1] * case["dt"]  # model time of the particles after the timed steps
     fs = build_fieldset(case)
     fs.to_device(device=local_rank)
     pset = build_pset(case, fs, sort_by_cell=bool(args.sort))
@@ -546,7 +607,7 @@ def main():
     legs["setup_fieldset_particles_h2d"] = time.perf_counter() - t_start_wall
     # measured device-to-device copy bandwidth (float4 copy of 1 GiB): the practical HBM ceiling, and the calibration dispatch of
     # the FETCH_SIZE / WRITE_SIZE counter passes (tools/pmc_summary.py)
-    copy_gbps = eng.ctx.copy_bandwidth(1 << 30, 5) if rank == 0 else 0.0
+    copy_gbps = eng.ctx.copy_bandwidth(1 << 30, 5) if rank == 0 and full else 0.0
     try:
         di = eng.ctx.device_info()
         device = {"name": di["name"], "arch": di["arch"], "compute_units": di["compute_units"], "clock_mhz": di["clock_khz"] / 1e3,
@@ -561,47 +622,91 @@ def main():
         sort_ms = st_w["sort_ms"]
     # The timed region, repeated: every repetition restores the device columns to the state after the warm-up (pk_particles_checkpoint /
     # _restore, outside the timed region) and times EXACTLY K steps between two barriers.  One repetition of the headline is a 9 ms
-    # launch: a single sample of it says little (clock ramp, first touch), the median of several is what is quoted.
+    # launch: a single sample of it says little (clock ramp, first touch), the median of several is what is quoted.  Repetitions after the
+    # first are run only while all of them stay within REPS_BUDGET_S (a long --steps is one repetition: its steps are the sample).
     import ctypes as C
+
+    chk = {"valid": True}  # does the device checkpoint still hold the state after the warm-up?
+
+    def run_path(launches):
+        """The launches of `path`, back to back: (kernel ms, particle-steps) summed.  A bounced launch sets the particles' dt to the sign
+        of its direction first (ParticleSet.execute does the same on the host: particles.dt = dt); that fill discards the checkpoint."""
+        kms_, steps_ = 0.0, 0.0
+        for j, (a, b) in enumerate(launches):
+            d = dt if b > a else -dt
+            if j > 0:
+                eng.fill_column("dt", d)
+                chk["valid"] = False
+            st_ = eng.execute(kern.kernel_ids, endtime=b * dt, dt0=d, sort_by_cell=0, t_start=a * dt)
+            kms_ += st_["kernel_ms"]
+            steps_ += float(st_["steps"])
+        return {"kernel_ms": kms_, "steps": steps_, "sclk_mhz": st_.get("sclk_mhz")}
+
+    def back_to_warm():
+        """The device columns as after the warm-up, outside the timed region: from the checkpoint while it holds, else uploaded again
+        from the host columns (still the initial ones) and warmed up again, cell sort included."""
+        if chk["valid"]:
+            eng.ctx.check(eng.lib.pk_particles_restore(eng.ctx.handle), "pk_particles_restore")
+            return
+        eng.h2d()
+        if W > 0:
+            eng.execute(kern.kernel_ids, endtime=W * dt, dt0=dt, sort_by_cell=int(args.sort), t_start=0.0)
 
     eng.ctx.check(eng.lib.pk_particles_checkpoint(eng.ctx.handle), "pk_particles_checkpoint")
     reps = max(int(args.reps), 1)
     rep_el, rep_kms, rep_steps, rep_sclk = [], [], [], []
     settle_ms = None
-    if reps > 1:  # one untimed run of the timed region first (the first launch after the sort runs on cold caches and a ramping clock)
+    if reps > 1:  # one untimed run of the first timed launch first (the first launch after the sort runs on cold caches and a ramping clock)
         sync()
         t0 = time.perf_counter()
-        eng.execute(kern.kernel_ids, endtime=(W + K) * dt, dt0=dt, sort_by_cell=0, t_start=W * dt)
+        run_path(path[:1])
         sync()
         settle_ms = (time.perf_counter() - t0) * 1e3
-    for r in range(reps):
+    r = 0
+    while r < reps:
         if r > 0 or settle_ms is not None:
-            eng.ctx.check(eng.lib.pk_particles_restore(eng.ctx.handle), "pk_particles_restore")
+            back_to_warm()
         sync()
         t0 = time.perf_counter()
-        st = eng.execute(kern.kernel_ids, endtime=(W + K) * dt, dt0=dt, sort_by_cell=0, t_start=W * dt)
+        st = run_path(path)
         sync()
         rep_el.append(time.perf_counter() - t0)
         rep_kms.append(st["kernel_ms"])
         rep_steps.append(float(st["steps"]))
+        if r == 0:  # how many repetitions fit into the budget, from the first one (the smallest over the ranks: all run the same number)
+            nrep = torch.tensor([min(reps, max(1, int(REPS_BUDGET_S / max(rep_el[0], 1e-9))))], dtype=torch.int64,
+                                device="cpu" if rehearsal else "cuda")
+            if dist is not None:
+                dist.all_reduce(nrep, op=dist.ReduceOp.MIN)
+            reps = int(nrep.item())
+        r += 1
     # one more repetition of the same launch, untimed, with the clock probe spinning beside it
     probe_kms = None
-    try:
-        eng.ctx.set_option("clock_probe", 1)
-        eng.ctx.check(eng.lib.pk_particles_restore(eng.ctx.handle), "pk_particles_restore")
-        sync()
-        st_p = eng.execute(kern.kernel_ids, endtime=(W + K) * dt, dt0=dt, sort_by_cell=0, t_start=W * dt)
-        sync()
-        if st_p.get("sclk_mhz"):
-            rep_sclk.append(float(st_p["sclk_mhz"]))
-        probe_kms = float(st_p["kernel_ms"])
-    finally:
-        eng.ctx.set_option("clock_probe", 0)
+    if full:
+        try:
+            eng.ctx.set_option("clock_probe", 1)
+            back_to_warm()
+            sync()
+            st_p = run_path(path)
+            sync()
+            if st_p.get("sclk_mhz"):
+                rep_sclk.append(float(st_p["sclk_mhz"]))
+            probe_kms = float(st_p["kernel_ms"])
+        finally:
+            eng.ctx.set_option("clock_probe", 0)
+    # the particle columns after the last repetition (with --full the probe's: the same launches from the same state) come back to the
+    # host arrays (what ParticleSet.execute hands its caller)
+    t_d2h = time.perf_counter()
+    eng.d2h()
+    t_d2h = time.perf_counter() - t_d2h
+    ok = bool(np.all(pset._data["state"] == pa.StatusCode.EndofLoop))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pset._data, shard.start, shard.stop - shard.start)
     # the write-out exchange (not a step), straight from the device columns: the all-gather of the to-write columns that the north star
     # names, and the gather-to-rank-0 that ParticleFile.write uses (parcels_amd/distributed.py) -- both timed, neither in `value`
     t_ag = t_g0 = 0.0
     comm = {}
-    if dist is not None:
+    if dist is not None and full:
         from parcels_amd.distributed import allgather_output, device_write_rows, gather_write_columns
 
         from parcels_amd.distributed import ensure_comm
@@ -635,12 +740,12 @@ def main():
         if cabi:  # what ParticleFile.write calls: the write filter on the device, counts all-gathered, rows to rank 0 -- pk_gather_rows_to_root
             sync()
             t1 = time.perf_counter()
-            eng.gather_rows(names_w, (W + K) * dt, fetch=False)
+            eng.gather_rows(names_w, t_end, fetch=False)
             sync()
             t_g0 = time.perf_counter() - t1
             assert int(eng.comm_last_counts.sum()) == world * npart, eng.comm_last_counts
         else:
-            cols = device_write_rows(eng, names_w, (W + K) * dt)  # the product's write filter, on the device
+            cols = device_write_rows(eng, names_w, t_end)  # the product's write filter, on the device
             sync()
             t1 = time.perf_counter()
             rooted = gather_write_columns(cols, device=local_rank)  # (host tensors over gloo)
@@ -660,7 +765,7 @@ def main():
     # installed (parcels_amd.distributed.batch_agreement: after every pass the ranks all-reduce the first erring iteration / failing sample, at
     # the end the error codes) -- outside the timed region; calls and seconds inside the all-reduces, max over ranks
     agreements = None
-    if dist is not None and (W + K + 4) * dt <= case["time_s"][-1]:
+    if dist is not None and full and len(path) == 1 and (W + K + 4) * dt <= case["time_s"][-1]:
         try:
             from parcels_amd.distributed import batch_agreement
 
@@ -699,79 +804,79 @@ def main():
         dist.all_reduce(agt, op=dist.ReduceOp.MAX)
     t_ag, t_g0 = (float(v) for v in agt.tolist()[:2])
     ag_max = [float(v) for v in agt.tolist()[2:]]
-    t_d2h = time.perf_counter()
-    eng.d2h()
-    t_d2h = time.perf_counter() - t_d2h
-    ok = bool(np.all(pset._data["state"] == pa.StatusCode.EndofLoop))
     # TEST INFRASTRUCTURE inside the measurement script (like `secondary[*].check`): the first ids of the timed run, re-run ALONE through the
     # CPU oracle over the same W + K steps -- particles are independent, so the subset must reproduce: state, ei, t, ids exactly, positions to
     # 1e-12 relative.  After the timed region; never part of `value`.
     headline_check = None
-    if rank == 0 and args.check:
+    if rank == 0 and full and args.check:
         try:
-            headline_check = check_headline(case, pset._data, int(args.check), (W + K) * dt)
+            # (the oracle is scalar C: a long --steps re-runs fewer ids, so that the check stays at the work of 1e5 ids x 26 steps)
+            n_check = min(int(args.check), max(1000, int(args.check) * 26 // (W + K)))
+            headline_check = check_headline(case, pset._data, n_check, path)
         except AssertionError as e:
             headline_check = {"passed": False, "error": str(e)[:2000]}
     if rank == 0:
         value = total_steps / el
         kernel_s = float(kms.item()) * 1e-3
         per_gpu_steps = total_steps / world
-        algo_gbps = ALGO_BYTES_PER_STEP_C2_RK4 * per_gpu_steps / kernel_s / 1e9 if kernel_s > 0 else 0.0
-        peak_cycles = N_SIMD * PEAK_CLOCK_GHZ  # G SIMD-cycles per second
-        evals_s = per_gpu_steps * 4 / kernel_s if kernel_s > 0 else 0.0  # RK4: 4 evaluations per particle-step; per lane
-        algo_tflops = ALGO_FLOPS_PER_EVAL_C2 * evals_s / 1e12
-        # `frac` is a fraction of a ROOF: algorithmic fp64 flops over the launch time against the fp64 vector peak (the kernel is bound by
-        # fp64-rate VALU issue, its gathers are served by L2 / Infinity Cache).  `valu_busy_frac` (rounds 1-4 quoted it as `frac`) is the share
-        # of SIMD cycles with a VALU instruction in flight -- utilisation, not a roof: moves, selects and address arithmetic count in it.
-        roof = {"bound": "valu_fp64", "achieved": algo_tflops, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": algo_tflops / FP64_VECTOR_PEAK_TFLOPS,
-                # what `frac` is, spelled out so that trend lines across rounds compare like with like: rounds 1-4 printed the
-                # VALU-busy share there (now `valu_busy_frac`), rounds 5-6 ALGORITHMIC flops over the fp64 vector peak (= `algorithmic_frac`);
-                # the flops this binary really executes are `frac_executed_fp64` (PMC instruction count x static fp64 mix, below)
-                "frac_definition": "algorithmic fp64 flops (143.46 per velocity evaluation, an FMA = 2) / kernel time / 78.6 TFLOP/s",
-                "algorithmic_frac": algo_tflops / FP64_VECTOR_PEAK_TFLOPS,
-                "traffic": None, "algorithmic_fp64_flops_per_evaluation": ALGO_FLOPS_PER_EVAL_C2,
-                "frac_no_fma_peak": algo_tflops / (FP64_VECTOR_PEAK_TFLOPS / 2) * (121.59 / ALGO_FLOPS_PER_EVAL_C2),  # one op per lane and slot: NumPy never fuses (-ffp-contract=off)
-                "kernel": "pk::advect_fast_kernel<double, 0, false> (csrc/pk_kernels.h, pk_fast_agrid.h)", "kernel_ms_per_launch": float(kms.item()),
-                # shader clock DURING the timed launches (a cycle-counter / 100 MHz-counter probe spinning beside each kernel for 1 ms; median over
-                # the first millisecond of it): reconciles this line with a trace taken at another clock
-                "sclk_mhz": (rep_sclk[0] if rep_sclk else None),  # (of the untimed probe repetition that follows the timed ones; its kernel ms beside it)
-                "sclk_probe_rep_kernel_ms": probe_kms,
-                "hbm": None,
-                "algorithmic": {"note": "SURVEY 8(d) byte model; these bytes are served by L2 / Infinity Cache, this is NOT an HBM fraction",
-                                "bytes_per_particle_step": ALGO_BYTES_PER_STEP_C2_RK4, "bytes_per_launch": ALGO_BYTES_PER_STEP_C2_RK4 * per_gpu_steps,
-                                "achieved_gbps": algo_gbps, "over_hbm_peak": algo_gbps / HBM_PEAK_GBPS},
-                "measured_copy_gbps": copy_gbps}
-        pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
-        if os.path.exists(pmc):  # per-particle-step counters of the rocprofv3 PMC passes (tools/pmc_summary.py), scaled to THIS launch
-            try:
-                pj = json.load(open(pmc))
-                pp = pj["per_particle_step"]
-                busy = pp["valu_busy_simd_cycles"] * per_gpu_steps  # SIMD-cycles
-                roof["valu_busy_frac"] = busy / kernel_s / 1e9 / peak_cycles  # at the 2.4 GHz peak clock
-                roof["valu_insts_per_wave_evaluation"] = pp["valu_insts_per_wave_eval"]
-                if pp.get("fetch_bytes") is not None and pp.get("write_bytes") is not None:
-                    traffic = (pp["fetch_bytes"] + pp["write_bytes"]) * per_gpu_steps
-                    roof["traffic"] = traffic
-                    roof["hbm"] = {"achieved": traffic / kernel_s / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                                   "frac": traffic / kernel_s / 1e9 / HBM_PEAK_GBPS, "bytes_per_particle_step": pp["fetch_bytes"] + pp["write_bytes"]}
-                roof["counters_source"] = pj.get("source")
-                roof["counters_stale"] = counters_stale("AdvectionRK4", pj)  # the kernel changed since the PMC passes
-                isa = os.path.join(ROOT, "profiles", "isa_latest.json")
-                if os.path.exists(isa):
-                    # what the busy share is made of (tools/isa_histogram.py: instruction classes of the kernel's inner loops from hipcc -S):
-                    # EXECUTED fp64 arithmetic of this binary, next to the algorithmic figure `frac` is built on
-                    ij = json.load(open(isa))
-                    ops = pp["valu_insts_per_wave_eval"] * ij["fp64_arith_fraction_of_valu"]
-                    flops = pp["valu_insts_per_wave_eval"] * ij["fp64_flops_per_valu_instruction_per_lane"]
-                    roof["executed_fp64_ops_per_evaluation"] = ops  # fp64 arithmetic wave-instructions per evaluation
-                    roof["executed_fp64_flops_per_evaluation"] = flops  # per lane, an FMA counts 2
-                    roof["frac_executed_fp64"] = flops * evals_s / (FP64_VECTOR_PEAK_TFLOPS * 1e12)
-                    roof["valu_class_fractions"] = ij["valu_class_fractions"]
-                    roof["valu_cycles_per_instruction_model"] = ij["valu_cycles_per_instruction"]  # fp64 / conversions 4 cycles, everything else 2
-                    roof["frac_issue_model"] = pp["valu_insts_per_wave_eval"] * ij["valu_cycles_per_instruction"] * (evals_s / 64) / (peak_cycles * 1e9)
-                    roof["isa_source"] = "profiles/isa_latest.json (tools/isa_histogram.py, static mix of the inner loops x the PMC instruction count)"
-            except Exception as e:  # a malformed summary must not kill the bench line
-                roof["counters_error"] = repr(e)
+        roof = None  # (--full: the fp64 roof of the timed launch, the PMC counters of the committed profiles scaled to it)
+        if full:
+            algo_gbps = ALGO_BYTES_PER_STEP_C2_RK4 * per_gpu_steps / kernel_s / 1e9 if kernel_s > 0 else 0.0
+            peak_cycles = N_SIMD * PEAK_CLOCK_GHZ  # G SIMD-cycles per second
+            evals_s = per_gpu_steps * 4 / kernel_s if kernel_s > 0 else 0.0  # RK4: 4 evaluations per particle-step; per lane
+            algo_tflops = ALGO_FLOPS_PER_EVAL_C2 * evals_s / 1e12
+            # `frac` is a fraction of a ROOF: algorithmic fp64 flops over the launch time against the fp64 vector peak (the kernel is bound by
+            # fp64-rate VALU issue, its gathers are served by L2 / Infinity Cache).  `valu_busy_frac` (rounds 1-4 quoted it as `frac`) is the share
+            # of SIMD cycles with a VALU instruction in flight -- utilisation, not a roof: moves, selects and address arithmetic count in it.
+            roof = {"bound": "valu_fp64", "achieved": algo_tflops, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": algo_tflops / FP64_VECTOR_PEAK_TFLOPS,
+                    # what `frac` is, spelled out so that trend lines across rounds compare like with like: rounds 1-4 printed the
+                    # VALU-busy share there (now `valu_busy_frac`), rounds 5-6 ALGORITHMIC flops over the fp64 vector peak (= `algorithmic_frac`);
+                    # the flops this binary really executes are `frac_executed_fp64` (PMC instruction count x static fp64 mix, below)
+                    "frac_definition": "algorithmic fp64 flops (143.46 per velocity evaluation, an FMA = 2) / kernel time / 78.6 TFLOP/s",
+                    "algorithmic_frac": algo_tflops / FP64_VECTOR_PEAK_TFLOPS,
+                    "traffic": None, "algorithmic_fp64_flops_per_evaluation": ALGO_FLOPS_PER_EVAL_C2,
+                    "frac_no_fma_peak": algo_tflops / (FP64_VECTOR_PEAK_TFLOPS / 2) * (121.59 / ALGO_FLOPS_PER_EVAL_C2),  # one op per lane and slot: NumPy never fuses (-ffp-contract=off)
+                    "kernel": "pk::advect_fast_kernel<double, 0, false> (csrc/pk_kernels.h, pk_fast_agrid.h)", "kernel_ms_per_launch": float(kms.item()),
+                    # shader clock DURING the timed launches (a cycle-counter / 100 MHz-counter probe spinning beside each kernel for 1 ms; median over
+                    # the first millisecond of it): reconciles this line with a trace taken at another clock
+                    "sclk_mhz": (rep_sclk[0] if rep_sclk else None),  # (of the untimed probe repetition that follows the timed ones; its kernel ms beside it)
+                    "sclk_probe_rep_kernel_ms": probe_kms,
+                    "hbm": None,
+                    "algorithmic": {"note": "SURVEY 8(d) byte model; these bytes are served by L2 / Infinity Cache, this is NOT an HBM fraction",
+                                    "bytes_per_particle_step": ALGO_BYTES_PER_STEP_C2_RK4, "bytes_per_launch": ALGO_BYTES_PER_STEP_C2_RK4 * per_gpu_steps,
+                                    "achieved_gbps": algo_gbps, "over_hbm_peak": algo_gbps / HBM_PEAK_GBPS},
+                    "measured_copy_gbps": copy_gbps}
+            pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
+            if os.path.exists(pmc):  # per-particle-step counters of the rocprofv3 PMC passes (tools/pmc_summary.py), scaled to THIS launch
+                try:
+                    pj = json.load(open(pmc))
+                    pp = pj["per_particle_step"]
+                    busy = pp["valu_busy_simd_cycles"] * per_gpu_steps  # SIMD-cycles
+                    roof["valu_busy_frac"] = busy / kernel_s / 1e9 / peak_cycles  # at the 2.4 GHz peak clock
+                    roof["valu_insts_per_wave_evaluation"] = pp["valu_insts_per_wave_eval"]
+                    if pp.get("fetch_bytes") is not None and pp.get("write_bytes") is not None:
+                        traffic = (pp["fetch_bytes"] + pp["write_bytes"]) * per_gpu_steps
+                        roof["traffic"] = traffic
+                        roof["hbm"] = {"achieved": traffic / kernel_s / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                       "frac": traffic / kernel_s / 1e9 / HBM_PEAK_GBPS, "bytes_per_particle_step": pp["fetch_bytes"] + pp["write_bytes"]}
+                    roof["counters_source"] = pj.get("source")
+                    roof["counters_stale"] = counters_stale("AdvectionRK4", pj)  # the kernel changed since the PMC passes
+                    isa = os.path.join(ROOT, "profiles", "isa_latest.json")
+                    if os.path.exists(isa):
+                        # what the busy share is made of (tools/isa_histogram.py: instruction classes of the kernel's inner loops from hipcc -S):
+                        # EXECUTED fp64 arithmetic of this binary, next to the algorithmic figure `frac` is built on
+                        ij = json.load(open(isa))
+                        ops = pp["valu_insts_per_wave_eval"] * ij["fp64_arith_fraction_of_valu"]
+                        flops = pp["valu_insts_per_wave_eval"] * ij["fp64_flops_per_valu_instruction_per_lane"]
+                        roof["executed_fp64_ops_per_evaluation"] = ops  # fp64 arithmetic wave-instructions per evaluation
+                        roof["executed_fp64_flops_per_evaluation"] = flops  # per lane, an FMA counts 2
+                        roof["frac_executed_fp64"] = flops * evals_s / (FP64_VECTOR_PEAK_TFLOPS * 1e12)
+                        roof["valu_class_fractions"] = ij["valu_class_fractions"]
+                        roof["valu_cycles_per_instruction_model"] = ij["valu_cycles_per_instruction"]  # fp64 / conversions 4 cycles, everything else 2
+                        roof["frac_issue_model"] = pp["valu_insts_per_wave_eval"] * ij["valu_cycles_per_instruction"] * (evals_s / 64) / (peak_cycles * 1e9)
+                        roof["isa_source"] = "profiles/isa_latest.json (tools/isa_histogram.py, static mix of the inner loops x the PMC instruction count)"
+                except Exception as e:  # a malformed summary must not kill the bench line
+                    roof["counters_error"] = repr(e)
         t_all = el + t_h2d + t_d2h + sort_ms * 1e-3
         out = {
             "metric": "RK4 particle-steps/sec",
@@ -794,25 +899,27 @@ def main():
             "config": {"workload": "C2: 3D rectilinear A-grid 360x180x50x24 fp64 U,V (spherical), AdvectionRK4, dt=3600 s",
                        "particles_per_gpu": npart, "particle_dtype": "f64", "cell_sorted": bool(args.sort),
                        "parallelism": f"one id space of {world * npart} particles sharded by id x{world}, fields replicated",
+                       "timed_launches": (f"one forward launch, steps {W} to {W + K}" if len(path) == 1 else
+                                          f"{len(path)} launches between steps {W} and {max(max(p) for p in path)}, alternately forward and backward "
+                                          f"in time ({W} + {K} steps exceed the {fit} of the time interval)"),
                        "all_states_endofloop": ok, **({"rehearsal_shared_gpu_gloo": True} if rehearsal else {})},
-            "check": headline_check,
-            "roofline": roof,
+            **({"check": headline_check, "roofline": roof} if full else {}),
             # boundary costs outside the timed steps (rank 0): host<->device copies of the particle columns, the one-off cell sort
             "host_boundary": {"h2d_ms": t_h2d * 1e3, "d2h_ms": t_d2h * 1e3, "cell_sort_ms": sort_ms,
                               "value_pcie_inclusive": total_steps / (el + t_h2d + t_d2h)},
             "value_end_to_end": total_steps / t_all,  # H2D of the particle columns + cell sort + K steps + D2H
-            "writeout_allgather_ms": t_ag * 1e3 if world > 1 else None,
-            "writeout_gather_to_root_ms": t_g0 * 1e3 if world > 1 else None,  # what ParticleFile.write does (rows of the write filter -> rank 0)
+            "writeout_allgather_ms": t_ag * 1e3 if world > 1 and full else None,
+            "writeout_gather_to_root_ms": t_g0 * 1e3 if world > 1 and full else None,  # what ParticleFile.write does (rows of the write filter -> rank 0)
             "comm": comm or None,
             # 4 more steps with the batch agreements of a sharded ParticleSet installed (outside `value`): all-reduce calls per rank, seconds
             # inside them / wall / kernel ms, each the max over ranks
             "batch_agreements": ({"steps": 4, "calls": int(ag_max[0]), "seconds_in_allreduce_max_rank": ag_max[1], "wall_ms_max_rank": ag_max[2] * 1e3,
                                   "kernel_ms_max_rank": ag_max[3]} if world > 1 and ag_max[0] >= 0 else None),
             "device": device,
-            "value_incl_writeout": total_steps / (el + t_ag) if world > 1 else None,
+            "value_incl_writeout": total_steps / (el + t_ag) if world > 1 and full else None,
         }
         ref = os.path.join(ROOT, "profiles", "r02_cpu_reference.json")
-        if os.path.exists(ref):
+        if full and os.path.exists(ref):
             try:
                 rj = json.load(open(ref))
                 out["cpu_baseline_reference"] = {"value": rj["all_cores"]["value"], "unit": rj["unit"], "cores": rj["all_cores"]["processes"],
@@ -823,32 +930,32 @@ def main():
             except Exception:
                 pass
         legs["headline_warmup_and_timed_reps"] = time.perf_counter() - t_start_wall - legs["setup_fieldset_particles_h2d"]
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg is reported at N = 1 only
+        if full and not args.no_cpu_baseline and world == 1:  # the CPU leg is reported at N = 1 only
             _t = time.perf_counter()
-            out["cpu_baseline"] = cpu_baseline(case, steps=K, sample=min(args.cpu_sample, npart))
+            out["cpu_baseline"] = cpu_baseline(case, steps=K if len(path) == 1 else BOUNCE_STEPS, sample=min(args.cpu_sample, npart))
             legs["cpu_baseline"] = time.perf_counter() - _t
-        if args.long_run and world == 1:
+        if full and args.long_run and world == 1:
             _t = time.perf_counter()
             try:
                 out["long_run"] = long_run(case, fs, int(args.long_run))
             except Exception as e:
                 out["long_run"] = {"error": repr(e)[:2000]}
             legs["long_run"] = time.perf_counter() - _t
-        if args.repeat_execute and world == 1:
+        if full and args.repeat_execute and world == 1:
             _t = time.perf_counter()
             try:
-                out["repeat_execute"] = repeat_execute(case, fs, int(args.repeat_execute), K)
+                out["repeat_execute"] = repeat_execute(case, fs, int(args.repeat_execute), min(K, fit // max(int(args.repeat_execute), 1)))
             except Exception as e:
                 out["repeat_execute"] = {"error": repr(e)[:2000]}
             legs["repeat_execute"] = time.perf_counter() - _t
-        if args.with_output and world == 1:
+        if full and args.with_output and world == 1:
             _t = time.perf_counter()
             try:
                 out["with_output"] = with_output(case, fs, int(args.with_output), 24)
             except Exception as e:
                 out["with_output"] = {"error": repr(e)[:2000]}
             legs["with_output"] = time.perf_counter() - _t
-        if args.secondary and world == 1:
+        if full and args.secondary and world == 1:
             # release the headline's device and host memory first: C3 needs 36 GB of HBM and 48 GB of host arrays
             pset = kern = eng = fs = case = None
             import gc

@@ -56,7 +56,7 @@ def test_c4_two_ranks_write_the_single_process_file(gpu, tmp_path):
 def test_bench_py_runs_under_torchrun_with_two_ranks(gpu):
     """The driver's multi-GPU entry point, `python -m torch.distributed.run ... bench.py --gpus N`, rehearsed with two ranks sharing
     this box's one GPU over gloo (PARCELS_AMD_BENCH_REHEARSAL=1; RCCL refuses two ranks on one device): one JSON line from rank 0,
-    whole-job value over one id space sharded by id, the write-out all-gather of the device columns timed."""
+    whole-job value over one id space sharded by id, the write-out all-gather of the device columns timed (`--full`)."""
     import json
     import os
     import socket
@@ -70,7 +70,8 @@ def test_bench_py_runs_under_torchrun_with_two_ranks(gpu):
         port = s.getsockname()[1]
     env = dict(os.environ, PARCELS_AMD_BENCH_REHEARSAL="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
-           str(port), os.path.join(ROOT_DIR, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--particles", "200000", "--no-cpu-baseline"]
+           str(port), os.path.join(ROOT_DIR, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--particles", "200000", "--no-cpu-baseline",
+           "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT_DIR, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -115,7 +116,7 @@ def test_bench_py_starts_its_own_ranks(gpu):
 
 @pytest.mark.gpu
 def test_bench_py_secondary_configs_carry_the_oracle_check(gpu):
-    """The bench line's `secondary` array (BASELINE configs 3 and 5 next to the C2 headline), here on a shrunken grid: one entry per
+    """The `--full` bench line's `secondary` array (BASELINE configs 3 and 5 next to the C2 headline), here on a shrunken grid: one entry per
     kernel list with steps/s, the algorithmic-byte roofline fraction and the verdict of the oracle re-run of a subset."""
     import json
     import os
@@ -125,7 +126,7 @@ def test_bench_py_secondary_configs_carry_the_oracle_check(gpu):
     from case_utils import ROOT_DIR
 
     cmd = [sys.executable, os.path.join(ROOT_DIR, "bench.py"), "--steps", "4", "--warmup", "1", "--particles", "200000", "--no-cpu-baseline",
-           "--secondary-scale", "0.1", "--secondary-particles", "100000", "--secondary-check", "5000"]
+           "--secondary-scale", "0.1", "--secondary-particles", "100000", "--secondary-check", "5000", "--full"]
     r = subprocess.run(cmd, cwd=ROOT_DIR, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -139,3 +140,63 @@ def test_bench_py_secondary_configs_carry_the_oracle_check(gpu):
     lr = out["long_run"]
     assert lr["particle_steps"] > 0.9 * 200000 * 552 and lr["value"] > 0 and "error" not in lr
     assert out["timed_reps"]["n"] == 7 and set(out["legs_wall_s"]) >= {"secondary", "long_run", "total_after_imports"}
+
+
+@pytest.mark.gpu
+def test_bench_py_plain_run_is_the_headline_and_dumps_its_outputs(gpu, tmp_path):
+    """A plain `bench.py` run measures the headline alone (no side legs in its line) and `--dump-outputs DIR` writes the particle columns
+    of the timed path after its last step: float64 .npy files of a fixed, seeded sample of ids, the same in two runs of the same arguments."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    from case_utils import ROOT_DIR
+
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        cmd = [sys.executable, os.path.join(ROOT_DIR, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--particles", "200000",
+               "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, cwd=ROOT_DIR, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["metric"] == "RK4 particle-steps/sec" and out["unit"] == "particle-steps/s" and out["higher_is_better"] is True
+        assert out["dtype"] == "f64" and out["steps"] == 4 and out["value"] > 0 and out["config"]["all_states_endofloop"] is True
+        assert abs(out["value"] * out["ms_per_step"] * 1e-3 * out["steps"] - 200000 * 4) < 1e-6 * 200000 * 4
+        assert not {"roofline", "check", "cpu_baseline", "cpu_baseline_reference", "long_run", "repeat_execute", "with_output", "secondary",
+                    "user_kernels"} & set(out), sorted(out)
+        files = sorted(os.listdir(d))
+        assert files == sorted(f"{n}.npy" for n in ("x", "y", "z", "t", "dt", "state", "ei", "particle_id")), files
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float64 for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert np.all(np.diff(arrs["particle_id"]) > 0) and np.all(arrs["t"] == 5 * 3600.0)
+        outs.append(arrs)
+    for name, a in outs[0].items():
+        assert np.array_equal(a, outs[1][name]), name
+
+
+@pytest.mark.gpu
+def test_bench_py_steps_beyond_the_time_interval(gpu):
+    """`--steps` larger than the 552 steps the 24 levels hold: the timed steps bounce forward and backward in time, every one of them is
+    timed and counted, and the oracle re-run of a subset follows the same launches to the same state."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from case_utils import ROOT_DIR
+
+    cmd = [sys.executable, os.path.join(ROOT_DIR, "bench.py"), "--gpus", "1", "--steps", "600", "--warmup", "2", "--particles", "200000", "--full",
+           "--no-cpu-baseline", "--secondary", "0", "--long-run", "0", "--repeat-execute", "0", "--with-output", "0", "--user-kernels", "0"]
+    r = subprocess.run(cmd, cwd=ROOT_DIR, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert out["steps"] == 600 and out["value"] > 0 and out["config"]["all_states_endofloop"] is True
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 * out["steps"] - 200000 * 600) < 1e-6 * 200000 * 600
+    assert "alternately forward and backward" in out["config"]["timed_launches"]
+    assert out["check"]["passed"] is True and out["check"]["steps"] == 602, out["check"]

@@ -116,11 +116,9 @@ def test_zarr_v3_levels_read_what_was_written(tmp_path, codec, key_encoding):
 
 
 def test_zarr_levels_decodes_the_reference_s_blosc_stores():
-    """The zarr stores the reference ships (tests/test_data/*.zarr, numcodecs Blosc lz4 + byte shuffle) through the product's own
-    frame decoder, against oracle/mini_zarr.py (build container only)."""
-    root = "/root/reference/tests/test_data/test_interpolation_jit_linear.zarr"
-    if not os.path.isdir(root):
-        pytest.skip("reference test data not present")
+    """A zarr store the reference ships (its tests/test_data/test_interpolation_jit_linear.zarr, numcodecs Blosc lz4 + byte shuffle,
+    kept as a fixture under tests/golden/zarr/) through the product's own frame decoder, against oracle/mini_zarr.py."""
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "zarr", "test_interpolation_jit_linear.zarr")
     from oracle import mini_zarr
     from parcels_amd.sources import _blosc_decode
 

@@ -7,7 +7,7 @@ for r in $(seq 1 $reps); do
   for v in $vs; do
     if [ $v = new ]; then unset PARCELS_HIP_LIB; else export PARCELS_HIP_LIB=$PWD/parcels_amd/libparcels_hip_$v.so; fi
     if [ $v = base ] && [ -n "$PK_BASE_ABI" ]; then export PARCELS_HIP_ALLOW_ABI=$PK_BASE_ABI; else unset PARCELS_HIP_ALLOW_ABI; fi  # (the library of the previous round)
-    timeout 300 python bench.py --steps 24 --warmup 2 --secondary 0 --no-cpu-baseline --user-kernels 0 > $out/c2_${v}_$r.json 2> $out/c2_${v}_$r.err
+    timeout 300 python bench.py --full --steps 24 --warmup 2 --secondary 0 --no-cpu-baseline --user-kernels 0 > $out/c2_${v}_$r.json 2> $out/c2_${v}_$r.err
     python - $out/c2_${v}_$r.json $v $r <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().split("\n")[-1]); k=d["timed_reps"]["kernel_ms"]; lr=d.get("long_run") or {}

@@ -4,8 +4,8 @@
 TAG=${1:-c2}; shift
 OUT=$PWD/gpurun_out; mkdir -p $OUT
 export TMPDIR=/tmp
-B="python $PWD/bench.py --no-cpu-baseline $*"
-python bench.py $* > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+B="python $PWD/bench.py --full --no-cpu-baseline $*"
+python bench.py --full $* > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_trace -o t -- $B > /dev/null 2> $OUT/${TAG}_trace.err
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE -d $OUT/${TAG}_pmc_sq -o p --output-format csv -- $B > /dev/null 2> $OUT/${TAG}_pmc_sq.err

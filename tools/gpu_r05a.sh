@@ -10,7 +10,7 @@ import json,sys
 for l in open(sys.argv[1]):
     d=json.loads(l); print(d['kernels'], 'kernel_ms', d['kernel_ms'], d['kernel_ms_stats'], 'pairs', d.get('velocity_pairs'), 'check', (d.get('check') or {}).get('max_abs_diff'))
 PY
-timeout 600 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc $?" | tee -a $out/summary.txt
+timeout 600 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc $?" | tee -a $out/summary.txt
 python - $out/bench.json <<'PY' | tee -a $out/summary.txt
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])

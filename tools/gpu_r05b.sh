@@ -3,7 +3,7 @@
 out=gpurun_out/r05b; mkdir -p $out
 timeout 900 python -m pytest tests/test_gpu_resident_columns.py tests/test_gpu_twe_passes.py tests/test_gpu_fast_cgrid.py -m gpu -q -x > $out/pytest_new.log 2>&1; echo "pytest new rc $?" | tee -a $out/summary.txt; tail -25 $out/pytest_new.log | tee -a $out/summary.txt
 timeout 900 python -m pytest tests -m gpu -q > $out/pytest.log 2>&1; echo "pytest all rc $?" | tee -a $out/summary.txt; grep -E "passed|failed" $out/pytest.log | tee -a $out/summary.txt; grep -E "^FAILED|^ERROR" $out/pytest.log | head -20 | tee -a $out/summary.txt
-timeout 600 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc $?" | tee -a $out/summary.txt
+timeout 600 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc $?" | tee -a $out/summary.txt
 python - $out/bench.json <<'PY' | tee -a $out/summary.txt
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])

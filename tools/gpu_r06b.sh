@@ -16,7 +16,7 @@ for v in base dma pxgdma; do
 done
 unset PARCELS_HIP_LIB
 find $OUT -name "*.db" -delete 2>/dev/null
-timeout 900 python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc $?" | tee -a $out/summary.txt
+timeout 900 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc $?" | tee -a $out/summary.txt
 python - $out/bench_default.json <<'PY' | tee -a $out/summary.txt
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])

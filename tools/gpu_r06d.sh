@@ -25,7 +25,7 @@ timeout 1800 python -m pytest tests -m gpu -q > $out/pytest_all.log 2>&1; echo "
 bash tools/gpu_round6_profiles.sh r06f > $out/profiles.log 2>&1; echo "profiles rc $?" | tee -a $out/summary.txt
 cp -r gpurun_out/r06_profiles $out/ 2>/dev/null
 cp profiles/pmc_latest.json profiles/pmc_secondary_latest.json /tmp/ 2>/dev/null
-timeout 1200 python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc $?" | tee -a $out/summary.txt
+timeout 1200 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc $?" | tee -a $out/summary.txt
 python - $out/bench_default.json <<'PY' | tee -a $out/summary.txt
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])

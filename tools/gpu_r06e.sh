@@ -22,4 +22,4 @@ for f in sys.argv[1:]:
     for k,v in d["encode_one_table_of_n_rows"].items():
         print("  encode", k, v if not isinstance(v,dict) else (round(v["seconds"]*1e3,1), "ms", round(v["GB_per_s"],2), "GB/s"))
 PY
-PARCELS_AMD_BENCH_REHEARSAL=1 timeout 900 python bench.py --gpus 2 --particles 2e6 --steps 8 --warmup 2 > $out/bench_gpus2_rehearsal.json 2> $out/bench_gpus2_rehearsal.err; echo "bench --gpus 2 rehearsal rc $?" | tee -a $out/summary.txt; tail -1 $out/bench_gpus2_rehearsal.json | cut -c1-900 | tee -a $out/summary.txt
+PARCELS_AMD_BENCH_REHEARSAL=1 timeout 900 python bench.py --full --gpus 2 --particles 2e6 --steps 8 --warmup 2 > $out/bench_gpus2_rehearsal.json 2> $out/bench_gpus2_rehearsal.err; echo "bench --gpus 2 rehearsal rc $?" | tee -a $out/summary.txt; tail -1 $out/bench_gpus2_rehearsal.json | cut -c1-900 | tee -a $out/summary.txt

@@ -14,7 +14,7 @@ for f in sys.argv[1:]:
     for c in d["cadences"]:
         print("  every", c["every_steps"], "wall", {k:round(v,3) for k,v in c["wall_s"].items()}, "per table ms", {k:round(v,1) for k,v in c["per_table_ms"].items()}, "hidden", round(c["output_hidden_frac"],3), "async<=inline", c["async_not_slower_than_inline"], "identical", c["byte_identical"], c["async_writer"])
 PY
-timeout 900 python bench.py --secondary 0 --user-kernels 0 --no-cpu-baseline --long-run 0 --repeat-execute 0 > $out/bench_with_output.json 2> $out/bench_with_output.err; echo "bench rc $?" | tee -a $out/summary.txt
+timeout 900 python bench.py --full --secondary 0 --user-kernels 0 --no-cpu-baseline --long-run 0 --repeat-execute 0 > $out/bench_with_output.json 2> $out/bench_with_output.err; echo "bench rc $?" | tee -a $out/summary.txt
 python - $out/bench_with_output.json <<'PY' | tee -a $out/summary.txt
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])

@@ -4,7 +4,7 @@ out=gpurun_out/r06k; mkdir -p $out
 export TMPDIR=/tmp
 timeout 1800 python -m pytest tests -m gpu -q > $out/pytest_all.log 2>&1; echo "pytest all rc $?" | tee -a $out/summary.txt; tail -3 $out/pytest_all.log | tee -a $out/summary.txt
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc $?" | tee -a $out/summary.txt; tail -1 $out/smoke.log | tee -a $out/summary.txt
-timeout 1200 python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc $?" | tee -a $out/summary.txt
+timeout 1200 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc $?" | tee -a $out/summary.txt
 python - $out/bench_default.json <<'PY' | tee -a $out/summary.txt
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])

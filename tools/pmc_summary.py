@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Summarise the rocprofv3 passes that tools/gpu_profile_c2.sh leaves under gpurun_out/ into profiles/<name>.md and
-profiles/pmc_latest.json (which bench.py folds into its `roofline` object).
+profiles/pmc_latest.json (which bench.py --full folds into its `roofline` object).
 
     python tools/pmc_summary.py TAG NAME [--particles 1e7 --steps 24]
         reads  gpurun_out/TAG_pmc_{sq,sq2,fetch,write}/p_counter_collection.csv, gpurun_out/TAG_trace/, gpurun_out/TAG_bench.json
@@ -9,7 +9,7 @@ profiles/pmc_latest.json (which bench.py folds into its `roofline` object).
 Counter conventions on gfx950 (MI355X_MICROARCH.md): the passes are separate runs with --kernel-trace only; SQ_ACTIVE_INST_* and
 SQ_WAVE_CYCLES / SQ_WAIT_* count QUAD-cycles (x4 = cycles); GRBM_GUI_ACTIVE is summed over the 8 XCDs; FETCH_SIZE / WRITE_SIZE
 are KiB of 64-byte fabric requests and FETCH_SIZE reports half the bytes of a wide coalesced read -- both are calibrated here on
-the float4 copy kernel bench.py runs first (pk::copy_kernel: exactly 1 GiB read + 1 GiB written per dispatch).
+the float4 copy kernel bench.py --full runs first (pk::copy_kernel: exactly 1 GiB read + 1 GiB written per dispatch).
 Everything is reported PER PARTICLE-STEP as well, so that bench.py can scale it to any --steps / --particles.
 """
 import argparse
@@ -73,7 +73,7 @@ def trace_summary(tag, out_md):
     if not dbs:
         return None
     cur = sqlite3.connect(dbs[0]).cursor()
-    lines = [f"# rocprofv3 --kernel-trace --stats of `python bench.py --no-cpu-baseline` ({tag})", "", "## top kernels (us)", "",
+    lines = [f"# rocprofv3 --kernel-trace --stats of `python bench.py --full --no-cpu-baseline` ({tag})", "", "## top kernels (us)", "",
              "| kernel | calls | total_us | avg_us | % |", "|---|---|---|---|---|"]
     for name, calls, total, avg, pct in cur.execute("select name,total_calls,total_duration,average,percentage from top_kernels"):
         short = name if len(name) < 110 else name[:70] + " ... " + name[-30:]
