@@ -59,6 +59,14 @@ struct PkSelect {
     size_t tmp_bytes = 0;
 };
 struct PkComm;
+// {a, 1/width} rows of the coordinate vectors a dedicated kernel stages in LDS, built once per (grid, field) by coord_table
+struct CoordTable {
+    double* d = nullptr;  // device copy, `cap` doubles
+    size_t cap = 0;
+    int grid = -1, field = -1;
+    bool ok = false;       // every cell width has a well-scaled reciprocal and the table fits the kernel's LDS
+    int32_t off[5] = {};   // first row of each vector, then the row count
+};
 struct pk_ctx {
     int device = 0;
     hipStream_t compute = nullptr, copy = nullptr;
@@ -142,6 +150,7 @@ struct pk_ctx {
     int no_cell_table = 0;
     int no_fast = 0;
     int no_fast_cgrid = 0;
+    bool no_block_cache = false;  // PK_NO_BLOCK_CACHE: the 2-D A-grid kernel without its per-lane corner-block cache
     // asynchronous write-out snapshots (pk_particles_snapshot_begin / _wait): two sets of device staging columns (host row order)
     // + pinned host columns, so that the D2H and the encode of interval k overlap the launch of interval k+1
     struct Snapshot {
@@ -156,13 +165,10 @@ struct pk_ctx {
         hipEvent_t ready = nullptr, done = nullptr;
         bool in_flight = false;
     } snap[2];
-    // {a, 1/width} coordinate tables of the fast A-grid path (pk_fast_agrid.h), cached per (main grid, main field)
-    double* d_fast_tab = nullptr;
-    size_t fast_tab_cap = 0;
-    int fast_tab_grid = -1, fast_tab_field = -1;
-    bool fast_tab_ok = false;
-    int32_t fast_tab_off[5] = {0, 0, 0, 0, 0};
-    // fast C-grid path (pk_fast_cgrid.h): per-cell records of one grid + {a, 1/width} tables of time | depth, cached per (grid, field)
+    // coordinate tables of the fast A-grid path (pk_fast_agrid.h: time | depth | lat | lon) and of the fast C-grid path (pk_fast_cgrid.h:
+    // time | depth), cached per (main grid, main field)
+    CoordTable tab_a, tab_c;
+    // fast C-grid path: per-cell records of one grid
     double* d_ct2 = nullptr;
     int ct2_grid = -1;
     int ct2_near = 0;  // FastC::near_edges of that grid
@@ -177,11 +183,6 @@ struct pk_ctx {
     int no_velocity_pairs = 1;  // OPT-IN since round 5 (option "velocity_pairs" / PK_VELOCITY_PAIRS=1): packing a pair costs more than the
                                 // launch it serves saves at BASELINE config 5 (pk_exec_stats.pack_ms)
     uint64_t upload_counter = 0;
-    double* d_cg_tab = nullptr;
-    size_t cg_tab_cap = 0;
-    int cg_tab_grid = -1, cg_tab_field = -1;
-    bool cg_tab_ok = false;
-    int32_t cg_tab_off[3] = {0, 0, 0};
 
     PkSelect sel;                   // write filter on the device rows (pk_select.inc): the filtered snapshot and the multi-GPU exchange use it
     struct PkComm* comm = nullptr;  // the multi-GPU exchange (pk_comm.inc: RCCL communicator + staging), NULL until pk_comm_init
@@ -665,6 +666,7 @@ int32_t pk_init(int32_t device, pk_ctx** out) {
     if (const char* e = getenv("PK_NO_FAST_CGRID")) ctx->no_fast_cgrid = atoi(e);
     if (const char* e = getenv("PK_NO_VELOCITY_PAIRS")) ctx->no_velocity_pairs = atoi(e);
     if (const char* e = getenv("PK_VELOCITY_PAIRS")) ctx->no_velocity_pairs = !atoi(e);
+    ctx->no_block_cache = getenv("PK_NO_BLOCK_CACHE") != nullptr;
     *out = ctx;
     PK_HIP(ctx, hipSetDevice(device));
     PK_HIP(ctx, hipGetDeviceProperties(&ctx->prop, device));
@@ -774,8 +776,8 @@ int32_t pk_destroy(pk_ctx* ctx) {
         if (sn.done) (void)hipEventDestroy(sn.done);
     }
     if (ctx->d_pack_tmp) (void)hipFree(ctx->d_pack_tmp);
-    if (ctx->d_fast_tab) (void)hipFree(ctx->d_fast_tab);
-    if (ctx->d_cg_tab) (void)hipFree(ctx->d_cg_tab);
+    if (ctx->tab_a.d) (void)hipFree(ctx->tab_a.d);
+    if (ctx->tab_c.d) (void)hipFree(ctx->tab_c.d);
     if (ctx->d_ct2) (void)hipFree(ctx->d_ct2);
     if (ctx->d_vp) (void)hipFree(ctx->d_vp);
     if (ctx->d_counters) (void)hipFree(ctx->d_counters);
@@ -1779,6 +1781,12 @@ int32_t pk_particles_compact(pk_ctx* ctx, const pk_particles_desc* new_host, int
 }
 
 // ---- execution -----------------------------------------------------------------------------------------
+// pk_exec_stats.program of a launch that runs a dedicated kernel (other launches report their PROG_*, pk_kernels.h)
+enum { PROGRAM_FAST_AGRID = 100, PROGRAM_FAST_CGRID = 101 };
+// Which dedicated kernel runs a launch.  The values are the `prog` argument of a user module's launcher (pk_set_user_program), where
+// DEDICATED_NONE is its kernel-list interpreter.
+enum Dedicated { DEDICATED_NONE = 0, DEDICATED_A2 = 1, DEDICATED_A3 = 2, DEDICATED_C2 = 3, DEDICATED_C3 = 4 };
+
 // Some grid stores a coordinate as float32: NumPy's float32 arithmetic on coordinate / barycentric arrays has to be reproduced
 // (pk_device.h: TYPED), which only the PROG_TYPED program and the typed sampling kernels carry.
 static bool ctx_is_typed(const pk_ctx* ctx) {
@@ -1787,39 +1795,14 @@ static bool ctx_is_typed(const pk_ctx* ctx) {
     return false;
 }
 
-static int32_t fill_args(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, size_t& lds_bytes, int& use_lds) {
+// The kernel-list interpreter variant of a launch (include/parcels_hip.h: pk_generic_variant)
+static int32_t interp_key(const pk_ctx* ctx, const pk_exec_params* prm, const KArgs& a) {
+    return (ctx->fields[prm->fU].d.dtype == PK_F32 ? 6 : 0) + (ctx->grids[a.main_grid].d.kind == 1 ? 3 : 0) + std::min<int>(prm->interp_uv, 2);
+}
+
+// The launch arguments of `prm` apart from the descriptor tables (upload_descriptors): main field and grid, resident time window, LDS layout.
+static int32_t launch_args(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, size_t& lds_bytes, int& use_lds) {
     memset(&a, 0, sizeof(a));
-    {
-        // descriptor tables: [grids][fields] in one device buffer, refreshed on the compute stream when anything changed since the last
-        // launch (ring slots move with every streamed level).  In stream order, so a kernel still running keeps reading the old values.
-        const size_t gb = ctx->grids.size() * sizeof(DGrid), fb = ctx->fields.size() * sizeof(DField);
-        const size_t need = gb + fb;
-        if (need > ctx->desc_bytes) {
-            const size_t cap = (size_t)PK_MAX_GRIDS * sizeof(DGrid) + (size_t)PK_MAX_FIELDS * sizeof(DField);
-            if (ctx->d_desc) (void)hipFree(ctx->d_desc);
-            if (ctx->h_desc) (void)hipHostFree(ctx->h_desc);
-            ctx->d_desc = ctx->h_desc = nullptr;
-            ctx->desc_bytes = 0;
-            PK_HIP(ctx, hipMalloc((void**)&ctx->d_desc, cap));
-            PK_HIP(ctx, hipHostMalloc((void**)&ctx->h_desc, 2 * cap, hipHostMallocDefault));  // staged copy + what the device holds
-            memset(ctx->h_desc, 0xFF, 2 * cap);
-            ctx->desc_bytes = cap;
-        }
-        char* stage = ctx->h_desc;                    // what this launch needs
-        char* mirror = ctx->h_desc + ctx->desc_bytes;  // what was uploaded last
-        std::vector<char> cur(need);
-        for (size_t g = 0; g < ctx->grids.size(); g++) memcpy(cur.data() + g * sizeof(DGrid), &ctx->grids[g].d, sizeof(DGrid));
-        for (size_t f = 0; f < ctx->fields.size(); f++) memcpy(cur.data() + gb + f * sizeof(DField), &ctx->fields[f].d, sizeof(DField));
-        if (need && memcmp(cur.data(), mirror, need) != 0) {
-            // the previous upload from `stage` completed long ago unless a launch is still queued behind it: wait for the stream then
-            PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
-            memcpy(stage, cur.data(), need);
-            PK_HIP(ctx, hipMemcpyAsync(ctx->d_desc, stage, need, hipMemcpyHostToDevice, ctx->compute));
-            memcpy(mirror, cur.data(), need);
-        }
-        a.grids = (const PK_CONST_AS DGrid*)ctx->d_desc;
-        a.fields = (const PK_CONST_AS DField*)(ctx->d_desc + gb);
-    }
     a.p = ctx->dev;
     a.prm = *prm;
     a.counters = ctx->d_counters;
@@ -1889,14 +1872,111 @@ static int32_t fill_args(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, size_
     return 0;
 }
 
-// Fold the descriptors of the velocity fields and their grid into the wave-uniform constants of the fast A-grid path
-// (pk_device.h: FastA, pk_fast_agrid.h) when its preconditions hold: rectilinear grid with float64 coordinates, XLinear_Velocity,
+// Descriptor tables: [grids][fields] in one device buffer, refreshed on the compute stream when anything changed since the last launch (ring
+// slots move with every streamed level).  In stream order, so a kernel still running keeps reading the old values.
+static int32_t upload_descriptors(pk_ctx* ctx, KArgs& a) {
+    const size_t gb = ctx->grids.size() * sizeof(DGrid), fb = ctx->fields.size() * sizeof(DField);
+    const size_t need = gb + fb;
+    if (need > ctx->desc_bytes) {
+        const size_t cap = (size_t)PK_MAX_GRIDS * sizeof(DGrid) + (size_t)PK_MAX_FIELDS * sizeof(DField);
+        if (ctx->d_desc) (void)hipFree(ctx->d_desc);
+        if (ctx->h_desc) (void)hipHostFree(ctx->h_desc);
+        ctx->d_desc = ctx->h_desc = nullptr;
+        ctx->desc_bytes = 0;
+        PK_HIP(ctx, hipMalloc((void**)&ctx->d_desc, cap));
+        PK_HIP(ctx, hipHostMalloc((void**)&ctx->h_desc, 2 * cap, hipHostMallocDefault));  // staged copy + what the device holds
+        memset(ctx->h_desc, 0xFF, 2 * cap);
+        ctx->desc_bytes = cap;
+    }
+    char* stage = ctx->h_desc;                    // what this launch needs
+    char* mirror = ctx->h_desc + ctx->desc_bytes;  // what was uploaded last
+    std::vector<char> cur(need);
+    for (size_t g = 0; g < ctx->grids.size(); g++) memcpy(cur.data() + g * sizeof(DGrid), &ctx->grids[g].d, sizeof(DGrid));
+    for (size_t f = 0; f < ctx->fields.size(); f++) memcpy(cur.data() + gb + f * sizeof(DField), &ctx->fields[f].d, sizeof(DField));
+    if (need && memcmp(cur.data(), mirror, need) != 0) {
+        // the previous upload from `stage` completed long ago unless a launch is still queued behind it: wait for the stream then
+        PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
+        memcpy(stage, cur.data(), need);
+        PK_HIP(ctx, hipMemcpyAsync(ctx->d_desc, stage, need, hipMemcpyHostToDevice, ctx->compute));
+        memcpy(mirror, cur.data(), need);
+    }
+    a.grids = (const PK_CONST_AS DGrid*)ctx->d_desc;
+    a.fields = (const PK_CONST_AS DField*)(ctx->d_desc + gb);
+    return 0;
+}
+
+// Two fields a dedicated kernel addresses with one set of offsets: same dtype, layout, time levels and ring
+static bool same_layout(const DField& x, const DField& y) {
+    return x.dtype == y.dtype && x.st_t == y.st_t && x.st_z == y.st_z && x.st_y == y.st_y && x.st_x == y.st_x && x.nt == y.nt && x.nz == y.nz &&
+           x.ny == y.ny && x.nx == y.nx && x.nslots == y.nslots && x.has_time_interval == y.has_time_interval;
+}
+
+// Ravel strides of `ei` (basegrid.py:83-152), 0 for an axis the grid lacks
+static void ravel_strides(const DGrid& g, uint32_t& ex, uint32_t& ey, uint32_t& ez) {
+    uint32_t stride = 1;
+    ex = ey = ez = 0;
+    if (g.has_x) { ex = stride; stride *= (uint32_t)g.xdim; }
+    if (g.has_y) { ey = stride; stride *= (uint32_t)g.ydim; }
+    if (g.has_z) ez = stride;
+}
+
+// (Re)build `t` for (grid, field) unless it holds them already: {a, 1/width} rows of the host time axis time[0 .. nt), then of each device
+// vector of `axes`.  t.ok when every width d has a well-scaled reciprocal and the table fits `max_bytes` of LDS.  An empty table is
+// uploaded as one zero row (the kernel still binds it).
+static int32_t coord_table(pk_ctx* ctx, CoordTable& t, int grid, int field, const double* time, int nt,
+                           std::initializer_list<std::pair<const double*, int>> axes, size_t max_bytes) {
+    if (t.grid == grid && t.field == field) return 0;
+    t.grid = grid;
+    t.field = field;
+    t.ok = false;
+    std::vector<double> tab, tmp;
+    bool ok = true;
+    auto push = [&](const double* arr, int n) {
+        for (int i = 0; i < n; i++) {
+            double r = 0.0;
+            if (i + 1 < n) {
+                const double d = arr[i + 1] - arr[i];
+                r = 1.0 / d;
+                if (!(d > 1e-100 && d < 1e100) || !std::isfinite(r)) ok = false;
+            }
+            tab.push_back(arr[i]);
+            tab.push_back(r);
+        }
+    };
+    int k = 0;
+    t.off[k++] = 0;
+    push(time, nt);
+    for (const auto& [dev, n] : axes) {
+        t.off[k++] = (int32_t)(tab.size() / 2);
+        tmp.assign((size_t)std::max(n, 0), 0.0);
+        if (n > 0) PK_HIP(ctx, hipMemcpy(tmp.data(), dev, sizeof(double) * n, hipMemcpyDeviceToHost));
+        push(tmp.data(), n);
+    }
+    t.off[k] = (int32_t)(tab.size() / 2);
+    if (tab.size() * sizeof(double) > max_bytes) ok = false;
+    if (tab.empty()) tab.assign(2, 0.0);
+    if (ok) {
+        PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
+        if (tab.size() > t.cap) {
+            if (t.d) PK_HIP(ctx, hipFree(t.d));
+            PK_HIP(ctx, hipMalloc((void**)&t.d, tab.size() * sizeof(double)));
+            t.cap = tab.size();
+        }
+        PK_HIP(ctx, hipMemcpy(t.d, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    t.ok = ok;
+    return 0;
+}
+
+// Fold the descriptors of the velocity fields and their grid into the wave-uniform constants of the fast A-grid path for `prog` (PROG_RK4 /
+// PROG_RK4_3D; pk_device.h: FastA, pk_fast_agrid.h) when its preconditions hold: rectilinear grid with float64 coordinates, XLinear_Velocity,
 // U / V (/ W) plain arrays of one layout with adjacent x-corners, a time level below 4 GiB (32-bit lane offsets), and coordinate
 // vectors whose cell widths have well-scaled reciprocals.  a.fast.ok == 0 otherwise (the general program runs).
-static int32_t fill_fast(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, bool want_w) {
+static int32_t fill_fast(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, int prog) {
     FastA& F = a.fast;
     memset(&F, 0, sizeof(F));
     if (ctx->no_fast || prm->interp_uv != 0 || prm->rk45_mode) return 0;  // rk45_mode: dt follows the next_dt column (kernel.py:118-120)
+    const bool want_w = prog == PROG_RK4_3D;
     const HostField& U = ctx->fields[prm->fU];
     const HostField& V = ctx->fields[prm->fV];
     const HostField* W = (want_w && prm->fW >= 0) ? &ctx->fields[prm->fW] : nullptr;
@@ -1904,10 +1984,7 @@ static int32_t fill_fast(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, bool 
     const HostGrid& g = ctx->grids[U.d.grid];
     if (g.d.kind != 0 || g.d.lon_f32 || g.d.lat_f32 || g.d.depth_f32) return 0;
     if (V.d.grid != U.d.grid || (W && W->d.grid != U.d.grid)) return 0;
-    auto same = [](const DField& x, const DField& y) {
-        return x.ncomp == 1 && y.ncomp == 1 && x.dtype == y.dtype && x.st_t == y.st_t && x.st_z == y.st_z && x.st_y == y.st_y && x.st_x == y.st_x &&
-               x.nt == y.nt && x.nz == y.nz && x.ny == y.ny && x.nx == y.nx && x.nslots == y.nslots && x.has_time_interval == y.has_time_interval;
-    };
+    auto same = [](const DField& x, const DField& y) { return x.ncomp == 1 && y.ncomp == 1 && same_layout(x, y); };
     if (!same(U.d, V.d) || (W && !same(U.d, W->d))) return 0;
     if (V.time != U.time || (W && W->time != U.time)) return 0;
     const DField& f = U.d;
@@ -1921,59 +1998,11 @@ static int32_t fill_fast(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, bool 
     const uint64_t lvl_b = (uint64_t)f.st_t * esz;
     const uint64_t last_b = ((uint64_t)f.nz * (uint64_t)f.st_z + (uint64_t)f.ny * (uint64_t)f.st_y + (uint64_t)f.nx) * esz;
     if (lvl_b >= (1ull << 32) || last_b >= (1ull << 32)) return 0;
-    // coordinate tables, built once per (grid, field)
-    if (ctx->fast_tab_grid != U.d.grid || ctx->fast_tab_field != prm->fU) {
-        ctx->fast_tab_grid = U.d.grid;
-        ctx->fast_tab_field = prm->fU;
-        ctx->fast_tab_ok = false;
-        std::vector<double> tab;
-        bool ok = true;
-        auto push = [&](const double* arr, int n) {
-            for (int i = 0; i < n; i++) {
-                double r = 0.0;
-                if (i + 1 < n) {
-                    const double d = arr[i + 1] - arr[i];
-                    r = 1.0 / d;
-                    if (!(d > 1e-100 && d < 1e100) || !std::isfinite(r)) ok = false;
-                }
-                tab.push_back(arr[i]);
-                tab.push_back(r);
-            }
-        };
-        const int nt = f.has_time_interval ? f.nt : 0;
-        const int nz = g.d.has_z ? g.d.nz : 0, ny = g.d.has_y ? g.d.ny : 0, nx = g.d.nx;
-        ctx->fast_tab_off[0] = 0;
-        push(U.time.data(), nt);
-        ctx->fast_tab_off[1] = (int32_t)(tab.size() / 2);
-        std::vector<double> tmp;
-        auto fetch = [&](const double* dev, int n) -> int32_t {
-            tmp.assign((size_t)std::max(n, 0), 0.0);
-            if (n > 0) PK_HIP(ctx, hipMemcpy(tmp.data(), dev, sizeof(double) * n, hipMemcpyDeviceToHost));
-            return 0;
-        };
-        if (int32_t rc = fetch(g.d.depth, nz)) return rc;
-        push(tmp.data(), nz);
-        ctx->fast_tab_off[2] = (int32_t)(tab.size() / 2);
-        if (int32_t rc = fetch(g.d.lat, ny)) return rc;
-        push(tmp.data(), ny);
-        ctx->fast_tab_off[3] = (int32_t)(tab.size() / 2);
-        if (int32_t rc = fetch(g.d.lon, nx)) return rc;
-        push(tmp.data(), nx);
-        ctx->fast_tab_off[4] = (int32_t)(tab.size() / 2);
-        if (tab.size() * sizeof(double) > 60 * 1024) ok = false;  // must fit the LDS of a workgroup
-        if (ok) {
-            if (tab.size() > ctx->fast_tab_cap) {
-                PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
-                if (ctx->d_fast_tab) PK_HIP(ctx, hipFree(ctx->d_fast_tab));
-                PK_HIP(ctx, hipMalloc((void**)&ctx->d_fast_tab, tab.size() * sizeof(double)));
-                ctx->fast_tab_cap = tab.size();
-            }
-            PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
-            PK_HIP(ctx, hipMemcpy(ctx->d_fast_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        ctx->fast_tab_ok = ok;
-    }
-    if (!ctx->fast_tab_ok) return 0;
+    const CoordTable& T = ctx->tab_a;
+    if (int32_t rc = coord_table(ctx, ctx->tab_a, U.d.grid, prm->fU, U.time.data(), f.has_time_interval ? f.nt : 0,
+                                 {{g.d.depth, g.d.has_z ? g.d.nz : 0}, {g.d.lat, g.d.has_y ? g.d.ny : 0}, {g.d.lon, g.d.nx}}, 60 * 1024))
+        return rc;
+    if (!T.ok) return 0;
     const double inv_deg2m = 1.0 / g.d.deg2m;
     if (!(g.d.deg2m > 1e-100 && g.d.deg2m < 1e100) || !std::isfinite(inv_deg2m)) return 0;
     F.grid = U.d.grid;
@@ -1983,19 +2012,16 @@ static int32_t fill_fast(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, bool 
     F.nt = f.nt;
     F.nslots = f.nslots;
     F.gnz = g.d.nz; F.gny = g.d.ny; F.gnx = g.d.nx;
-    uint32_t stride = 1;
-    if (g.d.has_x) { F.ex = stride; stride *= (uint32_t)g.d.xdim; }
-    if (g.d.has_y) { F.ey = stride; stride *= (uint32_t)g.d.ydim; }
-    if (g.d.has_z) { F.ez = stride; }
+    ravel_strides(g.d, F.ex, F.ey, F.ez);
     F.st_z = (uint32_t)f.st_z;
     F.st_y = (uint32_t)f.st_y;
     F.dyb = fy ? (uint32_t)(f.st_y * esz) : 0u;
     F.dzb = fz ? (uint32_t)(f.st_z * esz) : 0u;
-    F.lds_time = ctx->fast_tab_off[0]; F.lds_depth = ctx->fast_tab_off[1]; F.lds_lat = ctx->fast_tab_off[2]; F.lds_lon = ctx->fast_tab_off[3];
-    F.lds_n = ctx->fast_tab_off[4];
+    F.lds_time = T.off[0]; F.lds_depth = T.off[1]; F.lds_lat = T.off[2]; F.lds_lon = T.off[3];
+    F.lds_n = T.off[4];
     F.lvl_b = (int64_t)lvl_b;
     F.U = (const char*)U.d.data; F.V = (const char*)V.d.data; F.W = W ? (const char*)W->d.data : nullptr;
-    F.tab = ctx->d_fast_tab;
+    F.tab = T.d;
     F.tlen = f.tlen; F.t0 = f.tfirst; F.t1 = f.tlast;
     F.z0 = g.d.zfirst; F.z1 = g.d.zlast; F.y0 = g.d.yfirst; F.y1 = g.d.ylast; F.x0 = g.d.xfirst; F.x1 = g.d.xlast;
     F.deg2m = g.d.deg2m;
@@ -2004,13 +2030,9 @@ static int32_t fill_fast(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, bool 
     return 0;
 }
 
-// Fold the descriptors of a C-grid velocity and its spherical curvilinear grid into the wave-uniform constants of the fast C-grid
-// path (pk_device.h: FastC, pk_fast_cgrid.h).  a.fastc.ok == 0 when a precondition fails (the general program runs): float64 node
-// coordinates, spherical mesh, per-cell table present, U / V (/ W) of one shape on the grid's own node counts with staggering offsets
-// in {0, 1} (then no staggered index needs clipping), a level below 2^31 elements, every search of the launch guessed.
-// The pair copies of FastC::vp for the levels that are resident right now: allocated on first use (no memory for them: the kernels read
-// the level rings), (re)packed on the compute stream -- ahead of the launch that is being prepared -- for every pair of adjacent
-// committed levels whose copy is missing or older than one of the four uploads it was made from.
+// The pair copies of FastC::vp (2-D C-grid kernels) for the levels that are resident right now: allocated on first use (no memory for
+// them: the kernels read the level rings), (re)packed on the compute stream -- ahead of the launch that is being prepared -- for every
+// pair of adjacent committed levels whose copy is missing or older than one of the four uploads it was made from.
 static void ensure_velocity_pairs(pk_ctx* ctx, const pk_exec_params* prm, FastC& F) {
     F.vp = nullptr;
     F.vp_slot_b = 0;
@@ -2090,14 +2112,20 @@ static void ensure_velocity_pairs(pk_ctx* ctx, const pk_exec_params* prm, FastC&
     F.vp_slot_b = (int64_t)slot_b;
 }
 
-static int32_t fill_fastc(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, bool want_w, size_t& lds_bytes, bool rk45 = false, bool m1 = false) {
+// Fold the descriptors of a C-grid velocity and its spherical curvilinear grid into the wave-uniform constants of the fast C-grid path for
+// `prog` (PROG_RK4 / PROG_RK4_3D / PROG_RK45 / PROG_M1; pk_device.h: FastC, pk_fast_cgrid.h).  a.fastc.ok == 0 when a precondition fails
+// (the general program runs): float64 node coordinates, spherical mesh, per-cell table present, U / V (/ W) of one shape on the grid's own
+// node counts with staggering offsets in {0, 1} (then no staggered index needs clipping), a level below 2^31 elements, every search of
+// the launch guessed (`guessed`).  The pair copies of a 2-D kernel are the launch's business (ensure_velocity_pairs).
+static int32_t fill_fastc(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, int prog, bool guessed, size_t& lds_bytes) {
     FastC& F = a.fastc;
     memset(&F, 0, sizeof(F));
+    const bool want_w = prog == PROG_RK4_3D, rk45 = prog == PROG_RK45, m1 = prog == PROG_M1;
     // the RK4 kernels reset dt every iteration (kernel.py:225-226); in RK45 mode (fieldset.RK45_tol present) dt follows next_dt, which
     // only the RK45 kernel implements -- and AdvectionRK45 itself always runs in that mode (Kernel.check_fieldsets_in_kernels)
     if (ctx->no_fast_cgrid || prm->interp_uv != 1 || (prm->rk45_mode != 0) != rk45) return 0;
     if (rk45 && !ctx->dev.next_dt) return 0;
-    if (prm->reset_state && !prm->have_guess0) return 0;  // an unguessed first search returns float32 (xsi, eta) ARRAYS (GPos::w32)
+    if (prm->reset_state && !guessed) return 0;  // an unguessed first search returns float32 (xsi, eta) ARRAYS (GPos::w32)
     const HostField& U = ctx->fields[prm->fU];
     const HostField& V = ctx->fields[prm->fV];
     const HostField* W = (want_w && prm->fW >= 0) ? &ctx->fields[prm->fW] : nullptr;
@@ -2106,10 +2134,7 @@ static int32_t fill_fastc(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, bool
     const HostGrid& g = ctx->grids[gid];
     if (g.d.kind != 1 || !g.d.spherical || g.d.lon_f32 || g.d.lat_f32 || g.d.depth_f32 || !g.d.cell_tab) return 0;
     if (V.d.grid != gid || (W && W->d.grid != gid)) return 0;
-    auto same = [](const DField& x, const DField& y) {
-        return x.ncomp == y.ncomp && x.dtype == y.dtype && x.st_t == y.st_t && x.st_z == y.st_z && x.st_y == y.st_y && x.st_x == y.st_x &&
-               x.nt == y.nt && x.nz == y.nz && x.ny == y.ny && x.nx == y.nx && x.nslots == y.nslots && x.has_time_interval == y.has_time_interval;
-    };
+    auto same = [](const DField& x, const DField& y) { return x.ncomp == y.ncomp && same_layout(x, y); };
     if (!same(U.d, V.d) || (W && !same(U.d, W->d))) return 0;
     if (V.time != U.time || (W && W->time != U.time)) return 0;
     const DField& f = U.d;
@@ -2128,48 +2153,12 @@ static int32_t fill_fastc(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, bool
     // `ei` must not wrap (the guess of the next search is the cell itself)
     if ((int64_t)std::max(g.d.xdim, 1) * std::max(g.d.ydim, 1) * std::max(g.d.zdim, 1) >= (1ll << 31)) return 0;
     if (!(g.d.deg2m > 1e-100 && g.d.deg2m < 1e100)) return 0;
-    // coordinate tables of time | depth, built once per (grid, field)
-    if (ctx->cg_tab_grid != gid || ctx->cg_tab_field != prm->fU) {
-        ctx->cg_tab_grid = gid;
-        ctx->cg_tab_field = prm->fU;
-        ctx->cg_tab_ok = false;
-        std::vector<double> tab;
-        bool ok = true;
-        auto push = [&](const double* arr, int n) {
-            for (int i = 0; i < n; i++) {
-                double r = 0.0;
-                if (i + 1 < n) {
-                    const double d = arr[i + 1] - arr[i];
-                    r = 1.0 / d;
-                    if (!(d > 1e-100 && d < 1e100) || !std::isfinite(r)) ok = false;
-                }
-                tab.push_back(arr[i]);
-                tab.push_back(r);
-            }
-        };
-        const int nt = f.has_time_interval ? f.nt : 0;
-        const int nz = g.d.has_z ? g.d.nz : 0;
-        ctx->cg_tab_off[0] = 0;
-        push(U.time.data(), nt);
-        ctx->cg_tab_off[1] = (int32_t)(tab.size() / 2);
-        std::vector<double> tmp((size_t)std::max(nz, 0), 0.0);
-        if (nz > 0) PK_HIP(ctx, hipMemcpy(tmp.data(), g.d.depth, sizeof(double) * nz, hipMemcpyDeviceToHost));
-        push(tmp.data(), nz);
-        ctx->cg_tab_off[2] = (int32_t)(tab.size() / 2);
-        if (tab.size() * sizeof(double) > 24 * 1024) ok = false;  // next to the per-lane slots in the LDS of a one-wavefront workgroup
-        if (tab.empty()) tab.assign(2, 0.0);
-        if (ok) {
-            PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
-            if (tab.size() > ctx->cg_tab_cap) {
-                if (ctx->d_cg_tab) PK_HIP(ctx, hipFree(ctx->d_cg_tab));
-                PK_HIP(ctx, hipMalloc((void**)&ctx->d_cg_tab, tab.size() * sizeof(double)));
-                ctx->cg_tab_cap = tab.size();
-            }
-            PK_HIP(ctx, hipMemcpy(ctx->d_cg_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-        ctx->cg_tab_ok = ok;
-    }
-    if (!ctx->cg_tab_ok) return 0;
+    // (next to the per-lane slots in the LDS of a one-wavefront workgroup)
+    const CoordTable& T = ctx->tab_c;
+    if (int32_t rc = coord_table(ctx, ctx->tab_c, gid, prm->fU, U.time.data(), f.has_time_interval ? f.nt : 0, {{g.d.depth, g.d.has_z ? g.d.nz : 0}},
+                                 24 * 1024))
+        return rc;
+    if (!T.ok) return 0;
     // per-cell records, built once per grid (optional: without the memory for them the general program runs)
     if (ctx->ct2_grid != gid) {
         if (ctx->d_ct2) {
@@ -2204,10 +2193,7 @@ static int32_t fill_fastc(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, bool
     F.nt = f.nt;
     F.nslots = f.nslots;
     F.gnz = g.d.nz; F.gny = g.d.ny; F.gnx = g.d.nx;
-    uint32_t stride = 1;
-    if (g.d.has_x) { F.ex = stride; stride *= (uint32_t)g.d.xdim; }
-    if (g.d.has_y) { F.ey = stride; stride *= (uint32_t)g.d.ydim; }
-    if (g.d.has_z) { F.ez = stride; }
+    ravel_strides(g.d, F.ex, F.ey, F.ez);
     F.st_z = (int32_t)f.st_z;
     F.st_y = (int32_t)f.st_y;
     const int64_t cb = (int64_t)f.ncomp * esz;
@@ -2224,7 +2210,7 @@ static int32_t fill_fastc(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, bool
     }
     F.U = (const char*)U.d.data; F.V = (const char*)V.d.data; F.W = W ? (const char*)W->d.data : nullptr;
     F.ct2 = ctx->d_ct2;
-    F.tab = ctx->d_cg_tab;
+    F.tab = T.d;
     if (m1) {  // AdvectionDiffusionM1: Kh_zonal / Kh_meridional as XLinear fields on the nodes of the same grid
         const int ids[2] = {prm->fKh_zonal, prm->fKh_meridional};
         for (int k = 0; k < 2; k++) {
@@ -2245,7 +2231,7 @@ static int32_t fill_fastc(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, bool
             F.kh_nslots[k] = kd.nslots;
         }
     }
-    F.lds_time = ctx->cg_tab_off[0]; F.lds_depth = ctx->cg_tab_off[1]; F.lds_n = ctx->cg_tab_off[2];
+    F.lds_time = T.off[0]; F.lds_depth = T.off[1]; F.lds_n = T.off[2];
     F.lds_rec = 2 * F.lds_n;
     const int cm = m1 ? CG_CACHE_M1 : (rk45 ? CG_CACHE_RK45 : CG_CACHE_RK4);  // which parts of a lane's cell cache the kernel keeps in registers
     F.lds_fv = F.lds_rec + fc_rec_rows(cm) * FC_LANES;
@@ -2253,7 +2239,6 @@ static int32_t fill_fastc(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, bool
     F.tlen = f.tlen; F.t0 = f.tfirst; F.t1 = f.tlast;
     F.z0 = g.d.zfirst; F.z1 = g.d.zlast;
     F.deg2m = g.d.deg2m;
-    if (!W) ensure_velocity_pairs(ctx, prm, F);
     F.ok = 1;
     return 0;
 }
@@ -2287,16 +2272,94 @@ static bool fill_fast_scalars(pk_ctx* ctx, const pk_exec_params* prm, FastA& F, 
         const int fid = fids[k];
         if (fid < 0 || fid >= (int)ctx->fields.size()) return false;
         const HostField& S = ctx->fields[fid];
-        const DField &x = S.d, &y = U.d;
-        const bool same = x.grid == y.grid && x.ncomp == 1 && x.dtype == y.dtype && x.st_t == y.st_t && x.st_z == y.st_z && x.st_y == y.st_y &&
-                          x.st_x == y.st_x && x.nt == y.nt && x.nz == y.nz && x.ny == y.ny && x.nx == y.nx && x.nslots == y.nslots &&
-                          x.has_time_interval == y.has_time_interval && x.is_const == 0 && S.time == U.time;
-        if (!same) return false;
+        if (S.d.grid != U.d.grid || S.d.ncomp != 1 || S.d.is_const != 0 || !same_layout(S.d, U.d) || S.time != U.time) return false;
         F.sfid[F.ns] = fid;
-        F.S[F.ns] = (const char*)x.data;
+        F.S[F.ns] = (const char*)S.d.data;
         F.ns++;
     }
     return true;
+}
+
+// What is known about the user kernels when a launch is planned: pk_execute_begin plans the launch at hand with what pk_set_user_program
+// registered; pk_generic_variant plans for the module about to be built, which has to serve every launch of its list.
+struct UserShape {
+    bool present;          // the list holds user kernels (only such a list may ride in a dedicated kernel)
+    int32_t flags;         // PK_USER_RIDE | PK_USER_SAMPLES_*
+    int nsample;           // scalar fields the user kernels sample: fids[0 .. nsample)
+    const int32_t* fids;
+    bool assume_guessed;   // plan as if the first search were guessed (the module is also launched after the unguessed first launch)
+    bool assume_unlisted;  // plan as if no time-error key were listed (a listed launch runs the interpreter every module carries)
+};
+
+struct LaunchPlan {
+    int prog = PROG_GENERIC;             // PROG_* (pk_kernels.h)
+    Dedicated kernel = DEDICATED_NONE;   // the dedicated kernel that runs it, if any (a.fast / a.fastc filled)
+    bool ride = false;                   // the user kernels ride in that dedicated kernel (else they run in the interpreter)
+    size_t lds = 0;                      // dynamic LDS bytes of the kernel that runs
+};
+
+// Which program and which kernel run a launch with `prm`, given the launch arguments (launch_args) and what is known about the user kernels.
+// Device work only for the one-time builds of the coordinate tables and of the C-grid cell table.
+static int32_t plan_launch(pk_ctx* ctx, const pk_exec_params* prm, const UserShape& us, KArgs& a, size_t lds_bytes, int use_lds, LaunchPlan& p) {
+    p = LaunchPlan{PROG_GENERIC, DEDICATED_NONE, false, lds_bytes};
+    bool rest_policy = true;  // entries after the first are the sampling-free recovery kernels
+    for (int k = 1; k < prm->nk; k++)
+        rest_policy = rest_policy && (prm->kernels[k] == PK_KERNEL_DELETE_ON_ERROR || prm->kernels[k] == PK_KERNEL_DELETE_OUT_OF_BOUNDS);
+    if (rest_policy && use_lds) {
+        if (prm->kernels[0] == PK_KERNEL_ADVECTION_RK4) p.prog = PROG_RK4;
+        if (prm->kernels[0] == PK_KERNEL_ADVECTION_RK4_3D) p.prog = PROG_RK4_3D;
+        if (prm->kernels[0] == PK_KERNEL_ADVECTION_RK45 && !ctx->no_special) p.prog = PROG_RK45;
+        if (prm->kernels[0] == PK_KERNEL_ADVECTIONDIFFUSION_M1 && !ctx->no_special) p.prog = PROG_M1;
+    }
+    if (prm->body_only) p.prog = PROG_GENERIC;  // only the kernel-list interpreter knows the mode
+    const bool typed = ctx_is_typed(ctx);
+    if (typed) p.prog = PROG_TYPED;
+    const bool curv = ctx->grids[a.main_grid].d.kind == 1;
+    // A launch that knows samples which fail call-wide (pk_exec_params.twe_key: the repeat of a call in which some particle left a
+    // field's time interval) runs the general programs: only they test the list (the dedicated kernels report such samples and pay
+    // nothing else for it); same results otherwise, which the parity tests hold them to at rtol 0.  (Round 6 built the list test into the
+    // dedicated kernels -- one scalar bit test per sample when nothing is listed -- held it bit-identical and measured it: +2.4 % on the
+    // headline kernel, +0.6 % / +1 % on RK45 / M1 through the register allocation alone (profiles/r06e_summary.txt), for repeats that only
+    // a run past the last time level makes.  Not kept.)
+    const bool listed = prm->twe_n > 0 && !us.assume_unlisted;
+    const int ufast = (us.present && use_lds && !listed && !typed) ? user_fast_shape(prm, us.flags) : -1;
+    const bool user_samples = us.nsample > 0 || (us.flags & (PK_USER_SAMPLES_UV | PK_USER_SAMPLES_UVW));
+    // the program a dedicated kernel is asked to run: the user kernels' advection kernel, or the program of a list without user kernels
+    int fast_prog = -1;
+    const bool ride = ufast >= 0 && (!curv || !user_samples);
+    if (ride) fast_prog = ufast ? PROG_RK4_3D : PROG_RK4;
+    else if (!listed && (p.prog == PROG_RK4 || p.prog == PROG_RK4_3D || (curv && (p.prog == PROG_RK45 || p.prog == PROG_M1)))) fast_prog = p.prog;
+    if (fast_prog < 0) return 0;
+    if (!curv) {
+        if (int32_t rc = fill_fast(ctx, prm, a, fast_prog)) return rc;
+        if (ride && a.fast.ok && !fill_fast_scalars(ctx, prm, a.fast, us.nsample, us.fids)) a.fast.ok = 0;
+        if (!a.fast.ok) return 0;
+        p.kernel = fast_prog == PROG_RK4_3D ? DEDICATED_A3 : DEDICATED_A2;
+        // the A-grid kernel's LDS: the coordinate tables and, behind them (2-D kernels), 64 bytes per lane of corner-block cache
+        p.lds = (size_t)a.fast.lds_n * 2 * sizeof(double);
+        const bool blk = fast_prog != PROG_RK4_3D && p.lds + (size_t)FAST_BLK_BYTES <= 64 * 1024 && !ctx->no_block_cache;
+        a.fast.lds_blk = blk ? a.fast.lds_n : 0;
+        if (blk) p.lds += (size_t)FAST_BLK_BYTES;
+    } else {
+        if (int32_t rc = fill_fastc(ctx, prm, a, fast_prog, prm->have_guess0 || us.assume_guessed, p.lds)) return rc;
+        if (!a.fastc.ok) return 0;
+        p.kernel = fast_prog == PROG_RK4_3D ? DEDICATED_C3 : DEDICATED_C2;
+    }
+    p.prog = fast_prog;
+    p.ride = ride;
+    return 0;
+}
+
+// The programs without a dedicated kernel
+static void launch_general(int prog, int field_f32, int curv, const pk_exec_params* prm, int use_lds, const KArgs& a, dim3 grid, size_t lds_bytes, hipStream_t s) {
+    switch (prog) {
+        case PROG_RK4: launch_program<PROG_RK4>(field_f32, curv, prm->interp_uv, use_lds, a, grid, lds_bytes, s); break;
+        case PROG_RK4_3D: launch_program<PROG_RK4_3D>(field_f32, curv, prm->interp_uv, use_lds, a, grid, lds_bytes, s); break;
+        case PROG_RK45: launch_program<PROG_RK45>(field_f32, curv, prm->interp_uv, use_lds, a, grid, lds_bytes, s); break;
+        case PROG_M1: launch_program<PROG_M1>(field_f32, curv, prm->interp_uv, use_lds, a, grid, lds_bytes, s); break;
+        case PROG_TYPED: launch_program<PROG_TYPED>(field_f32, curv, prm->interp_uv, use_lds, a, grid, lds_bytes, s); break;
+        default: launch_program<PROG_GENERIC>(field_f32, curv, prm->interp_uv, use_lds, a, grid, lds_bytes, s); break;
+    }
 }
 
 int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
@@ -2309,7 +2372,9 @@ int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
     KArgs a;
     size_t lds_bytes = 0;
     int use_lds = 0;
-    int32_t rc = fill_args(ctx, prm, a, lds_bytes, use_lds);
+    int32_t rc = launch_args(ctx, prm, a, lds_bytes, use_lds);
+    if (rc) return rc;
+    rc = upload_descriptors(ctx, a);
     if (rc) return rc;
     bool need_kh = false, has_user = false;
     for (int k = 0; k < prm->nk; k++) {
@@ -2366,52 +2431,11 @@ int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
     bool sorted = false;
     if (n > 0) {
         const dim3 grid((unsigned)((n + 255) / 256));
-        int prog = PROG_GENERIC;
-        bool rest_policy = true;  // entries after the first are the sampling-free recovery kernels
-        for (int k = 1; k < prm->nk; k++)
-            rest_policy = rest_policy && (prm->kernels[k] == PK_KERNEL_DELETE_ON_ERROR || prm->kernels[k] == PK_KERNEL_DELETE_OUT_OF_BOUNDS);
-        if (rest_policy && use_lds) {
-            if (prm->kernels[0] == PK_KERNEL_ADVECTION_RK4) prog = PROG_RK4;
-            if (prm->kernels[0] == PK_KERNEL_ADVECTION_RK4_3D) prog = PROG_RK4_3D;
-            if (prm->kernels[0] == PK_KERNEL_ADVECTION_RK45 && !ctx->no_special) prog = PROG_RK45;
-            if (prm->kernels[0] == PK_KERNEL_ADVECTIONDIFFUSION_M1 && !ctx->no_special) prog = PROG_M1;
-        }
-        if (prm->body_only) prog = PROG_GENERIC;  // only the kernel-list interpreter knows the mode
-        if (ctx_is_typed(ctx)) prog = PROG_TYPED;
-        if (has_user && prog != PROG_GENERIC) return ctx->fail("user kernels run in the plain kernel-list interpreter only (float32 coordinate arrays are not supported)");
-        bool fast_a = false, fast_c = false;  // a.fast / a.fastc share storage: at most one is filled
-        size_t cgrid_lds = 0;
-        // A launch that knows samples which fail call-wide (pk_exec_params.twe_key: the repeat of a call in which some particle left a
-        // field's time interval) runs the general programs: only they test the list (the dedicated kernels report such samples and pay
-        // nothing else for it); same results otherwise, which the parity tests hold them to at rtol 0.  (Round 6 built the list test into the
-        // dedicated kernels -- one scalar bit test per sample when nothing is listed -- held it bit-identical and measured it: +2.4 % on the
-        // headline kernel, +0.6 % / +1 % on RK45 / M1 through the register allocation alone (profiles/r06e_summary.txt), for repeats that only
-        // a run past the last time level makes.  Not kept.)
-        const bool listed = prm->twe_n > 0;
-        const int ufast = (has_user && use_lds && !listed) ? user_fast_shape(prm, ctx->user_flags) : -1;
-        const bool user_samples = ctx->user_nsample > 0 || (ctx->user_flags & (PK_USER_SAMPLES_UV | PK_USER_SAMPLES_UVW));
-        if (ufast >= 0 && !curv) {
-            rc = fill_fast(ctx, prm, a, ufast == 1);
-            if (rc) return rc;
-            if (a.fast.ok && !fill_fast_scalars(ctx, prm, a.fast, ctx->user_nsample, ctx->user_sample_fid)) a.fast.ok = 0;
-            fast_a = a.fast.ok != 0;
-            if (fast_a) prog = ufast ? PROG_RK4_3D : PROG_RK4;
-        } else if (ufast >= 0 && curv && !user_samples) {
-            rc = fill_fastc(ctx, prm, a, ufast == 1, cgrid_lds);
-            if (rc) return rc;
-            fast_c = a.fastc.ok != 0;
-            if (fast_c) prog = ufast ? PROG_RK4_3D : PROG_RK4;
-        } else if (listed) {
-            // (general program)
-        } else if ((prog == PROG_RK4 || prog == PROG_RK4_3D) && !curv) {
-            rc = fill_fast(ctx, prm, a, prog == PROG_RK4_3D);
-            if (rc) return rc;
-            fast_a = a.fast.ok != 0;
-        } else if ((prog == PROG_RK4 || prog == PROG_RK4_3D || prog == PROG_RK45 || prog == PROG_M1) && curv) {
-            rc = fill_fastc(ctx, prm, a, prog == PROG_RK4_3D, cgrid_lds, prog == PROG_RK45, prog == PROG_M1);
-            if (rc) return rc;
-            fast_c = a.fastc.ok != 0;
-        }
+        LaunchPlan p;
+        rc = plan_launch(ctx, prm, UserShape{has_user, ctx->user_flags, ctx->user_nsample, ctx->user_sample_fid, false, false}, a, lds_bytes, use_lds, p);
+        if (rc) return rc;
+        if (has_user && p.prog == PROG_TYPED) return ctx->fail("user kernels run in the plain kernel-list interpreter only (float32 coordinate arrays are not supported)");
+        if (p.kernel == DEDICATED_C2) ensure_velocity_pairs(ctx, prm, a.fastc);
         if (prm->sort_by_cell && !prm->body_only) {
             PK_HIP(ctx, hipEventRecord(ctx->ev2, ctx->compute));
             // curvilinear sort order (measured on the NEMO-size grid): depth-major for 3-D advection (+4 %), horizontal-major
@@ -2455,34 +2479,20 @@ int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
             PK_HIP(ctx, hipStreamWaitEvent(ctx->probe, ctx->ev_probe, 0));
         }
         PK_HIP(ctx, hipEventRecord(ctx->ev0, ctx->compute));
-        // the A-grid kernel's LDS: the coordinate tables and, behind them (2-D kernels), 64 bytes per lane of corner-block cache
-        size_t fast_lds = fast_a ? (size_t)a.fast.lds_n * 2 * sizeof(double) : 0;
-        if (fast_a) {
-            const bool blk = prog != PROG_RK4_3D && fast_lds + (size_t)FAST_BLK_BYTES <= 64 * 1024 && !getenv("PK_NO_BLOCK_CACHE");
-            a.fast.lds_blk = blk ? a.fast.lds_n : 0;
-            if (blk) fast_lds += (size_t)FAST_BLK_BYTES;
-        }
         const int pf32 = ctx->dev.spatial_f32;
-        if (has_user && fast_a) ctx->user_launch(&a, prog == PROG_RK4_3D ? 2 : 1, field_f32 * 2 + pf32, 1, (uint64_t)fast_lds, (void*)ctx->compute);
-        else if (has_user && fast_c) ctx->user_launch(&a, prog == PROG_RK4_3D ? 4 : 3, field_f32 * 2 + pf32, 1, (uint64_t)cgrid_lds, (void*)ctx->compute);
-        else if (fast_a && prog == PROG_RK4) launch_fast<PROG_RK4>(field_f32, pf32, a, grid, fast_lds, ctx->compute);
-        else if (fast_a && prog == PROG_RK4_3D) launch_fast<PROG_RK4_3D>(field_f32, pf32, a, grid, fast_lds, ctx->compute);
-        else if (fast_c && prog == PROG_RK45) launch_cgrid_rk45(field_f32, pf32, a, n, cgrid_lds, ctx->compute);
-        else if (fast_c && prog == PROG_M1) launch_cgrid_m1(field_f32, pf32, a, n, cgrid_lds, ctx->compute);
-        else if (fast_c) launch_cgrid(field_f32, pf32, prog == PROG_RK4_3D, a, n, cgrid_lds, ctx->compute);
-        else switch (prog) {
-            case PROG_RK4: launch_program<PROG_RK4>(field_f32, curv, prm->interp_uv, use_lds, a, grid, lds_bytes, ctx->compute); break;
-            case PROG_RK4_3D: launch_program<PROG_RK4_3D>(field_f32, curv, prm->interp_uv, use_lds, a, grid, lds_bytes, ctx->compute); break;
-            case PROG_RK45: launch_program<PROG_RK45>(field_f32, curv, prm->interp_uv, use_lds, a, grid, lds_bytes, ctx->compute); break;
-            case PROG_M1: launch_program<PROG_M1>(field_f32, curv, prm->interp_uv, use_lds, a, grid, lds_bytes, ctx->compute); break;
-            case PROG_TYPED: launch_program<PROG_TYPED>(field_f32, curv, prm->interp_uv, use_lds, a, grid, lds_bytes, ctx->compute); break;
-            default:
-                if (has_user) {
-                    const int ik = prm->interp_uv >= 2 ? 2 : prm->interp_uv;
-                    ctx->user_launch(&a, 0, (field_f32 ? 6 : 0) + (curv ? 3 : 0) + ik, use_lds, (uint64_t)lds_bytes, (void*)ctx->compute);
-                } else {
-                    launch_program<PROG_GENERIC>(field_f32, curv, prm->interp_uv, use_lds, a, grid, lds_bytes, ctx->compute);
-                }
+        if (p.ride) ctx->user_launch(&a, p.kernel, field_f32 * 2 + pf32, 1, (uint64_t)p.lds, (void*)ctx->compute);
+        else switch (p.kernel) {
+            case DEDICATED_A2: launch_fast<PROG_RK4>(field_f32, pf32, a, grid, p.lds, ctx->compute); break;
+            case DEDICATED_A3: launch_fast<PROG_RK4_3D>(field_f32, pf32, a, grid, p.lds, ctx->compute); break;
+            case DEDICATED_C2:
+                if (p.prog == PROG_RK45) launch_cgrid_rk45(field_f32, pf32, a, n, p.lds, ctx->compute);
+                else if (p.prog == PROG_M1) launch_cgrid_m1(field_f32, pf32, a, n, p.lds, ctx->compute);
+                else launch_cgrid(field_f32, pf32, 0, a, n, p.lds, ctx->compute);
+                break;
+            case DEDICATED_C3: launch_cgrid(field_f32, pf32, 1, a, n, p.lds, ctx->compute); break;
+            case DEDICATED_NONE:
+                if (has_user) ctx->user_launch(&a, DEDICATED_NONE, interp_key(ctx, prm, a), use_lds, (uint64_t)p.lds, (void*)ctx->compute);
+                else launch_general(p.prog, field_f32, curv, prm, use_lds, a, grid, p.lds, ctx->compute);
                 break;
         }
         PK_HIP(ctx, hipGetLastError());
@@ -2494,7 +2504,7 @@ int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
         }
         ctx->fl_clock_probe = ctx->clock_probe != 0;
         launches = 1;
-        ctx->fl_program = fast_a ? 100 : (fast_c ? 101 : prog);
+        ctx->fl_program = p.kernel == DEDICATED_NONE ? p.prog : (p.kernel <= DEDICATED_A3 ? PROGRAM_FAST_AGRID : PROGRAM_FAST_CGRID);
         swap_launch_outputs(ctx);
         ctx->rerun_valid = true;
         ctx->rerun_prm = *prm;
@@ -2609,28 +2619,17 @@ int32_t pk_generic_variant(pk_ctx* ctx, const pk_exec_params* prm, int32_t sampl
     KArgs a;
     size_t lds_bytes = 0;
     int use_lds = 0;
-    const int32_t rc = fill_args(ctx, prm, a, lds_bytes, use_lds);
+    int32_t rc = launch_args(ctx, prm, a, lds_bytes, use_lds);
     if (rc) return rc;
-    const int ik = prm->interp_uv >= 2 ? 2 : prm->interp_uv;
-    *key = (ctx->fields[prm->fU].d.dtype == PK_F32 ? 6 : 0) + (ctx->grids[a.main_grid].d.kind == 1 ? 3 : 0) + ik;
+    // the module serves every launch of the list: it is asked about as a list with user kernels that may ride
+    const UserShape us{true, PK_USER_RIDE | (sample_flags & (PK_USER_SAMPLES_UV | PK_USER_SAMPLES_UVW)), nsample, sample_fids, true, true};
+    LaunchPlan p;
+    rc = plan_launch(ctx, prm, us, a, lds_bytes, use_lds, p);
+    if (rc) return rc;
+    *key = interp_key(ctx, prm, a);
     *lds = use_lds;
     *typed = ctx_is_typed(ctx) ? 1 : 0;
-    *fast = 0;
-    const int32_t sflags = PK_USER_RIDE | (sample_flags & (PK_USER_SAMPLES_UV | PK_USER_SAMPLES_UVW));
-    const bool samples = nsample > 0 || (sample_flags & (PK_USER_SAMPLES_UV | PK_USER_SAMPLES_UVW));
-    const int ufast = (use_lds && !*typed) ? user_fast_shape(prm, sflags) : -1;
-    if (ufast >= 0 && ctx->grids[a.main_grid].d.kind != 1) {
-        const int32_t rc2 = fill_fast(ctx, prm, a, ufast == 1);
-        if (rc2) return rc2;
-        if (a.fast.ok && fill_fast_scalars(ctx, prm, a.fast, nsample, sample_fids)) *fast = 1 + ufast;
-    } else if (ufast >= 0 && !samples) {  // the dedicated curvilinear C-grid kernel (a first launch without `ei` guesses still runs the interpreter)
-        pk_exec_params guessed = *prm;
-        guessed.have_guess0 = 1;
-        size_t cl = 0;
-        const int32_t rc2 = fill_fastc(ctx, &guessed, a, ufast == 1, cl);
-        if (rc2) return rc2;
-        if (a.fastc.ok) *fast = 3 + ufast;
-    }
+    *fast = p.ride ? p.kernel : DEDICATED_NONE;
     return 0;
 }
 int32_t pk_set_user_program(pk_ctx* ctx, void* launcher, int32_t flags, int32_t nsample, const int32_t* sample_fids) {
@@ -2701,7 +2700,8 @@ int32_t pk_eval(pk_ctx* ctx, const pk_exec_params* prm, int32_t what, int64_t m,
     size_t lds_bytes;
     int use_lds;
     ctx->bound = true;
-    int32_t rc = fill_args(ctx, &p2, a, lds_bytes, use_lds);
+    int32_t rc = launch_args(ctx, &p2, a, lds_bytes, use_lds);
+    if (!rc) rc = upload_descriptors(ctx, a);
     ctx->bound = was_bound;
     ctx->dev = saved;
     if (rc) return rc;
