@@ -19,6 +19,11 @@ from .interpolators import (
     XLinearInvdistLandTracer,
     XNearest,
     XPartialslip,
+    Ux_Velocity,
+    UxConstantFaceConstantZC,
+    UxConstantFaceLinearZF,
+    UxLinearNodeConstantZC,
+    UxLinearNodeLinearZF,
 )
 from .kernel import Kernel, KernelWarning
 from .kernels import (
@@ -57,6 +62,7 @@ from .statuscodes import (
     OutsideTimeInterval,
     StatusCode,
 )
+from .uxgrid import UxGrid, UxMesh
 from .xgrid import SphericalMesh, XGrid
 
 __version__ = "0.1.0"

@@ -82,6 +82,30 @@ class GridDesc(C.Structure):
     ]
 
 
+class UGridDesc(C.Structure):  # pk_ugrid_desc
+    _fields_ = [
+        ("spherical", C.c_int32),
+        ("n_face", C.c_int32),
+        ("n_node", C.c_int32),
+        ("nz", C.c_int32),
+        ("deg2m", C.c_double),
+        ("node_lon", C.c_void_p),
+        ("node_lat", C.c_void_p),
+        ("node_xyz", C.c_void_p),
+        ("face_nodes", C.c_void_p),
+        ("zf", C.c_void_p),
+        ("h_keys", C.c_void_p),
+        ("h_starts", C.c_void_p),
+        ("h_counts", C.c_void_p),
+        ("h_faces", C.c_void_p),
+        ("h_nkeys", C.c_int64),
+        ("h_nentries", C.c_int64),
+        ("h_bitwidth", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("h_bbox", C.c_double * 6),
+    ]
+
+
 class FieldDesc(C.Structure):
     _fields_ = [
         ("grid", C.c_int32),
@@ -197,6 +221,7 @@ ABI_SYMBOLS = [
     "pk_last_error",
     "pk_get_device_info",
     "pk_grid_create",
+    "pk_ugrid_create",
     "pk_grid_hash_info",
     "pk_grid_hash_download",
     "pk_field_create",
@@ -277,6 +302,7 @@ def load():
     lib.pk_destroy.argtypes = [C.c_void_p]
     lib.pk_get_device_info.argtypes = [C.c_void_p, C.POINTER(DeviceInfo)]
     lib.pk_grid_create.argtypes = [C.c_void_p, C.POINTER(GridDesc), C.POINTER(C.c_int32)]
+    lib.pk_ugrid_create.argtypes = [C.c_void_p, C.POINTER(UGridDesc), C.POINTER(C.c_int32)]
     lib.pk_grid_hash_info.argtypes = [C.c_void_p, C.c_int32, C.POINTER(HashInfo)]
     lib.pk_grid_hash_download.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4
     lib.pk_field_create.argtypes = [C.c_void_p, C.POINTER(FieldDesc), C.POINTER(C.c_int32)]

@@ -20,6 +20,7 @@
 #include "pk_hashbuild.h"
 #include "pk_host_stage.h"
 #include "pk_kernels.h"
+#include "pk_ux.h"
 
 using namespace pk;
 
@@ -956,6 +957,87 @@ int32_t pk_grid_create(pk_ctx* ctx, const pk_grid_desc* desc, int32_t* grid_id) 
     return 0;
 }
 
+// UxGrid (uxgrid.py:16-135): a DGrid of kind PK_UX_KIND (pk_ux.h) with the per-face records of the point-in-triangle test
+int32_t pk_ugrid_create(pk_ctx* ctx, const pk_ugrid_desc* desc, int32_t* grid_id) {
+    if (!ctx || !desc || !grid_id) return -2;
+    if ((int)ctx->grids.size() >= PK_MAX_GRIDS) return ctx->fail("too many grids (PK_MAX_GRIDS)");
+    if (desc->n_face < 1 || desc->n_node < 3 || desc->nz < 2) return ctx->fail("pk_ugrid_create: n_face >= 1, n_node >= 3 and nz >= 2 (zf levels) required");
+    if (!desc->node_lon || !desc->node_lat || !desc->face_nodes || !desc->zf) return ctx->fail("pk_ugrid_create: node_lon, node_lat, face_nodes and zf are required");
+    if (desc->spherical && !desc->node_xyz) return ctx->fail("pk_ugrid_create: a spherical mesh needs node_xyz");
+    if (!desc->h_keys || !desc->h_starts || !desc->h_counts || !desc->h_faces || desc->h_nkeys < 1)
+        return ctx->fail("pk_ugrid_create: the hash table (h_keys / h_starts / h_counts / h_faces) is required");
+    const int64_t nf = desc->n_face, nn = desc->n_node;
+    for (int64_t k = 0; k < 3 * nf; k++)
+        if (desc->face_nodes[k] < 0 || desc->face_nodes[k] >= nn) return ctx->fail("pk_ugrid_create: face_nodes refers to a node that does not exist");
+    for (int64_t k = 0; k < desc->h_nentries; k++)
+        if (desc->h_faces[k] >= (uint32_t)nf) return ctx->fail("pk_ugrid_create: h_faces refers to a face that does not exist");
+    for (int64_t k = 0; k < desc->h_nkeys; k++)
+        if (desc->h_starts[k] < 0 || desc->h_counts[k] < 0 || desc->h_starts[k] + desc->h_counts[k] > desc->h_nentries)
+            return ctx->fail("pk_ugrid_create: h_starts / h_counts exceed h_nentries");
+    PK_HIP(ctx, hipSetDevice(ctx->device));
+    ctx->grids.emplace_back();
+    HostGrid& g = ctx->grids.back();
+    memset(&g.desc, 0, sizeof(g.desc));
+    g.desc.kind = PK_UX_KIND;
+    g.desc.spherical = desc->spherical;
+    g.desc.nx = desc->n_face;  // (host-side bookkeeping: pk_field_create checks the lateral extent of a field against these)
+    g.desc.ny = desc->n_node;
+    DGrid& d = g.d;
+    memset(&d, 0, sizeof(d));
+    d.kind = PK_UX_KIND;
+    d.spherical = desc->spherical;
+    d.has_x = 1; d.has_y = 0; d.has_z = 1;
+    d.nx = desc->n_face; d.ny = 1; d.nz = desc->nz;
+    d.xdim = desc->n_face; d.ydim = 0; d.zdim = desc->nz;
+    d.deg2m = desc->deg2m;
+    d.zfirst = desc->zf[0];
+    d.zlast = desc->zf[desc->nz - 1];
+    int32_t rc;
+    if ((rc = upload(ctx, g, desc->zf, (size_t)desc->nz, &d.depth))) return rc;
+    // per-face records (pk_ux.h), the query-independent part of uxgrid_point_in_cell in the reference's operation order
+    const int stride = desc->spherical ? UXF_SPH : UXF_FLAT;
+    std::vector<double> rec((size_t)nf * stride, 0.0);
+    for (int64_t f = 0; f < nf; f++) {
+        double* r = rec.data() + f * stride;
+        const int32_t* ids = desc->face_nodes + 3 * f;
+        if (desc->spherical) {
+            double V[3][3];
+            for (int k = 0; k < 3; k++)
+                for (int c = 0; c < 3; c++) V[k][c] = desc->node_xyz[c * nn + ids[k]];
+            const double r1[3] = {V[1][0] - V[0][0], V[1][1] - V[0][1], V[1][2] - V[0][2]};
+            const double r2[3] = {V[2][0] - V[0][0], V[2][1] - V[0][1], V[2][2] - V[0][2]};
+            const double c0 = r1[1] * r2[2] - r1[2] * r2[1], c1 = r1[2] * r2[0] - r1[0] * r2[2], c2 = r1[0] * r2[1] - r1[1] * r2[0];
+            double nrm = std::sqrt((c0 * c0 + c1 * c1) + c2 * c2);  // np.linalg.norm (index_search.py:341-343)
+            const double area = 0.5 * nrm;                             // _triangle_area(v0, v1, v2): the same cross product
+            if (nrm == 0.0) nrm = 1.0;
+            for (int k = 0; k < 3; k++)
+                for (int c = 0; c < 3; c++) r[3 * k + c] = V[k][c];
+            r[9] = c0 / nrm;
+            r[10] = c1 / nrm;
+            r[11] = c2 / nrm;
+            r[12] = area;
+            memcpy(r + 13, ids, 3 * sizeof(int32_t));
+        } else {
+            for (int k = 0; k < 3; k++) {
+                r[2 * k] = desc->node_lon[ids[k]];
+                r[2 * k + 1] = desc->node_lat[ids[k]];
+            }
+            memcpy(r + 6, ids, 3 * sizeof(int32_t));
+        }
+    }
+    if ((rc = upload(ctx, g, (const double*)rec.data(), rec.size(), &d.cell_tab))) return rc;
+    if ((rc = upload(ctx, g, desc->h_keys, (size_t)desc->h_nkeys, &d.h_keys))) return rc;
+    if ((rc = upload(ctx, g, desc->h_starts, (size_t)desc->h_nkeys, &d.h_starts))) return rc;
+    if ((rc = upload(ctx, g, desc->h_counts, (size_t)desc->h_nkeys, &d.h_counts))) return rc;
+    if ((rc = upload(ctx, g, desc->h_faces, (size_t)desc->h_nentries, &d.h_faces))) return rc;
+    d.h_nkeys = desc->h_nkeys;
+    g.h_nentries = desc->h_nentries;
+    d.h_bitwidth = desc->h_bitwidth;
+    for (int k = 0; k < 6; k++) d.h_bbox[k] = desc->h_bbox[k];
+    *grid_id = (int32_t)ctx->grids.size() - 1;
+    return 0;
+}
+
 int32_t pk_grid_hash_info(pk_ctx* ctx, int32_t grid, pk_hash_info* out) {
     if (!ctx || !out) return -2;
     if (grid < 0 || grid >= (int)ctx->grids.size()) return ctx->fail("unknown grid");
@@ -990,6 +1072,16 @@ int32_t pk_field_create(pk_ctx* ctx, const pk_field_desc* desc, int32_t* field_i
     if (desc->grid < 0 || desc->grid >= (int)ctx->grids.size()) return ctx->fail("field refers to an unknown grid");
     if (desc->dtype != PK_F32 && desc->dtype != PK_F64) return ctx->fail("field dtype must be PK_F32 or PK_F64");
     if (desc->nt < 1 || desc->nz < 1 || desc->ny < 1 || desc->nx < 1) return ctx->fail("field extents must be >= 1");
+    if (ctx->grids[desc->grid].d.kind == PK_UX_KIND) {  // (pk_ux.h: ux_interp reads float64 levels at face / node ids and zi, zi + 1)
+        const HostGrid& g = ctx->grids[desc->grid];
+        const int code = desc->is_const;
+        if (code < 5 || code > 8) return ctx->fail("a field on a UxGrid needs a Ux* interpolator (is_const 5-8)");
+        if (!desc->has_x || !desc->has_z || desc->has_y) return ctx->fail("a field on a UxGrid has the axes Z and X (= FACE | NODE), not Y");
+        if (desc->dtype != PK_F64) return ctx->fail("fields on a UxGrid must be float64");
+        const bool node = code >= 7, zf = code == 6 || code == 8;
+        if (desc->ny != 1 || desc->nx != (node ? g.desc.ny : g.desc.nx)) return ctx->fail("a field on a UxGrid has ny = 1 and nx = n_face (face) or n_node (node)");
+        if (desc->nz != (zf ? g.d.nz : g.d.nz - 1)) return ctx->fail("a field on a UxGrid has nz = number of zf levels (zf) or one less (zc)");
+    }
     PK_HIP(ctx, hipSetDevice(ctx->device));
     ctx->fields.emplace_back();
     HostField& f = ctx->fields.back();
@@ -1795,6 +1887,13 @@ static bool ctx_is_typed(const pk_ctx* ctx) {
     return false;
 }
 
+// some grid of the context is a UxGrid (pk_ugrid_create)
+static bool ctx_has_ugrid(const pk_ctx* ctx) {
+    for (const HostGrid& g : ctx->grids)
+        if (g.d.kind == PK_UX_KIND) return true;
+    return false;
+}
+
 // The kernel-list interpreter variant of a launch (include/parcels_hip.h: pk_generic_variant)
 static int32_t interp_key(const pk_ctx* ctx, const pk_exec_params* prm, const KArgs& a) {
     return (ctx->fields[prm->fU].d.dtype == PK_F32 ? 6 : 0) + (ctx->grids[a.main_grid].d.kind == 1 ? 3 : 0) + std::min<int>(prm->interp_uv, 2);
@@ -2302,6 +2401,21 @@ struct LaunchPlan {
 // Device work only for the one-time builds of the coordinate tables and of the C-grid cell table.
 static int32_t plan_launch(pk_ctx* ctx, const pk_exec_params* prm, const UserShape& us, KArgs& a, size_t lds_bytes, int use_lds, LaunchPlan& p) {
     p = LaunchPlan{PROG_GENERIC, DEDICATED_NONE, false, lds_bytes};
+    if (ctx_has_ugrid(ctx)) {  // a fieldset on a UxGrid: the unstructured program (pk_ux.h) and nothing else
+        if (ctx->grids[a.main_grid].d.kind != PK_UX_KIND) return ctx->fail("a launch on a context with a UxGrid needs its velocity on the UxGrid");
+        if (us.present) return ctx->fail("user kernels are not compiled for a UxGrid (they run in the host loop)");
+        if (prm->rk45_mode) return ctx->fail("AdvectionRK45 is not implemented on a UxGrid");
+        if (prm->interp_uv != 4) return ctx->fail("the velocity on a UxGrid is interpolated with Ux_Velocity (interp_uv 4)");
+        for (int k = 0; k < prm->nk; k++) {
+            const int id = prm->kernels[k];
+            if (id == PK_KERNEL_ADVECTION_RK45 || id == PK_KERNEL_ADVECTIONDIFFUSION_M1 || id == PK_KERNEL_ADVECTIONDIFFUSION_EM ||
+                id == PK_KERNEL_DIFFUSION_UNIFORM_KH || id == PK_KERNEL_SUBMERGE_THROUGH_SURFACE)
+                return ctx->fail("this built-in kernel is not implemented on a UxGrid");
+        }
+        p.prog = PROG_UX;
+        p.lds = 0;
+        return 0;
+    }
     bool rest_policy = true;  // entries after the first are the sampling-free recovery kernels
     for (int k = 1; k < prm->nk; k++)
         rest_policy = rest_policy && (prm->kernels[k] == PK_KERNEL_DELETE_ON_ERROR || prm->kernels[k] == PK_KERNEL_DELETE_OUT_OF_BOUNDS);
@@ -2436,7 +2550,7 @@ int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
         if (rc) return rc;
         if (has_user && p.prog == PROG_TYPED) return ctx->fail("user kernels run in the plain kernel-list interpreter only (float32 coordinate arrays are not supported)");
         if (p.kernel == DEDICATED_C2) ensure_velocity_pairs(ctx, prm, a.fastc);
-        if (prm->sort_by_cell && !prm->body_only) {
+        if (prm->sort_by_cell && !prm->body_only && p.prog != PROG_UX) {
             PK_HIP(ctx, hipEventRecord(ctx->ev2, ctx->compute));
             // curvilinear sort order (measured on the NEMO-size grid): depth-major for 3-D advection (+4 %), horizontal-major
             // (water columns share node-table lines) for 2-D kernels (RK45 +18 %, M1 +28 %); PK_SORT_HORIZONTAL overrides
@@ -2491,7 +2605,8 @@ int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
                 break;
             case DEDICATED_C3: launch_cgrid(field_f32, pf32, 1, a, n, p.lds, ctx->compute); break;
             case DEDICATED_NONE:
-                if (has_user) ctx->user_launch(&a, DEDICATED_NONE, interp_key(ctx, prm, a), use_lds, (uint64_t)p.lds, (void*)ctx->compute);
+                if (p.prog == PROG_UX) launch_ux(pf32, a, n, ctx->compute);
+                else if (has_user) ctx->user_launch(&a, DEDICATED_NONE, interp_key(ctx, prm, a), use_lds, (uint64_t)p.lds, (void*)ctx->compute);
                 else launch_general(p.prog, field_f32, curv, prm, use_lds, a, grid, p.lds, ctx->compute);
                 break;
         }
@@ -2719,7 +2834,8 @@ int32_t pk_eval(pk_ctx* ctx, const pk_exec_params* prm, int32_t what, int64_t m,
     const dim3 grid((unsigned)((m + 255) / 256));
     const int fsel = what >= 0 ? what : p2.fU;
     const bool f32 = ctx->fields[fsel].d.dtype == PK_F32;
-    if ((what >= 0 && ctx->fields[fsel].d.is_const == 4) || (what < 0 && p2.interp_uv >= 2)) {  // batch-global lenT / lenZ
+    const bool ux = ctx_has_ugrid(ctx);
+    if (!ux && ((what >= 0 && ctx->fields[fsel].d.is_const == 4) || (what < 0 && p2.interp_uv >= 2))) {  // batch-global lenT / lenZ
         unsigned* dflags = (unsigned*)ds;  // reused as the state output afterwards
         PK_HIP(ctx, hipMemsetAsync(dflags, 0, sizeof(unsigned), ctx->compute));
         hipLaunchKernelGGL(batch_len_kernel, grid, dim3(256), 0, ctx->compute, ctx->fields[fsel].d, ctx->grids[ctx->fields[fsel].d.grid].d, m, dt_, dz, dflags);
@@ -2730,6 +2846,11 @@ int32_t pk_eval(pk_ctx* ctx, const pk_exec_params* prm, int32_t what, int64_t m,
         a.prm.force_lenz = (hflags & 2u) ? 2 : 1;
     }
     const bool typed = ctx_is_typed(ctx);
+    if (ux) {
+        const int eg = ctx->fields[what >= 0 ? what : p2.fU].d.grid;
+        if (ctx->grids[eg].d.kind != PK_UX_KIND && what < 0) return ctx->fail("a vector field next to a UxGrid must live on the UxGrid");
+        launch_ux_eval(a, what, m, dt_, dz, dy, dx, du, dv, dw, ds, ctx->compute);
+    } else {
 #define PK_EVAL(FT, IN, TY) hipLaunchKernelGGL((eval_kernel<FT, IN, TY>), grid, dim3(256), 0, ctx->compute, a, what, m, dt_, dz, dy, dx, du, dv, dw, ds)
 #define PK_EVAL_T(FT, IN) do { if (typed) PK_EVAL(FT, IN, true); else PK_EVAL(FT, IN, false); } while (0)
     const int ik = p2.interp_uv >= 2 ? 2 : p2.interp_uv;
@@ -2740,6 +2861,7 @@ int32_t pk_eval(pk_ctx* ctx, const pk_exec_params* prm, int32_t what, int64_t m,
     }
 #undef PK_EVAL_T
 #undef PK_EVAL
+    }
     PK_HIP(ctx, hipGetLastError());
     PK_HIP(ctx, hipMemcpyAsync(out_u, du, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->compute));
     if (out_v) PK_HIP(ctx, hipMemcpyAsync(out_v, dv, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->compute));
@@ -2763,7 +2885,8 @@ int32_t pk_search(pk_ctx* ctx, int32_t grid_id, int64_t m, const double* z, cons
     PK_HIP(ctx, hipMemcpyAsync(d, z, sizeof(double) * m, hipMemcpyHostToDevice, ctx->compute));
     PK_HIP(ctx, hipMemcpyAsync(d + m, y, sizeof(double) * m, hipMemcpyHostToDevice, ctx->compute));
     PK_HIP(ctx, hipMemcpyAsync(d + 2 * m, x, sizeof(double) * m, hipMemcpyHostToDevice, ctx->compute));
-    hipLaunchKernelGGL(search_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->compute, ctx->grids[grid_id].d, m, d, d + m, d + 2 * m, de);
+    if (ctx->grids[grid_id].d.kind == PK_UX_KIND) launch_ux_search(ctx->grids[grid_id].d, m, d, d + m, d + 2 * m, de, ctx->compute);
+    else hipLaunchKernelGGL(search_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->compute, ctx->grids[grid_id].d, m, d, d + m, d + 2 * m, de);
     PK_HIP(ctx, hipGetLastError());
     PK_HIP(ctx, hipMemcpyAsync(ei_out, de, sizeof(int32_t) * m, hipMemcpyDeviceToHost, ctx->compute));
     PK_HIP(ctx, hipStreamSynchronize(ctx->compute));

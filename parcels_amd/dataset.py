@@ -47,11 +47,12 @@ def _as_da(v) -> DataArray:
 class Dataset:
     """data_vars / coords: name -> (dims, array[, attrs]); sgrid: SGrid2DMetadata."""
 
-    def __init__(self, data_vars=None, coords=None, sgrid: SGrid2DMetadata | None = None, attrs=None):
+    def __init__(self, data_vars=None, coords=None, sgrid: SGrid2DMetadata | None = None, attrs=None, uxgrid=None):
         self.data_vars = {k: _as_da(v) for k, v in (data_vars or {}).items()}
         self.coords = {k: _as_da(v) for k, v in (coords or {}).items()}
         self.sgrid = sgrid
         self.attrs = dict(attrs or {})
+        self.uxgrid = uxgrid  # parcels_amd.UxMesh of a UGRID dataset (FieldSet.from_ugrid_conventions), None otherwise
 
     @property
     def sizes(self) -> dict:
@@ -80,7 +81,7 @@ class Dataset:
         return k in self.data_vars or k in self.coords
 
     def copy(self):
-        return Dataset(dict(self.data_vars), dict(self.coords), self.sgrid, dict(self.attrs))
+        return Dataset(dict(self.data_vars), dict(self.coords), self.sgrid, dict(self.attrs), self.uxgrid)
 
     @classmethod
     def from_xarray(cls, ds):  # pragma: no cover - xarray is optional
@@ -98,3 +99,14 @@ class Dataset:
         dv = {k: (ds[k].dims, ds[k].values, dict(ds[k].attrs)) for k in ds.data_vars if k not in skip}
         co = {k: (ds[k].dims, ds[k].values, dict(ds[k].attrs)) for k in ds.coords}
         return cls(dv, co, meta, dict(ds.attrs))
+
+    @classmethod
+    def from_uxarray(cls, uxds):  # pragma: no cover - uxarray is optional
+        """A uxarray.UxDataset: its variables, coordinates and the triangle mesh (node_lon, node_lat, face_node_connectivity)."""
+        from .uxgrid import UxMesh
+
+        g = uxds.uxgrid
+        mesh = UxMesh(np.asarray(g.node_lon.values), np.asarray(g.node_lat.values), np.asarray(g.face_node_connectivity.values))
+        dv = {k: (uxds[k].dims, np.asarray(uxds[k].values), dict(uxds[k].attrs)) for k in uxds.data_vars}
+        co = {k: (uxds[k].dims, np.asarray(uxds[k].values), dict(uxds[k].attrs)) for k in uxds.coords if uxds[k].ndim == 1}
+        return cls(dv, co, None, dict(uxds.attrs), uxgrid=mesh)

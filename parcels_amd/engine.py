@@ -25,6 +25,7 @@ from .columns import LazyColumns
 from .field import Field, VectorField
 from .interpolators import CGrid_Velocity, XConstantField
 from .statuscodes import StatusCode
+from .uxgrid import UxGrid
 
 
 def _ptr(a):
@@ -112,6 +113,8 @@ class DeviceEngine:
 
     # ---- grids -----------------------------------------------------------------------------------------------
     def _create_grid(self, g) -> int:
+        if isinstance(g, UxGrid):
+            return self._create_ugrid(g)
         d = _hip.GridDesc()
         axes = g.axes
         lon, lat = np.asarray(g.lon), np.asarray(g.lat)
@@ -161,6 +164,38 @@ class DeviceEngine:
         del keep  # copied on call
         return gid.value
 
+    def _create_ugrid(self, g) -> int:
+        """pk_ugrid_create: the mesh, the zf levels and the host-built triangle hash (spatialhash.py:164-206)"""
+        m = g.uxgrid
+        d = _hip.UGridDesc()
+        d.spherical = int(g._mesh.is_spherical())
+        d.n_face, d.n_node = m.n_face, m.n_node
+        zf = np.ascontiguousarray(g.depth, dtype=np.float64)
+        d.nz = zf.shape[0]
+        d.deg2m = float(g.deg2m)
+        lon, lat = np.ascontiguousarray(m.node_lon), np.ascontiguousarray(m.node_lat)
+        faces = np.ascontiguousarray(m.face_node_connectivity, dtype=np.int32)
+        keep = [zf, lon, lat, faces]
+        d.node_lon, d.node_lat, d.face_nodes, d.zf = _ptr(lon), _ptr(lat), _ptr(faces), _ptr(zf)
+        if d.spherical:
+            xyz = np.ascontiguousarray(np.stack(m.node_xyz()), dtype=np.float64)
+            keep.append(xyz)
+            d.node_xyz = _ptr(xyz)
+        t = g.get_spatial_hash().table()
+        keys = np.ascontiguousarray(t["keys"], dtype=np.uint32)
+        starts = np.ascontiguousarray(t["starts"], dtype=np.int64)
+        counts = np.ascontiguousarray(t["counts"], dtype=np.int64)
+        hfaces = np.ascontiguousarray(t["faces"], dtype=np.uint32)
+        keep += [keys, starts, counts, hfaces]
+        d.h_keys, d.h_starts, d.h_counts, d.h_faces = _ptr(keys), _ptr(starts), _ptr(counts), _ptr(hfaces)
+        d.h_nkeys, d.h_nentries, d.h_bitwidth = keys.size, hfaces.size, int(t["bitwidth"])
+        for i, v in enumerate(np.asarray(t["bbox"], dtype=np.float64)):
+            d.h_bbox[i] = float(v)
+        gid = C.c_int32(-1)
+        self.ctx.check(self.lib.pk_ugrid_create(self.ctx.handle, C.byref(d), C.byref(gid)), "pk_ugrid_create")
+        del keep  # copied on call
+        return gid.value
+
     def hash_table(self, igrid: int = 0) -> dict:
         """The spatial-hash table resident on the device for grid ``igrid`` (same dict layout as SpatialHash.table())."""
         info = _hip.HashInfo()
@@ -193,7 +228,12 @@ class DeviceEngine:
         for f in self.scalar_fields:
             a = f.data.data
             tgt = share.get(f.name, np.float32 if np.dtype(a.dtype) == np.float32 else np.float64)
-            if is_level_source(a):
+            if isinstance(f.grid, UxGrid):  # (time, z, 1, lateral); the Ux* interpolators run on float64 levels (csrc/pk_ux.h)
+                if np.dtype(a.dtype) != np.float64:
+                    raise NotImplementedError(f"field '{f.name}' on a UxGrid: {np.dtype(a.dtype)} data is not supported on the device yet; "
+                                              "give it as float64")
+                hosts[f.name] = np.ascontiguousarray(f.model.device_layout(f.name), dtype=np.float64)
+            elif is_level_source(a):
                 fill = getattr(f.model, "level_fill_nan", {}).get(f.name, getattr(a, "fill_nan", True))
                 hosts[f.name] = _LazyLevels(a, tgt, fill_nan=fill)  # levels are read (and converted) when `_upload` asks for them
             else:  # no copy for a C-contiguous array / np.memmap of the target dtype
@@ -247,11 +287,14 @@ class DeviceEngine:
             d.grid = self.grid_ids[self.grids.index(f.grid)]
             d.dtype = _hip.PK_F64 if h.dtype == np.float64 else _hip.PK_F32
             d.nt, d.nz, d.ny, d.nx = h.shape
-            d2a = f.grid.sgrid_metadata.dim_to_axis()
-            d.has_t = int(dims[0] == "time")
-            d.has_z = int(d2a.get(dims[1]) == "Z")
-            d.has_y = int(d2a.get(dims[2]) == "Y")
-            d.has_x = int(d2a.get(dims[3]) == "X")
+            if isinstance(f.grid, UxGrid):
+                d.has_t, d.has_z, d.has_y, d.has_x = int("time" in dims), 1, 0, 1
+            else:
+                d2a = f.grid.sgrid_metadata.dim_to_axis()
+                d.has_t = int(dims[0] == "time")
+                d.has_z = int(d2a.get(dims[1]) == "Z")
+                d.has_y = int(d2a.get(dims[2]) == "Y")
+                d.has_x = int(d2a.get(dims[3]) == "X")
             tflt = f.model.time_flt
             has_ti = f.time_interval is not None and tflt is not None
             d.has_time_interval = int(has_ti)

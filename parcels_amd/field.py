@@ -23,6 +23,7 @@ from .interpolators import (
     XLinear_Velocity,
 )
 from .interpolators import CGrid_Tracer, XLinearInvdistLandTracer, XNearest  # noqa: E402
+from .interpolators import UX_SCALAR_INTERPOLATORS, Ux_Velocity  # noqa: E402
 from .statuscodes import StatusCode
 from .xgrid import XGrid
 
@@ -223,7 +224,7 @@ class Field:
     def interp_method(self, value):
         if not isinstance(value, ScalarInterpolator):
             raise ValueError(f"interp_method must be a `ScalarInterpolator` object. Got {type(value)=!r}")
-        if not isinstance(value, (XLinear, XConstantField, XNearest, CGrid_Tracer, XLinearInvdistLandTracer)):
+        if not isinstance(value, (XLinear, XConstantField, XNearest, CGrid_Tracer, XLinearInvdistLandTracer) + UX_SCALAR_INTERPOLATORS):
             raise NotImplementedError(f"{type(value).__name__} has no HIP implementation")
         self.model.field_to_interpolator[self.name] = value
         if self._fieldset is not None:  # the scalar interpolator code and the C-grid packing are part of the device descriptors
@@ -355,7 +356,7 @@ class VectorField:
     def interp_method(self, method):
         if not isinstance(method, VectorInterpolator):
             raise ValueError(f"method must be a `VectorInterpolator` object. Got {type(method)=!r}")
-        if not isinstance(method, (XLinear_Velocity, CGrid_Velocity, XFreeslip, XPartialslip)):
+        if not isinstance(method, (XLinear_Velocity, CGrid_Velocity, XFreeslip, XPartialslip, Ux_Velocity)):
             raise NotImplementedError(f"{type(method).__name__} has no HIP implementation yet")
         self._interp_method = method
         if self._fieldset is not None:  # C-grid component packing is decided when the device copy is made

@@ -157,6 +157,17 @@ class FieldSet:
                 f.interp_method = XLinear()
         return cls([model])
 
+    @classmethod
+    def from_ugrid_conventions(cls, ds, mesh="spherical", vector_fields=None):
+        """fieldset.py:233-267 / model.py:357-380: a FieldSet on an unstructured triangle mesh (UxGrid).  ``ds``: a parcels_amd.Dataset
+        that carries the mesh (``Dataset(..., uxgrid=UxMesh(...))``, or Dataset.from_uxarray) and the dims ``time``, ``zf`` and ``zc``;
+        every field has one vertical (zf | zc) and one lateral (n_face | n_node) dimension, which choose its Ux* interpolator."""
+        from .uxgrid import UnstructuredModelData
+
+        if not isinstance(ds, Dataset):
+            ds = Dataset.from_uxarray(ds)
+        return cls([UnstructuredModelData.from_ugrid_conventions(ds, mesh=mesh, vector_fields=vector_fields)])
+
     # -- device side -------------------------------------------------------------------------------------------
     def _engine_or_create(self, device: int | None = None):
         from .engine import DeviceEngine

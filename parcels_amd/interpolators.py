@@ -1,4 +1,4 @@
-"""Interpolator markers (mirrors src/parcels/interpolators/_xinterpolators.py class names).
+"""Interpolator markers (mirrors the class names of src/parcels/interpolators/_xinterpolators.py and _uxinterpolators.py).
 
 The arithmetic lives in the HIP kernels (csrc/pk_device.h: xlinear, cgrid_velocity); these classes select it,
 exactly as assigning ``Field.interp_method`` does in the reference (field.py:130-135, 244-248).
@@ -53,3 +53,27 @@ class XFreeslip(VectorInterpolator):  # _xinterpolators.py:480-490 (free-slip bo
 
 class XPartialslip(VectorInterpolator):  # _xinterpolators.py:493-502 (partial slip, a = b = 0.5)
     kind = 3
+
+
+# unstructured meshes (interpolators/_uxinterpolators.py; csrc/pk_ux.h: ux_interp).  They read time level ti only: no interpolation in time.
+class UxConstantFaceConstantZC(ScalarInterpolator):  # face-registered, layer centres (zc): piecewise constant
+    kind = 5
+
+
+class UxConstantFaceLinearZF(ScalarInterpolator):  # face-registered, layer interfaces (zf): linear in the vertical
+    kind = 6
+
+
+class UxLinearNodeConstantZC(ScalarInterpolator):  # node-registered, zc: barycentric laterally, piecewise constant vertically
+    kind = 7
+
+
+class UxLinearNodeLinearZF(ScalarInterpolator):  # node-registered, zf: barycentric laterally, linear vertically
+    kind = 8
+
+
+class Ux_Velocity(VectorInterpolator):  # noqa: N801  _uxinterpolators.py:209-229
+    kind = 4
+
+
+UX_SCALAR_INTERPOLATORS = (UxConstantFaceConstantZC, UxConstantFaceLinearZF, UxLinearNodeConstantZC, UxLinearNodeLinearZF)

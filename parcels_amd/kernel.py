@@ -19,9 +19,19 @@ import numpy as np
 from . import kernels as _k
 from .engine import raise_particle_errors
 from .statuscodes import StatusCode
+from .uxgrid import UxGrid
 
 
 _RESERVED_COLUMNS = {"t", "z", "y", "x", "dz", "dy", "dx", "dt", "next_dt", "state", "ei", "particle_id"}
+
+
+
+# built-in kernels the UxGrid program does not carry (csrc/pk_ux.h): each needs fixtures of its own first
+_NOT_ON_UXGRID = (_k.AdvectionRK45, _k.AdvectionDiffusionM1, _k.AdvectionDiffusionEM, _k.DiffusionUniformKh, _k.SubmergeParticle)
+
+
+def _on_uxgrid(fieldset) -> bool:
+    return any(isinstance(g, UxGrid) for g in fieldset.gridset)
 
 
 class KernelWarning(RuntimeWarning):
@@ -125,6 +135,8 @@ class Kernel:
         """kernel.py:122-159, including its context side effects (RK45 defaults; the tolerance is divided by
         deg2m on a spherical mesh on EVERY Kernel construction, as in the reference)."""
         fs = self.fieldset
+        if kernel in _NOT_ON_UXGRID and _on_uxgrid(fs):
+            raise NotImplementedError(f"{kernel.__name__} is not implemented on a UxGrid (unstructured mesh) yet")
         if kernel is _k.AdvectionRK45:
             if "next_dt" not in [v.name for v in self.pclass.variables]:
                 raise ValueError('ParticleClass requires a "next_dt" for AdvectionRK45 Kernel.')
@@ -152,7 +164,11 @@ class Kernel:
             raise ValueError(f"{kernel.__name__} needs a W field (UVW)")
 
     def _have_guess0(self, data) -> int:
-        g0 = self.fieldset.gridset[0]
+        grids = self.fieldset.gridset
+        ux = [i for i, g in enumerate(grids) if isinstance(g, UxGrid)]
+        if ux:  # uxgrid.py:113: np.any(ei) over the batch
+            return int(np.any(data["ei"][:, ux[0]] != 0))
+        g0 = grids[0]
         if g0.is_curvilinear and "X" in g0.axes:  # np.any(xi) over the guesses (index_search.py:269)
             xdim = max(g0.xdim, 1)
             return int(np.any(np.mod(data["ei"][:, 0].astype(np.int64), xdim) != 0))
@@ -257,7 +273,11 @@ class Kernel:
         engine = pset._engine()
         pset._t_live = None
         if self.host_functions and not self._jit_tried:
-            self._try_jit(pset)
+            if _on_uxgrid(self._fieldset):  # no compiled user kernels on a UxGrid: they run in the host loop
+                self._jit_tried = True
+                self.jit_report = "user kernels are not compiled for a UxGrid"
+            else:
+                self._try_jit(pset)
         engine.device_variables = list(self.device_variables)
         engine.bind_particles(pset._data)
         engine.h2d()

@@ -52,7 +52,7 @@ def encode_morton3d(xq, yq, zq):
 
 
 class SpatialHash:
-    """CSR Morton hash over the faces of a curvilinear XGrid (lon/lat 2-D, degrees)."""
+    """CSR Morton hash over the faces of a curvilinear XGrid (lon/lat 2-D, degrees) or of a UxGrid's triangles (from_triangles)."""
 
     def __init__(self, lon: np.ndarray, lat: np.ndarray, spherical: bool):
         lon = np.asarray(lon)
@@ -75,6 +75,10 @@ class SpatialHash:
         else:
             self.zlow = np.zeros_like(self.xlow)
             self.zhigh = np.zeros_like(self.xlow)
+        self._finish()
+
+    def _finish(self):
+        """validity mask, bitwidth budget (spatialhash.py:214-228) and the table"""
         self.face_shape = self.xlow.shape
         self.valid = ~(
             np.isnan(self.xlow) | np.isnan(self.xhigh) | np.isnan(self.ylow) | np.isnan(self.yhigh)
@@ -92,6 +96,30 @@ class SpatialHash:
                     hi = mid - 1
             self.bitwidth = lo
         self.keys, self.starts, self.counts, self.faces = self._build()
+
+    @classmethod
+    def from_triangles(cls, node_lon, node_lat, face_nodes, spherical: bool) -> "SpatialHash":
+        """The table of a UxGrid (spatialhash.py:164-206): each face's box over its 3 nodes -- in unit-sphere xyz on a spherical mesh
+        (hash grid: the xyz box of the faces' nodes), in (lon, lat) with z = 0 on a flat mesh (hash grid: the node min / max)."""
+        self = cls.__new__(cls)
+        node_lon = np.asarray(node_lon)
+        node_lat = np.asarray(node_lat)
+        nids = np.asarray(face_nodes)
+        lon, lat = node_lon[nids], node_lat[nids]
+        if spherical:
+            x, y, z = latlon_rad_to_xyz(np.deg2rad(lat), np.deg2rad(lon))
+            self.bbox = (x.min(), x.max(), y.min(), y.max(), z.min(), z.max())
+            self.zlow, self.zhigh = np.atleast_2d(np.min(z, axis=-1)), np.atleast_2d(np.max(z, axis=-1))
+        else:
+            x, y = lon, lat
+            self.bbox = (node_lon.min(), node_lon.max(), node_lat.min(), node_lat.max(), 0.0, 0.0)
+        self.xlow, self.xhigh = np.atleast_2d(np.min(x, axis=-1)), np.atleast_2d(np.max(x, axis=-1))
+        self.ylow, self.yhigh = np.atleast_2d(np.min(y, axis=-1)), np.atleast_2d(np.max(y, axis=-1))
+        if not spherical:
+            self.zlow = np.zeros_like(self.xlow)
+            self.zhigh = np.zeros_like(self.xlow)
+        self._finish()
+        return self
 
     def _quant_boxes(self, bitwidth):
         lo = quantize_coordinates(self.xlow, self.ylow, self.zlow, self.bbox, bitwidth)
