@@ -116,6 +116,13 @@ const char* pk_last_error(const pk_ctx* ctx); /* ctx may be NULL: error of the l
  *   "eval_points_f32"  0 (default); 1 = the y / x / z handed to pk_eval are float32 particle columns widened to double: the reference then
  *                      forms np.cos(np.deg2rad(y)) -- and, with float32 coordinate arrays, the barycentric coordinates -- in float32
  *                      (what a fused launch does for the default float32 Particle); set around the pk_eval calls it applies to
+ *   "block_cache"      per-lane LDS cache of the corner values in the 2-D A-grid kernel (AdvectionRK4): -1 (default) the level-pair cache
+ *                      (z-lerped corners of the two time levels around t, kept while the particle stays in its cell; 512-lane workgroups)
+ *                      when two such workgroups fit in a CU's LDS next to the coordinate tables, else the stage-pair block (t / z-lerped
+ *                      corners shared by the stage pairs 2 / 3 and 4 / 1) when it fits in 64 KB; 0 none; 1 stage-pair block; 2 level-pair
+ *                      cache or the launch fails (3-D advection, a list with compiled user kernels, tables too large).  In the library's
+ *                      2-D kernel 0 and 2 run one arithmetic and agree in every bit; PK_NO_BLOCK_CACHE (environment) = no cache at all,
+ *                      with the lerps in the reference's order
  * Environment variables PK_NO_FAST, PK_NO_FAST_CGRID, PK_NO_VELOCITY_PAIRS, PK_NO_SPECIAL, PK_NO_CELL_CACHE, PK_NO_HASH_DIR, PK_NO_CELL_TABLE, PK_SORT_HORIZONTAL give the initial
  * values. */
 int32_t pk_set_option(pk_ctx* ctx, const char* name, int32_t value);

@@ -152,6 +152,7 @@ struct pk_ctx {
     int no_fast = 0;
     int no_fast_cgrid = 0;
     bool no_block_cache = false;  // PK_NO_BLOCK_CACHE: the 2-D A-grid kernel without its per-lane corner-block cache
+    int block_cache = -1;         // option "block_cache": -1 plan_launch's rule, 0 none, 1 stage-pair block, 2 level-pair cache or fail
     // asynchronous write-out snapshots (pk_particles_snapshot_begin / _wait): two sets of device staging columns (host row order)
     // + pinned host columns, so that the D2H and the encode of interval k overlap the launch of interval k+1
     struct Snapshot {
@@ -705,6 +706,10 @@ int32_t pk_set_option(pk_ctx* ctx, const char* name, int32_t value) {
     else if (n == "cell_table") ctx->no_cell_table = !value;
     else if (n == "sort_horizontal") ctx->sort_horizontal_major = value;
     else if (n == "eval_points_f32") ctx->eval_points_f32 = value != 0;
+    else if (n == "block_cache") {
+        if (value < -1 || value > 2) return ctx->fail("pk_set_option: block_cache is -1 (planned), 0 (none), 1 (stage-pair block) or 2 (level-pair cache)");
+        ctx->block_cache = value;
+    }
     else return ctx->fail("pk_set_option: unknown option '" + n + "'");
     return 0;
 }
@@ -2395,12 +2400,13 @@ struct LaunchPlan {
     Dedicated kernel = DEDICATED_NONE;   // the dedicated kernel that runs it, if any (a.fast / a.fastc filled)
     bool ride = false;                   // the user kernels ride in that dedicated kernel (else they run in the interpreter)
     size_t lds = 0;                      // dynamic LDS bytes of the kernel that runs
+    int lp = FAST_LP_OFF;                // DEDICATED_A2: FAST_LP_* mode of the kernel (pk_fast_agrid.h)
 };
 
 // Which program and which kernel run a launch with `prm`, given the launch arguments (launch_args) and what is known about the user kernels.
 // Device work only for the one-time builds of the coordinate tables and of the C-grid cell table.
 static int32_t plan_launch(pk_ctx* ctx, const pk_exec_params* prm, const UserShape& us, KArgs& a, size_t lds_bytes, int use_lds, LaunchPlan& p) {
-    p = LaunchPlan{PROG_GENERIC, DEDICATED_NONE, false, lds_bytes};
+    p = LaunchPlan{PROG_GENERIC, DEDICATED_NONE, false, lds_bytes, FAST_LP_OFF};
     if (ctx_has_ugrid(ctx)) {  // a fieldset on a UxGrid: the unstructured program (pk_ux.h) and nothing else
         if (ctx->grids[a.main_grid].d.kind != PK_UX_KIND) return ctx->fail("a launch on a context with a UxGrid needs its velocity on the UxGrid");
         if (us.present) return ctx->fail("user kernels are not compiled for a UxGrid (they run in the host loop)");
@@ -2449,11 +2455,33 @@ static int32_t plan_launch(pk_ctx* ctx, const pk_exec_params* prm, const UserSha
         if (ride && a.fast.ok && !fill_fast_scalars(ctx, prm, a.fast, us.nsample, us.fids)) a.fast.ok = 0;
         if (!a.fast.ok) return 0;
         p.kernel = fast_prog == PROG_RK4_3D ? DEDICATED_A3 : DEDICATED_A2;
-        // the A-grid kernel's LDS: the coordinate tables and, behind them (2-D kernels), 64 bytes per lane of corner-block cache
+        // the A-grid kernel's LDS: the coordinate tables and, behind them (2-D kernels), the per-lane corner cache.  The level-pair cache
+        // (128 bytes per lane, 512-lane workgroups) when two workgroups -- 16 waves, the residency of the kernel without it -- fit in the
+        // CU's LDS (allocated in 2 KB steps at most); otherwise exactly the older choice: the stage-pair block (64 bytes per lane) when it fits
+        // in the 64 KB a workgroup gets by default, else nothing.  Only the library's own lean 2-D kernel has the level-pair modes: the 3-D
+        // kernel moves z, and a module that carries user kernels keeps the arithmetic order of the general program.
         p.lds = (size_t)a.fast.lds_n * 2 * sizeof(double);
-        const bool blk = fast_prog != PROG_RK4_3D && p.lds + (size_t)FAST_BLK_BYTES <= 64 * 1024 && !ctx->no_block_cache;
-        a.fast.lds_blk = blk ? a.fast.lds_n : 0;
-        if (blk) p.lds += (size_t)FAST_BLK_BYTES;
+        const bool lp_kernel = fast_prog == PROG_RK4 && !ride;
+        const size_t lp_lds = (p.lds + (size_t)FAST_LP_BYTES + 2047) / 2048 * 2048;
+        const bool lp_fits = 2 * lp_lds <= (size_t)160 * 1024;  // gfx950: 160 KiB per CU
+        int mode = ctx->block_cache;
+        if (ctx->no_block_cache && mode != 2) mode = 0;
+        if (mode == 2 && !(lp_kernel && lp_fits))
+            return ctx->fail(!lp_kernel ? "block_cache 2: only the library's 2-D A-grid kernel (AdvectionRK4 without user kernels) has the level-pair cache"
+                                        : "block_cache 2: the coordinate tables leave no room for the level-pair cache at 16 waves per CU");
+        if (mode < 0) mode = lp_kernel && lp_fits ? 2 : 1;
+        if (mode == 2) {
+            p.lp = FAST_LP_CACHE;
+            a.fast.lds_blk = a.fast.lds_n;
+            p.lds += (size_t)FAST_LP_BYTES;
+        } else if (mode == 0 && lp_kernel && !ctx->no_block_cache) {
+            p.lp = FAST_LP_REGS;  // the cache's arithmetic without the cache: on / off is bit-identical
+            a.fast.lds_blk = 0;
+        } else {
+            const bool blk = mode == 1 && fast_prog != PROG_RK4_3D && p.lds + (size_t)FAST_BLK_BYTES <= 64 * 1024;
+            a.fast.lds_blk = blk ? a.fast.lds_n : 0;
+            if (blk) p.lds += (size_t)FAST_BLK_BYTES;
+        }
     } else {
         if (int32_t rc = fill_fastc(ctx, prm, a, fast_prog, prm->have_guess0 || us.assume_guessed, p.lds)) return rc;
         if (!a.fastc.ok) return 0;
@@ -2596,7 +2624,10 @@ int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
         const int pf32 = ctx->dev.spatial_f32;
         if (p.ride) ctx->user_launch(&a, p.kernel, field_f32 * 2 + pf32, 1, (uint64_t)p.lds, (void*)ctx->compute);
         else switch (p.kernel) {
-            case DEDICATED_A2: launch_fast<PROG_RK4>(field_f32, pf32, a, grid, p.lds, ctx->compute); break;
+            case DEDICATED_A2:
+                if (p.lp != FAST_LP_OFF) PK_HIP(ctx, launch_fast_lp(p.lp, field_f32, pf32, a, p.lds, ctx->compute));
+                else launch_fast<PROG_RK4>(field_f32, pf32, a, grid, p.lds, ctx->compute);
+                break;
             case DEDICATED_A3: launch_fast<PROG_RK4_3D>(field_f32, pf32, a, grid, p.lds, ctx->compute); break;
             case DEDICATED_C2:
                 if (p.prog == PROG_RK45) launch_cgrid_rk45(field_f32, pf32, a, n, p.lds, ctx->compute);

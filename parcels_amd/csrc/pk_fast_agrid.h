@@ -26,7 +26,8 @@ struct FastTabs {  // LDS-resident {a, 1/width} tables of the main grid and the 
     const pk_tab2* depth;
     const pk_tab2* lat;
     const pk_tab2* lon;
-    pk_tab2* blk;  // this lane's corner-block cache (FCtx::bei): 4 x 16 bytes at stride FAST_WG, NULL = none
+    pk_tab2* blk;  // this lane's corner-block cache (FCtx::bei): 4 x 16 bytes at stride FAST_WG (stage-pair block), or 8 x 16 bytes at stride
+                   // FAST_WG_LP (level-pair cache: the Z0 and D rows of U and V, eval_uvw_fast); NULL = none
     uint32_t fl;   // FA_* bits of the wave-uniform yes / no questions of one evaluation (fast_flags)
     // Scalars of FastA that every evaluation reads, PINNED in scalar registers by the kernel (pin_scalars: an opaque asm makes them values
     // the allocator may spill to a VGPR lane -- one v_readlane where it is used -- but can no longer re-load from the kernel-argument
@@ -99,6 +100,16 @@ PK_DEV double fast_bary(double x, double a, double a1, double rw) {
 }
 constexpr int FAST_WG = 256;                          // lanes per workgroup of advect_fast_kernel
 constexpr int FAST_BLK_BYTES = FAST_WG * 8 * 8;       // LDS of the corner-block cache per workgroup (8 doubles per lane)
+// Modes of the 2-D kernel's corner cache (template parameter LP of eval_uvw_fast / advect_fast_kernel; pk_set_option "block_cache"):
+//   FAST_LP_OFF   the stage-pair block of FCtx::bei, or nothing (wave-uniform at run time: FA_BLK), lerps in the reference's order;
+//   FAST_LP_REGS  the level-pair arithmetic (lp_field) with Z0 / D formed in registers in every evaluation: the A/B partner of the cache;
+//   FAST_LP_CACHE the level-pair cache: Z0 / D of the lane's cell live in its LDS slot across evaluations.
+// The cache needs 128 bytes per lane: with 256-lane workgroups the 32 KB + tables allow three workgroups per CU (12 waves), so this mode
+// runs 512-lane workgroups, two of which fill the 16 wave slots of a CU (4 per SIMD) when 2 x (tables + 64 KB) fit in the 160 KB of LDS.
+constexpr int FAST_LP_OFF = 0, FAST_LP_REGS = 1, FAST_LP_CACHE = 2;
+constexpr int FAST_WG_LP = 512;                       // lanes per workgroup of advect_fast_kernel<.., FAST_LP_CACHE>
+constexpr int FAST_LP_BYTES = FAST_WG_LP * 16 * 8;    // LDS of the level-pair cache per workgroup (16 doubles per lane)
+constexpr int fast_wg(int lp) { return lp == FAST_LP_CACHE ? FAST_WG_LP : FAST_WG; }
 
 // clip(searchsorted(arr, x, "left") - 1, 0, n-2) over the interleaved table.  Cold (a lane that moved two cells or more, or holds a
 // NaN): one bisection loop -- the unrolled three-step walk of rounds 1-5 found the same index and cost the hot path seven nesting
@@ -331,6 +342,54 @@ PK_DEV void uvw_fast(const FastA& F, int64_t o0, int64_t o1, uint32_t b00, doubl
     }
 }
 
+// ---- level-pair cache (2-D kernel, PK_FAST_LEAN builds) --------------------------------------------------------------------------
+// The z-lerped corner values of the two time levels, Z0[c] = zlerp(level ti), Z1[c] = zlerp(level ti + 1) (c: the four (y, x) corners, for U
+// and V), depend on the cell, on z (which a 2-D kernel never moves) and on the level pair only -- not on the stage time.  They are kept
+// per lane as Z0 and D = Z1 - Z0 and only the last lerp runs per evaluation:
+//     Zk[c] = fma(zeta, d_k[c] - c_k[c], c_k[c])   (lenZ; else c_k[c])        D[c] = Z1[c] - Z0[c]   (lenT; else 0: level ti + 1 is not read)
+//     v[c]  = fma(tau, D[c], Z0[c])
+// ONE arithmetic whether the values come out of LDS or were just formed (FAST_LP_REGS forms them in every evaluation): a lane's result does
+// not depend on its wavefront's other lanes, on launch splits or on the cache.  Against the reference's order (t first, then z, each
+// a*(1-w) + b*w) the positions move by a few 1e-15 relative (the class of change PK_FAST_LEAN is).
+struct LpField {  // Z0 and D of one field: rows y (0) and y+1 (1) of two x-neighbours
+    pk_tab2 z0, z1, d0, d1;
+};
+template <class FT, bool LT, bool LZ>
+PK_DEV void lp_field(LpField& f, const char* l0, const char* l1, uint32_t bo, uint32_t dyb, uint32_t dzb, double zeta) {
+    Rows r;
+    load_rows<FT, LT, LZ>(r, l0, l1, bo, dyb, dzb);
+#if PK_FAST_BATCH >= 8
+    PK_FIELD_FENCE();
+#endif
+    double a00 = r.c00, a01 = r.c01, a10 = r.c10, a11 = r.c11;
+    if (LZ) {
+        a00 = fma(zeta, r.d00 - a00, a00); a01 = fma(zeta, r.d01 - a01, a01);
+        a10 = fma(zeta, r.d10 - a10, a10); a11 = fma(zeta, r.d11 - a11, a11);
+    }
+    f.z0.x = a00; f.z0.y = a01; f.z1.x = a10; f.z1.y = a11;
+    f.d0.x = f.d0.y = f.d1.x = f.d1.y = 0.0;
+    if (LT) {
+        double b00 = r.t00, b01 = r.t01, b10 = r.t10, b11 = r.t11;
+        if (LZ) {
+            b00 = fma(zeta, r.e00 - b00, b00); b01 = fma(zeta, r.e01 - b01, b01);
+            b10 = fma(zeta, r.e10 - b10, b10); b11 = fma(zeta, r.e11 - b11, b11);
+        }
+        f.d0.x = b00 - a00; f.d0.y = b01 - a01; f.d1.x = b10 - a10; f.d1.y = b11 - a11;
+    }
+}
+// Z0 / D of U and V at the lane's cell
+template <class FT, bool LT, bool LZ>
+PK_DEV void lp_fetch(const FastA& F, int64_t o0, int64_t o1, uint32_t b00, double zeta, LpField& fu, LpField& fv) {
+    uint32_t bo = b00;  // (opaque lane offset: see uvw_fast)
+    asm volatile("" : "+v"(bo));
+    lp_field<FT, LT, LZ>(fu, F.U + o0, F.U + o1, bo, F.dyb, F.dzb, zeta);
+    lp_field<FT, LT, LZ>(fv, F.V + o0, F.V + o1, bo, F.dyb, F.dzb, zeta);
+}
+PK_DEV double lp_sum(const LpField& f, double tau, double w00, double w01, double w10, double w11) {
+    const double v00 = fma(tau, f.d0.x, f.z0.x), v01 = fma(tau, f.d0.y, f.z0.y), v10 = fma(tau, f.d1.x, f.z1.x), v11 = fma(tau, f.d1.y, f.z1.y);
+    return w00 * v00 + w01 * v01 + w10 * v10 + w11 * v11;
+}
+
 PK_DEV int uniform_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // Per-particle evaluation context of the fast kernels.  Besides the status code and the `ei` entry of the velocity grid it holds
@@ -350,6 +409,9 @@ struct FCtx {
     // and the bilinear sum runs on the same values -- the same operations, so the same bits (measured: 0.998 / 1.000 of the wave-evaluations
     // of those two stage pairs on BASELINE config 2).  Invariant: bei >= 0 => the slot holds the block of cell bei at (mt, mz).
     int32_t bei;
+    // Level-pair cache (FAST_LP_CACHE): the slot holds Z0 / D of cell `bei` at depth mz for the wave-uniform key `bkey` of eval_uvw_fast
+    // (ti << 2 | lenT << 1 | lenZ); a new depth drops the block, a new time alone does not.
+    int32_t bkey;
 };
 constexpr int32_t FAST_NO_BLOCK = -0x7fffffff - 1;
 PK_DEV void fctx_init(FCtx& c, int state, int32_t ei) {
@@ -360,12 +422,14 @@ PK_DEV void fctx_init(FCtx& c, int state, int32_t ei) {
     c.mt = c.mz = __builtin_nan("");  // equal to nothing
     c.mtau = c.mzeta = 0.0;
     c.bei = FAST_NO_BLOCK;
+    c.bkey = -1;
 }
 
 // VectorField.eval (field.py:250-304) + XLinear_Velocity.interp (_xinterpolators.py:169-190).  PF: the sample point may come
 // straight from float32 particle storage (pos_f32); D3: sample W as well.  bmode (wave-uniform; FCtx::bei): bit 0 = this sample may
 // share (t, z) with the previous one -- test the cached corner block; bit 1 = the next one may share them with this one -- keep the block.
-template <class FT, bool PF, bool D3>
+// LP (2-D, PK_FAST_LEAN builds): FAST_LP_* -- the level-pair arithmetic, from registers or from the lane's LDS slot; bmode is not used then.
+template <class FT, bool PF, bool D3, int LP = FAST_LP_OFF>
 PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, double z, double y, double x, bool pos_f32, double& u,
                           double& v, double& w, unsigned it, int klo, int bmode = 0) {
     const FastA& F = a.fast;
@@ -385,7 +449,7 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
             int idx;
             fast_search<true>(T.time, F.nt, F.t0, F.t1, t, c.ht, idx, c.mtau, (fl & FA_NT2) != 0);  // level times start at 0 (host check): idx == c.ht
             c.mt = t;
-            c.bei = FAST_NO_BLOCK;
+            if (LP == FAST_LP_OFF) c.bei = FAST_NO_BLOCK;  // (the level-pair block does not depend on t: its key holds ti and lenT)
         }
         ti = c.ht;
         tau = c.mtau;
@@ -429,39 +493,84 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
     const double omt = 1 - tau, omz = 1 - zeta, omx = 1 - xsi, ome = 1 - eta;
     const double w00 = omx * ome, w01 = xsi * ome, w10 = omx * eta, w11 = xsi * eta;
     double uu = 0.0, vv = 0.0, ww = 0.0;
-    const bool bc = !D3 && PK_FAST_BLOCK_CACHE && (fl & FA_BLK) != 0;
-    // (in-bounds indices ravel to a non-negative `ei` that names the cell; the memo updates above already dropped a block of another (t, z))
-    bool reuse = false;
-    if (bc && (bmode & 1)) reuse = __builtin_amdgcn_ballot_w64(c.ei != c.bei) == 0;  // every active lane: same cell, same (t, z)
-    if (reuse) {
-        const pk_tab2 b0 = T.blk[0], b1 = T.blk[FAST_WG], b2 = T.blk[2 * FAST_WG], b3 = T.blk[3 * FAST_WG];
-        uu = w00 * b0.x + w01 * b0.y + w10 * b1.x + w11 * b1.y;
-        vv = w00 * b2.x + w01 * b2.y + w10 * b3.x + w11 * b3.y;
-    } else {
-        const bool keep = bc && (bmode & 2);
-        pk_tab2* const blk = keep ? T.blk : nullptr;
-        for (bool done = false; !done;) {
-            // everything derived from the wave-uniform key is formed BEFORE the lane test: inside `if (key == uk)` the optimiser
-            // may substitute the (divergent) key for uk, which would move the level arithmetic back into vector registers
-            const int uk = uniform_i32(key);
-            const int uti = uk >> 2;
-            int s0 = uti, s1 = uti + 1;  // has_ti: 0 <= ti <= nt-2; otherwise ti == 0 and the second level is never read
-            if (fl & FA_RING) {          // ring of time levels: level L lives in slot L % nslots
-                s0 = (int)((uint32_t)s0 % (uint32_t)F.nslots);
-                s1 = (int)((uint32_t)s1 % (uint32_t)F.nslots);
+    if constexpr (LP != FAST_LP_OFF) {
+        static_assert(!D3, "the level-pair arithmetic is the 2-D kernel's (z must not move)");
+        LpField fu, fv;
+        // FAST_LP_CACHE: only the lanes whose cell, depth or level pair changed since their block was formed fetch (a divergent branch most
+        // wave-evaluations of the odd stages skip and ~1.3 lanes take in the even ones); FAST_LP_REGS: every lane, every evaluation
+        const bool miss = LP == FAST_LP_REGS || c.ei != c.bei || key != c.bkey;
+        if (LP == FAST_LP_REGS || __builtin_amdgcn_ballot_w64(miss) != 0) {
+            // the waterfall over the key, as below (level bases stay in SGPRs); a lane that hit starts as done
+            for (bool done = !miss; !done;) {
+                const int uk = uniform_i32(key);
+                const int uti = uk >> 2;
+                int s0 = uti, s1 = uti + 1;
+                if (fl & FA_RING) {
+                    s0 = (int)((uint32_t)s0 % (uint32_t)F.nslots);
+                    s1 = (int)((uint32_t)s1 % (uint32_t)F.nslots);
+                }
+                int64_t o0 = (int64_t)s0 * F.lvl_b, o1 = (int64_t)s1 * F.lvl_b;
+                int lens = uk & 3;
+                asm volatile("" : "+s"(o0), "+s"(o1), "+s"(lens));
+                if (key == uk) {
+                    if (lens == 3) lp_fetch<FT, true, true>(F, o0, o1, b00, zeta, fu, fv);
+                    else if (lens == 2) lp_fetch<FT, true, false>(F, o0, o1, b00, zeta, fu, fv);
+                    else if (lens == 1) lp_fetch<FT, false, true>(F, o0, o1, b00, zeta, fu, fv);
+                    else lp_fetch<FT, false, false>(F, o0, o1, b00, zeta, fu, fv);
+                    done = true;
+                }
             }
-            int64_t o0 = (int64_t)s0 * F.lvl_b, o1 = (int64_t)s1 * F.lvl_b;
-            int lens = uk & 3;
-            asm volatile("" : "+s"(o0), "+s"(o1), "+s"(lens));  // opaque scalars: no path back to the divergent key
-            if (key == uk) {
-                if (lens == 3) uvw_fast<FT, D3, true, true>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
-                else if (lens == 2) uvw_fast<FT, D3, true, false>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
-                else if (lens == 1) uvw_fast<FT, D3, false, true>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
-                else uvw_fast<FT, D3, false, false>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
-                done = true;
+            // The block goes to LDS BEHIND the waterfall, from the registers FAST_LP_REGS uses.  (Written inside it -- U's entries between the two
+            // load batches, 4 VGPRs and 12 B of scratch less -- lanes of a wavefront that spans several level pairs read back other values
+            // than they had formed: tests/test_gpu_level_pair_cache.py::test_staggered_release_times_and_ring.)
+            if (LP == FAST_LP_CACHE && miss) {
+                T.blk[0] = fu.z0; T.blk[FAST_WG_LP] = fu.z1; T.blk[2 * FAST_WG_LP] = fu.d0; T.blk[3 * FAST_WG_LP] = fu.d1;
+                T.blk[4 * FAST_WG_LP] = fv.z0; T.blk[5 * FAST_WG_LP] = fv.z1; T.blk[6 * FAST_WG_LP] = fv.d0; T.blk[7 * FAST_WG_LP] = fv.d1;
+                c.bei = c.ei;
+                c.bkey = key;
             }
         }
-        if (keep) c.bei = c.ei;
+        if (LP == FAST_LP_CACHE) {
+            fu.z0 = T.blk[0]; fu.z1 = T.blk[FAST_WG_LP]; fu.d0 = T.blk[2 * FAST_WG_LP]; fu.d1 = T.blk[3 * FAST_WG_LP];
+            fv.z0 = T.blk[4 * FAST_WG_LP]; fv.z1 = T.blk[5 * FAST_WG_LP]; fv.d0 = T.blk[6 * FAST_WG_LP]; fv.d1 = T.blk[7 * FAST_WG_LP];
+        }
+        uu = lp_sum(fu, tau, w00, w01, w10, w11);
+        vv = lp_sum(fv, tau, w00, w01, w10, w11);
+    } else {
+        const bool bc = !D3 && PK_FAST_BLOCK_CACHE && (fl & FA_BLK) != 0;
+        // (in-bounds indices ravel to a non-negative `ei` that names the cell; the memo updates above already dropped a block of another (t, z))
+        bool reuse = false;
+        if (bc && (bmode & 1)) reuse = __builtin_amdgcn_ballot_w64(c.ei != c.bei) == 0;  // every active lane: same cell, same (t, z)
+        if (reuse) {
+            const pk_tab2 b0 = T.blk[0], b1 = T.blk[FAST_WG], b2 = T.blk[2 * FAST_WG], b3 = T.blk[3 * FAST_WG];
+            uu = w00 * b0.x + w01 * b0.y + w10 * b1.x + w11 * b1.y;
+            vv = w00 * b2.x + w01 * b2.y + w10 * b3.x + w11 * b3.y;
+        } else {
+            const bool keep = bc && (bmode & 2);
+            pk_tab2* const blk = keep ? T.blk : nullptr;
+            for (bool done = false; !done;) {
+                // everything derived from the wave-uniform key is formed BEFORE the lane test: inside `if (key == uk)` the optimiser
+                // may substitute the (divergent) key for uk, which would move the level arithmetic back into vector registers
+                const int uk = uniform_i32(key);
+                const int uti = uk >> 2;
+                int s0 = uti, s1 = uti + 1;  // has_ti: 0 <= ti <= nt-2; otherwise ti == 0 and the second level is never read
+                if (fl & FA_RING) {          // ring of time levels: level L lives in slot L % nslots
+                    s0 = (int)((uint32_t)s0 % (uint32_t)F.nslots);
+                    s1 = (int)((uint32_t)s1 % (uint32_t)F.nslots);
+                }
+                int64_t o0 = (int64_t)s0 * F.lvl_b, o1 = (int64_t)s1 * F.lvl_b;
+                int lens = uk & 3;
+                asm volatile("" : "+s"(o0), "+s"(o1), "+s"(lens));  // opaque scalars: no path back to the divergent key
+                if (key == uk) {
+                    if (lens == 3) uvw_fast<FT, D3, true, true>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
+                    else if (lens == 2) uvw_fast<FT, D3, true, false>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
+                    else if (lens == 1) uvw_fast<FT, D3, false, true>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
+                    else uvw_fast<FT, D3, false, false>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
+                    done = true;
+                }
+            }
+            if (keep) c.bei = c.ei;
+        }
     }
     if (fl & FA_SPH) {  // _xinterpolators.py:183-187
         double conv;

@@ -701,15 +701,18 @@ PK_DEV void side_kernel_fast(const KArgs& a, const FastTabs& ft, FCtx& fc, int k
 #ifndef PK_MIN_WAVES_FAST
 #define PK_MIN_WAVES_FAST 4
 #endif
-template <class FT, int PFM, bool D3>
-__global__ void __launch_bounds__(256, PK_MIN_WAVES_FAST) advect_fast_kernel(const KArgs a) {
+// LP: FAST_LP_* (pk_fast_agrid.h) -- how the 2-D kernel forms / caches its corner values; the level-pair cache runs 512-lane workgroups
+// (its LDS slot is 128 bytes per lane: two workgroups fill the 16 wave slots of a CU).  The only barrier is the one behind the table staging.
+template <class FT, int PFM, bool D3, int LP = FAST_LP_OFF>
+__global__ void __launch_bounds__(fast_wg(LP), PK_MIN_WAVES_FAST) advect_fast_kernel(const KArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int WG = fast_wg(LP);
     FastTabs ft;
     {
         // {a[i], 1 / (a[i+1] - a[i])} tables of time | depth | lat | lon, staged once per workgroup (coalesced 16-byte copies)
         pk_tab2* s_tab = reinterpret_cast<pk_tab2*>(smem);
         const pk_tab2* g_tab = reinterpret_cast<const pk_tab2*>(a.fast.tab);
-        for (int k = threadIdx.x; k < a.fast.lds_n; k += 256) s_tab[k] = g_tab[k];
+        for (int k = threadIdx.x; k < a.fast.lds_n; k += WG) s_tab[k] = g_tab[k];
         __syncthreads();
         ft.time = s_tab + a.fast.lds_time;
         ft.depth = s_tab + a.fast.lds_depth;
@@ -721,7 +724,7 @@ __global__ void __launch_bounds__(256, PK_MIN_WAVES_FAST) advect_fast_kernel(con
                 (a.prm.max_iters > 0 ? FA_MAXIT : 0u);
     }
     // the row index is re-derived where it is needed (entry and exit) instead of living in two registers across the step loop
-    auto row = [&]() { return (int64_t)xcd_swizzle(blockIdx.x, gridDim.x) * 256 + threadIdx.x; };
+    auto row = [&]() { return (int64_t)xcd_swizzle(blockIdx.x, gridDim.x) * WG + threadIdx.x; };
     unsigned steps = 0, attempts = 0, paused = 0;  // per lane and launch: 32 bits are plenty
     if (row() < a.p.n) {
         int64_t i = row();
@@ -782,7 +785,7 @@ __global__ void __launch_bounds__(256, PK_MIN_WAVES_FAST) advect_fast_kernel(con
                     double u, v, w;
                     // stages 2 / 3 share t, stage 4 and stage 1 of the next step too: the odd evaluations keep their corner block, the even
                     // ones test it (pk_fast_agrid.h: FCtx::bei)
-                    eval_uvw_fast<FT, pf, D3>(a, ft, c, st, sz, sy, sx, pf && stage == 0, u, v, w, it, adv * 1000 + stage, (stage & 1) ? 2 : 1);
+                    eval_uvw_fast<FT, pf, D3, LP>(a, ft, c, st, sz, sy, sx, pf && stage == 0, u, v, w, it, adv * 1000 + stage, (stage & 1) ? 2 : 1);
                     if (stage == 0) { su = u; sv = v; sw = w; }
                     else if (stage == 3) { su = su + u; sv = sv + v; sw = sw + w; }
                     else { su = su + 2 * u; sv = sv + 2 * v; sw = sw + 2 * w; }
@@ -1369,6 +1372,9 @@ void launch_program(int field_f32, int curvilinear, int interp, int lds, const K
 // fast single-kernel programs (pk_fast_agrid.h): one TU per program defines launch_fast<PROG>
 template <int PROG>
 void launch_fast(int field_f32, int particles_f32, const KArgs& a, dim3 grid, size_t lds_bytes, hipStream_t stream);
+// AdvectionRK4 in the level-pair modes (lp: FAST_LP_REGS / FAST_LP_CACHE; a translation unit of its own): the grid is derived from the
+// mode's workgroup size, and the cache's workgroups may ask for more dynamic LDS than the 64 KB a kernel gets without saying so
+hipError_t launch_fast_lp(int lp, int field_f32, int particles_f32, const KArgs& a, size_t lds_bytes, hipStream_t stream);
 
 #define PK_LAUNCH_FAST_CASE(FT, PF) \
     hipLaunchKernelGGL((advect_fast_kernel<FT, PF, KIDV == PK_KERNEL_ADVECTION_RK4_3D>), grid, dim3(256), lds_bytes, stream, a)
@@ -1381,6 +1387,23 @@ void launch_fast(int field_f32, int particles_f32, const KArgs& a, dim3 grid, si
         } else {                                                                                                        \
             if (particles_f32) PK_LAUNCH_FAST_CASE(double, 1); else PK_LAUNCH_FAST_CASE(double, 0);                     \
         }                                                                                                               \
+    }
+
+#define PK_LAUNCH_FAST_LP_CASE(FT, PF, LP)                                                                                          \
+    do {                                                                                                                            \
+        constexpr int WG = fast_wg(LP);                                                                                             \
+        auto kern = advect_fast_kernel<FT, PF, false, LP>;                                                                          \
+        if (lds_bytes > 64 * 1024) {                                                                                                \
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
+            if (e != hipSuccess) return e;                                                                                          \
+        }                                                                                                                           \
+        hipLaunchKernelGGL(kern, dim3((unsigned)((a.p.n + WG - 1) / WG)), dim3(WG), lds_bytes, stream, a);                          \
+    } while (0)
+#define PK_LAUNCH_FAST_LP_KEYS(LP)                                                                                 \
+    if (field_f32) {                                                                                               \
+        if (particles_f32) PK_LAUNCH_FAST_LP_CASE(float, 1, LP); else PK_LAUNCH_FAST_LP_CASE(float, 0, LP);        \
+    } else {                                                                                                       \
+        if (particles_f32) PK_LAUNCH_FAST_LP_CASE(double, 1, LP); else PK_LAUNCH_FAST_LP_CASE(double, 0, LP);      \
     }
 
 // PK_PRINT_OCCUPANCY=1: what the runtime will co-schedule of the chosen instantiation (workgroups per CU at this LDS size)

@@ -20,7 +20,8 @@ CSRC = os.path.join(ROOT, "parcels_amd", "csrc")
 LLVM = "/opt/rocm/lib/llvm/bin"
 # bench key -> (object, demangled kernel name)
 KERNELS = {
-    "AdvectionRK4": ("pk_prog_rk4_fast.o", "void pk::advect_fast_kernel<double, 0, false>(pk::KArgs)"),
+    # (the headline launch runs the level-pair-cache instantiation: pk_fast_agrid.h FAST_LP_CACHE = 2)
+    "AdvectionRK4": ("pk_prog_rk4_fast_lp.o", "void pk::advect_fast_kernel<double, 0, false, 2>(pk::KArgs)"),
     "AdvectionRK4_3D": ("pk_prog_cgrid_fast.o", "void pk::advect_cgrid_kernel<float, 0, true, true>(pk::KArgs)"),
     "AdvectionRK45": ("pk_prog_cgrid_fast.o", "void pk::advect_cgrid_rk45_kernel<float, 0, true>(pk::KArgs)"),
     "AdvectionDiffusionM1": ("pk_prog_cgrid_fast.o", "void pk::advect_cgrid_m1_kernel<float, 0, true>(pk::KArgs)"),
