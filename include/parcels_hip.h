@@ -76,6 +76,12 @@ typedef struct pk_ctx pk_ctx;
 #define PK_SAMPLE_UV (-2)
 #define PK_SAMPLE_UVW (-3)
 #define PK_SAMPLE_DISCARD 0xFF
+/* CROCO sigma grids (src/parcels/kernels/_sigmagrids.py; csrc/pk_sigma.h).  Both need pk_set_croco on the context.
+ * PK_KERNEL_ADVECTION_RK2_3D_CROCO: AdvectionRK2_3D_CROCO (_sigmagrids.py:38-72), thirteen field evaluations per step; needs params.fW.
+ * PK_KERNEL_SAMPLE_SIGMA_CROCO: SampleOmegaCroco (_sigmagrids.py:28-35) for any scalar field: convert_z_to_sigma_croco at the particle, then
+ * `particles.<var> = fieldset.<F>[t, sigma, y, x, particles]` with F / var from sample_field / sample_var of the slot (scalar form). */
+#define PK_KERNEL_ADVECTION_RK2_3D_CROCO 11
+#define PK_KERNEL_SAMPLE_SIGMA_CROCO 12
 #define PK_KERNEL_DELETE_ON_ERROR 20
 #define PK_KERNEL_DELETE_OUT_OF_BOUNDS 21
 #define PK_KERNEL_SUBMERGE_THROUGH_SURFACE 22
@@ -420,7 +426,8 @@ typedef struct pk_exec_stats {
     int32_t launches;
     int32_t program; /* which device program ran (diagnostic; same results whichever): 0-5 the general programs RK4, RK4_3D, kernel-list
                         interpreter, RK45, M1, dtype-emulating interpreter; 100 the dedicated A-grid kernels (csrc/pk_fast_agrid.h), 101 the
-                        dedicated curvilinear C-grid kernels (csrc/pk_fast_cgrid.h), 6 the UxGrid program (csrc/pk_ux.h)  */
+                        dedicated curvilinear C-grid kernels (csrc/pk_fast_cgrid.h), 6 the UxGrid program (csrc/pk_ux.h), 7 the CROCO sigma-grid
+                        program (csrc/pk_sigma.h)  */
     int64_t first_error_iter; /* 0 = no particle entered an error state (or StopAllExecution); else the smallest 1-based index of the
                         iteration of the loop of kernel.py:190 in which one did (kernel.py:236-245 raises after THAT iteration)          */
     int64_t first_time_error_key; /* 0 = no sample of this launch left a field's time interval; else the smallest key (see
@@ -487,6 +494,17 @@ int32_t pk_eval(pk_ctx* ctx, const pk_exec_params* params, int32_t what, int64_t
 /* XGrid.search + ravel_index with no guess: ei_out[i] = ravel(search(z, y, x)) on grid `grid_id`
  * (ParticleSet.populate_indices, particleset.py:252-262).  Host arrays of length m. */
 int32_t pk_search(pk_ctx* ctx, int32_t grid_id, int64_t m, const double* z, const double* y, const double* x, int32_t* ei_out);
+
+/* ---- CROCO sigma grids (src/parcels/kernels/_sigmagrids.py) -------------------------------------- */
+/* The CROCO parameters of a context, read by PK_KERNEL_ADVECTION_RK2_3D_CROCO / PK_KERNEL_SAMPLE_SIGMA_CROCO and pk_sigma_croco: field ids of
+ * `fieldset.h` and `fieldset.zeta`, `fieldset.hc`, and the n >= 2 values of `fieldset.U.grid.depth` (sigma_levels, float64) and of
+ * `fieldset.Cs_w.data.values.flatten()` (cs_w, widened to float64 by the caller; cs_w_f32: they are float32 data -- NumPy's dtype rules then
+ * differ, _sigmagrids.py:17).  Uploaded once; may be called again to replace them. */
+int32_t pk_set_croco(pk_ctx* ctx, int32_t field_h, int32_t field_zeta, double hc, int32_t n, const double* sigma_levels, const double* cs_w,
+                     int32_t cs_w_f32);
+/* convert_z_to_sigma_croco(fieldset, t, z, y, x, None) (_sigmagrids.py:6-25) at m explicit points: host arrays of length m; with no particle
+ * both inner samples are detached (no guess, no state: field.py:145-195).  The device function behind the two kernels. */
+int32_t pk_sigma_croco(pk_ctx* ctx, int64_t m, const double* t, const double* z, const double* y, const double* x, double* out_sigma);
 
 /* achieved copy bandwidth probe (device-to-device float4 copy), GB/s; used as a measured roofline denominator */
 int32_t pk_measure_copy_bandwidth(pk_ctx* ctx, int64_t bytes, int32_t iters, double* gbps);

@@ -32,6 +32,7 @@ from .kernels import (
     AdvectionEE,
     AdvectionRK2,
     AdvectionRK2_3D,
+    AdvectionRK2_3D_CROCO,
     AdvectionRK4,
     AdvectionRK4_3D,
     AdvectionRK45,
@@ -42,7 +43,10 @@ from .kernels import (
     MoveEast,
     MoveNorth,
     SampleField,
+    SampleFieldCroco,
+    SampleOmegaCroco,
     SubmergeParticle,
+    convert_z_to_sigma_croco,
 )
 from .particle import Particle, ParticleClass, Variable, get_default_particle
 from .particlefile import ParticleFile, read_particlefile

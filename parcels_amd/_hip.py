@@ -19,6 +19,8 @@ PK_MAX_GRIDS, PK_MAX_FIELDS, PK_MAX_KERNELS, PK_NUM_STATE_CODES = 4, 64, 8, 80
 PK_MAX_EXTRA = 8
 PK_MAX_TWE = 1024
 PK_KERNEL_SAMPLE_FIELD = 10
+PK_KERNEL_ADVECTION_RK2_3D_CROCO = 11
+PK_KERNEL_SAMPLE_SIGMA_CROCO = 12
 PK_EVAL_MASKED = 0x10000  # pk_eval: or'ed into out_state where the value was zeroed for an out-of-bounds index
 PK_COL_EXTRA0 = 0x1000
 PK_COL_T, PK_COL_Z, PK_COL_Y, PK_COL_X, PK_COL_DT, PK_COL_STATE, PK_COL_PARTICLE_ID = 0x001, 0x002, 0x004, 0x008, 0x080, 0x200, 0x800
@@ -254,6 +256,8 @@ ABI_SYMBOLS = [
     "pk_execute_twe_report",
     "pk_eval",
     "pk_search",
+    "pk_set_croco",
+    "pk_sigma_croco",
     "pk_measure_copy_bandwidth",
     "pk_set_option",
     "pk_upload_stats",
@@ -336,6 +340,8 @@ def load():
     lib.pk_execute_twe_report.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_int32]
     lib.pk_eval.argtypes = [C.c_void_p, C.POINTER(ExecParams), C.c_int32, C.c_int64] + [C.c_void_p] * 8
     lib.pk_search.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pk_set_croco.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
+    lib.pk_sigma_croco.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5
     lib.pk_measure_copy_bandwidth.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_double)]
     lib.pk_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
     lib.pk_upload_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]

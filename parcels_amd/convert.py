@@ -18,6 +18,10 @@ _NEMO_DEPTH_DIMS = {"depthu": "depth_center", "depthv": "depth_center", "deptht"
 _NEMO_KEEP_DIMS = ("x", "y", "time", "x_center", "y_center", "depth", "depth_center")  # convert.py:44-56
 
 
+_CROCO_REQUIRED_COORDS = ("x_rho", "y_rho", "s_w", "time")  # convert.py:122-124
+_CROCO_VARNAMES = {"x_rho": "lon", "y_rho": "lat", "s_w": "depth"}  # convert.py:126-130
+
+
 def _field_da(name, src) -> DataArray:
     if isinstance(src, Dataset):  # convert.py:333-335: a dataset holding the field under its name
         src = src[name]
@@ -108,5 +112,44 @@ def nemo_to_sgrid(*, fields: dict, coords) -> Dataset:
         cf_role="grid_topology", topology_dimension=2, node_dimensions=("x", "y"), node_coordinates=("lon", "lat"),
         face_dimensions=(FaceNodePadding("x_center", "x", Padding.LOW), FaceNodePadding("y_center", "y", Padding.LOW)),
         vertical_dimensions=(FaceNodePadding("depth_center", "depth", Padding.HIGH),),
+    )
+    return Dataset(out_vars, out_coords, sgrid=md)
+
+
+def croco_to_sgrid(*, fields: dict, coords) -> Dataset:
+    """CROCO output -> SGRID-annotated Dataset (``parcels.convert.croco_to_sgrid``, src/parcels/convert.py:469-523).
+
+    fields: name -> (dims, array[, attrs]) / DataArray / Dataset containing ``name``, with CROCO dimension names (``time, s_rho | s_w,
+    eta_rho | eta_v, xi_rho | xi_u``; ``h`` on ``(eta_rho, xi_rho)``, ``Cs_w`` on ``(s_w,)``); coords: Dataset (or dict) with ``x_rho, y_rho``
+    (1-D or 2-D, in metres or degrees), ``s_w`` and ``time``.
+
+    The rho points are the nodes: ``x_rho, y_rho, s_w`` become ``lon, lat, depth`` (the sigma levels are the grid's depth axis), faces
+    ``xi_u:xi_rho`` and ``eta_v:eta_rho`` with padding high, vertical ``s_rho:depth`` with padding high -- C-grid index offsets X = Y = Z = 0.
+    A float ``time`` becomes timedelta64[ns] (``units`` attribute: hours / days / minutes, seconds by default; convert.py:228-246).
+    """
+    if not isinstance(coords, Dataset):
+        coords = Dataset({}, dict(coords))
+    for required in _CROCO_REQUIRED_COORDS:  # convert.py:133-136
+        if required not in coords:
+            raise ValueError(f"Expected coordinate '{required}' not found in provided coords dataset.")
+    rename = lambda dims: tuple(_CROCO_VARNAMES.get(d, d) for d in dims)  # noqa: E731  (s_w is a dimension coordinate: the dimension follows)
+    out_coords = {}
+    for name in _CROCO_REQUIRED_COORDS:
+        da = coords[name]
+        out_coords[_CROCO_VARNAMES.get(name, name)] = DataArray(rename(da.dims), da.data, da.attrs)
+    t = out_coords["time"]
+    if np.issubdtype(np.asarray(t.data).dtype, np.floating):
+        units = str(t.attrs.get("units", "")).lower()
+        factor = 3600.0 * 1e9 if "hour" in units else 86400.0 * 1e9 if "day" in units else 60.0 * 1e9 if "minute" in units else 1e9
+        ns = np.rint(np.asarray(t.data) * factor).astype("int64")
+        out_coords["time"] = DataArray(t.dims, ns.astype("timedelta64[ns]"), {k: v for k, v in t.attrs.items() if k != "units"})
+    out_vars = {}
+    for name, src in fields.items():
+        da = _field_da(name, src)
+        out_vars[name] = DataArray(rename(da.dims), da.data, da.attrs)
+    md = SGrid2DMetadata(  # convert.py:506-521
+        cf_role="grid_topology", topology_dimension=2, node_dimensions=("lon", "lat"), node_coordinates=("lon", "lat"),
+        face_dimensions=(FaceNodePadding("xi_u", "xi_rho", Padding.HIGH), FaceNodePadding("eta_v", "eta_rho", Padding.HIGH)),
+        vertical_dimensions=(FaceNodePadding("s_rho", "depth", Padding.HIGH),),
     )
     return Dataset(out_vars, out_coords, sgrid=md)

@@ -21,6 +21,7 @@
 #include "pk_host_stage.h"
 #include "pk_kernels.h"
 #include "pk_ux.h"
+#include "pk_sigma.h"
 
 using namespace pk;
 
@@ -143,6 +144,10 @@ struct pk_ctx {
     unsigned long long* d_tstats = nullptr;   // pk_particles_t_stats: {ordered min, ordered max, NaN count} (its own 24 bytes: not the clock-probe buffer)
     unsigned long long* d_clk = nullptr;      // clock probes around the advection kernel: [before | after][XCD 0..7]{shader-clock counter, 100 MHz counter}
     unsigned long long* h_clk = nullptr;      // pinned
+    // CROCO sigma grids (pk_set_croco): the {s_k, Cs_k} pairs on the device and what the kernels need beside them (pk_sigma.h)
+    double* d_sigma = nullptr;
+    SigmaA sigma{};
+    bool has_sigma = false;
     int sort_horizontal_major = -1;  // tuning knobs (environment: PK_SORT_HORIZONTAL = 0/1 forces, PK_NO_SPECIAL, PK_NO_CELL_CACHE)
     int no_special = 0;
     bool eval_points_f32 = false;  // pk_eval: the sample points are float32 particle columns (np.cos(np.deg2rad(y)) is then a float32 cosine)
@@ -786,6 +791,7 @@ int32_t pk_destroy(pk_ctx* ctx) {
     if (ctx->tab_c.d) (void)hipFree(ctx->tab_c.d);
     if (ctx->d_ct2) (void)hipFree(ctx->d_ct2);
     if (ctx->d_vp) (void)hipFree(ctx->d_vp);
+    if (ctx->d_sigma) (void)hipFree(ctx->d_sigma);
     if (ctx->d_counters) (void)hipFree(ctx->d_counters);
     if (ctx->d_twe) (void)hipFree(ctx->d_twe);
     if (ctx->d_twe_found) (void)hipFree(ctx->d_twe_found);
@@ -2422,6 +2428,18 @@ static int32_t plan_launch(pk_ctx* ctx, const pk_exec_params* prm, const UserSha
         p.lds = 0;
         return 0;
     }
+    bool croco = false;
+    for (int k = 0; k < prm->nk; k++) croco = croco || prm->kernels[k] == PK_KERNEL_ADVECTION_RK2_3D_CROCO || prm->kernels[k] == PK_KERNEL_SAMPLE_SIGMA_CROCO;
+    if (croco) {  // a list with a CROCO kernel: the sigma-grid program (pk_sigma.h), whatever built-in kernels stand beside it
+        if (!ctx->has_sigma) return ctx->fail("a CROCO kernel needs the CROCO parameters of the context (pk_set_croco)");
+        if (us.present) return ctx->fail("user kernels are not compiled next to a CROCO kernel (they run in the host loop)");
+        if (ctx_is_typed(ctx)) return ctx->fail("the CROCO kernels need float64 coordinate arrays");
+        if (prm->interp_uv != 0 && prm->interp_uv != 1) return ctx->fail("the CROCO program interpolates the velocity with XLinear_Velocity or CGrid_Velocity");
+        p.prog = PROG_SIGMA;
+        p.lds = (size_t)ctx->sigma.n * 2 * sizeof(double);
+        a.sigma = ctx->sigma;
+        return 0;
+    }
     bool rest_policy = true;  // entries after the first are the sampling-free recovery kernels
     for (int k = 1; k < prm->nk; k++)
         rest_policy = rest_policy && (prm->kernels[k] == PK_KERNEL_DELETE_ON_ERROR || prm->kernels[k] == PK_KERNEL_DELETE_OUT_OF_BOUNDS);
@@ -2531,6 +2549,12 @@ int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
         }
         if ((id == PK_KERNEL_ADVECTION_RK4_3D || id == PK_KERNEL_ADVECTION_RK2_3D) && prm->fW < 0)
             return ctx->fail("3-D advection needs the W field");
+        if (id == PK_KERNEL_ADVECTION_RK2_3D_CROCO && prm->fW < 0) return ctx->fail("AdvectionRK2_3D_CROCO needs the W field");
+        if (id == PK_KERNEL_SAMPLE_SIGMA_CROCO) {
+            const int sf = prm->sample_field[k], v = prm->sample_var[k];
+            if (sf < 0 || sf >= (int)ctx->fields.size()) return ctx->fail("PK_KERNEL_SAMPLE_SIGMA_CROCO: params.sample_field names no scalar field");
+            if (v < 0 || v >= ctx->host.n_extra) return ctx->fail("PK_KERNEL_SAMPLE_SIGMA_CROCO: params.sample_var names no extra particle column");
+        }
         if (id == PK_KERNEL_SAMPLE_FIELD) {
             const int sf = prm->sample_field[k];
             const bool vec = sf == PK_SAMPLE_UV || sf == PK_SAMPLE_UVW;
@@ -2637,6 +2661,7 @@ int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
             case DEDICATED_C3: launch_cgrid(field_f32, pf32, 1, a, n, p.lds, ctx->compute); break;
             case DEDICATED_NONE:
                 if (p.prog == PROG_UX) launch_ux(pf32, a, n, ctx->compute);
+                else if (p.prog == PROG_SIGMA) launch_sigma(field_f32, curv, prm->interp_uv, a, n, p.lds, ctx->compute);
                 else if (has_user) ctx->user_launch(&a, DEDICATED_NONE, interp_key(ctx, prm, a), use_lds, (uint64_t)p.lds, (void*)ctx->compute);
                 else launch_general(p.prog, field_f32, curv, prm, use_lds, a, grid, p.lds, ctx->compute);
                 break;
@@ -2923,6 +2948,72 @@ int32_t pk_search(pk_ctx* ctx, int32_t grid_id, int64_t m, const double* z, cons
     PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
     PK_HIP(ctx, hipFree(d));
     PK_HIP(ctx, hipFree(de));
+    return 0;
+}
+
+// ---- CROCO sigma grids (pk_sigma.h) ---------------------------------------------------------------------
+int32_t pk_set_croco(pk_ctx* ctx, int32_t field_h, int32_t field_zeta, double hc, int32_t n, const double* sigma_levels, const double* cs_w,
+                     int32_t cs_w_f32) {
+    if (!ctx || !sigma_levels || !cs_w) return -2;
+    const int nf = (int)ctx->fields.size();
+    if (field_h < 0 || field_h >= nf || field_zeta < 0 || field_zeta >= nf) return ctx->fail("pk_set_croco: h / zeta name no field");
+    if (n < 2) return ctx->fail("pk_set_croco: at least two sigma levels");
+    if ((size_t)n * 16 > 48 * 1024) return ctx->fail("pk_set_croco: too many sigma levels for the workgroup's LDS");
+    if (ctx->in_flight) return ctx->fail("pk_set_croco: a launch is in flight (call pk_execute_end)");
+    PK_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<double> pairs((size_t)n * 2);
+    for (int k = 0; k < n; k++) {
+        pairs[2 * k] = sigma_levels[k];
+        pairs[2 * k + 1] = cs_w[k];
+    }
+    PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
+    if (ctx->d_sigma) (void)hipFree(ctx->d_sigma);
+    ctx->d_sigma = nullptr;
+    ctx->has_sigma = false;
+    PK_HIP(ctx, hipMalloc((void**)&ctx->d_sigma, pairs.size() * sizeof(double)));
+    PK_HIP(ctx, hipMemcpy(ctx->d_sigma, pairs.data(), pairs.size() * sizeof(double), hipMemcpyHostToDevice));
+    ctx->sigma = SigmaA{ctx->d_sigma, n, field_h, field_zeta, cs_w_f32 ? 1 : 0, hc};
+    ctx->has_sigma = true;
+    return 0;
+}
+
+int32_t pk_sigma_croco(pk_ctx* ctx, int64_t m, const double* t, const double* z, const double* y, const double* x, double* out_sigma) {
+    if (!ctx || !t || !z || !y || !x || !out_sigma) return -2;
+    if (!ctx->has_sigma) return ctx->fail("pk_sigma_croco needs the CROCO parameters of the context (pk_set_croco)");
+    if (ctx_is_typed(ctx)) return ctx->fail("the CROCO conversion needs float64 coordinate arrays");
+    PK_HIP(ctx, hipSetDevice(ctx->device));
+    if (m <= 0) return 0;
+    pk_exec_params p2;
+    memset(&p2, 0, sizeof(p2));
+    p2.nk = 1;
+    p2.fU = p2.fV = ctx->sigma.fh;
+    p2.fW = p2.fKh_zonal = p2.fKh_meridional = -1;
+    DParticles saved = ctx->dev;
+    const bool was_bound = ctx->bound;
+    KArgs a;
+    size_t lds_bytes;
+    int use_lds;
+    ctx->bound = true;
+    int32_t rc = launch_args(ctx, &p2, a, lds_bytes, use_lds);
+    if (!rc) rc = upload_descriptors(ctx, a);
+    ctx->bound = was_bound;
+    ctx->dev = saved;
+    if (rc) return rc;
+    a.sigma = ctx->sigma;
+    double* d = nullptr;
+    PK_HIP(ctx, hipMalloc((void**)&d, sizeof(double) * m * 5));
+    hipError_t e = hipSuccess;  // (no early return between hipMalloc and hipFree)
+    const double* src[4] = {t, z, y, x};
+    for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipMemcpyAsync(d + k * m, src[k], sizeof(double) * m, hipMemcpyHostToDevice, ctx->compute);
+    if (e == hipSuccess) {
+        launch_sigma_points(a, m, d, d + m, d + 2 * m, d + 3 * m, d + 4 * m, (size_t)ctx->sigma.n * 2 * sizeof(double), ctx->compute);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_sigma, d + 4 * m, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->compute);
+    const hipError_t es = hipStreamSynchronize(ctx->compute);
+    (void)hipFree(d);
+    PK_HIP(ctx, e);
+    PK_HIP(ctx, es);
     return 0;
 }
 

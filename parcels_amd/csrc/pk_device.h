@@ -156,6 +156,16 @@ struct FastC {
     double tlen, t0, t1, z0, z1, deg2m;
 };
 
+// CROCO sigma grids (pk_sigma.h): what pk_set_croco registered.  Shares the union of the dedicated kernels' constants in KArgs, whose
+// size and layout stay as they are.
+struct SigmaA {
+    const double* tab;      // device copy of the {s_k, Cs_k} pairs: sigma levels of the velocity grid's depth axis and Cs_w
+    int32_t n;              // number of levels
+    int32_t fh, fzeta;      // field ids of h and zeta
+    int32_t cs_f32;         // Cs_w is float32 data
+    double hc;              // fieldset.hc
+};
+
 // The grid / field descriptors of a context live in ONE device buffer (uploaded before a launch when they changed), not in the kernel
 // arguments: the kernarg segment is 4 KiB, and 4 grids + 16 fields used 3 KiB of it -- one more descriptor member and the design had to
 // change (and any code shape that made the compiler take the address of the by-value argument cost a 4 KiB private copy per lane).
@@ -179,6 +189,7 @@ struct KArgs {
     union {  // at most one of the dedicated kernels runs per launch
         FastA fast;
         FastC fastc;
+        SigmaA sigma;
     };
 };
 

@@ -742,6 +742,11 @@ class DeviceEngine:
         p.nk = len(kernel_ids)
         for i, k in enumerate(kernel_ids):
             p.kernels[i] = int(k)
+        if any(int(k) in (_hip.PK_KERNEL_ADVECTION_RK2_3D_CROCO, _hip.PK_KERNEL_SAMPLE_SIGMA_CROCO) for k in kernel_ids):
+            # every launch with a CROCO kernel -- fused, or one body_only pass of the host loop -- needs the CROCO parameters on the context
+            from .kernel import croco_parameters
+
+            self.set_croco(croco_parameters(fs))
         uv = fs.fields.get("UV")
         uvw = fs.fields.get("UVW")
         vec = uvw if uvw is not None else uv
@@ -1078,6 +1083,34 @@ class DeviceEngine:
         if self.agree_codes is not None:
             total["codes_any_shard"] = self._agree_on_codes({})
         return total
+
+    # ---- CROCO sigma grids (csrc/pk_sigma.h) -------------------------------------------------------------------------------------
+    def set_croco(self, par: dict):
+        """pk_set_croco: the CROCO parameters of the context (kernel.croco_parameters), uploaded once per engine and set of values"""
+        key = (par["hc"], par["sigma_levels"].tobytes(), np.asarray(par["cs_w"]).tobytes(), bool(par["cs_w_f32"]))
+        if getattr(self, "_croco_key", None) == key:
+            return
+        sl = np.ascontiguousarray(par["sigma_levels"], dtype=np.float64)
+        cs = np.ascontiguousarray(par["cs_w"], dtype=np.float64)  # (widening float32 is exact)
+        self.ctx.check(self.lib.pk_set_croco(self.ctx.handle, self.field_ids["h"], self.field_ids["zeta"], float(par["hc"]), int(sl.size),
+                                             _ptr(sl), _ptr(cs), int(bool(par["cs_w_f32"]))), "pk_set_croco")
+        self._croco_key = key
+
+    def sigma_croco(self, par: dict, t, z, y, x):
+        """convert_z_to_sigma_croco(fieldset, t, z, y, x, None) on the device (pk_sigma_croco)"""
+        if self.windowed:
+            raise NotImplementedError("convert_z_to_sigma_croco at explicit points needs every time level resident (no ring of levels)")
+        tflt = self.fieldset.zeta.model.time_flt if self.fieldset.zeta.time_interval is not None else None
+        if tflt is not None and np.size(t) and not (np.all(np.asarray(t) >= 0) and np.all(np.asarray(t) <= tflt[-1])):
+            from .statuscodes import OutsideTimeInterval  # (index_search.py:85-86: the reference raises for the whole call)
+
+            raise OutsideTimeInterval("convert_z_to_sigma_croco: some t lies outside the time interval of field zeta")
+        self.set_croco(par)
+        t, z, y, x = (np.ascontiguousarray(v, dtype=np.float64) for v in np.broadcast_arrays(*(np.atleast_1d(np.asarray(v)) for v in (t, z, y, x))))
+        out = np.zeros(x.shape[0])
+        if x.shape[0]:
+            self.ctx.check(self.lib.pk_sigma_croco(self.ctx.handle, x.shape[0], _ptr(t), _ptr(z), _ptr(y), _ptr(x), _ptr(out)), "pk_sigma_croco")
+        return out
 
     # ---- sampling (Field.eval / VectorField.eval) ---------------------------------------------------------------
     def sample(self, name, t, z, y, x):

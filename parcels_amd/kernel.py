@@ -34,6 +34,55 @@ def _on_uxgrid(fieldset) -> bool:
     return any(isinstance(g, UxGrid) for g in fieldset.gridset)
 
 
+def _is_croco(kernel) -> bool:
+    return kernel is _k.AdvectionRK2_3D_CROCO or getattr(kernel, "_pk_sample_sigma", None) is not None
+
+
+def croco_parameters(fieldset, who="a CROCO kernel") -> dict:
+    """What the sigma conversion reads of a CROCO fieldset (_sigmagrids.py:12-17), checked: the fields h, zeta and Cs_w, the context hc,
+    the sigma levels (depth axis of the velocity grid).  ValueError naming what is missing; NotImplementedError for a mix of float32 and
+    float64 among h, zeta, Cs_w and W."""
+    fs = fieldset
+    for name in ("h", "zeta", "Cs_w"):
+        f = fs.fields.get(name)
+        if f is None or hasattr(f, "U"):
+            raise ValueError(f"{who} needs the field {name}")
+    if "hc" not in fs.context:
+        raise ValueError(f"{who} needs fieldset.add_context('hc', ...)")
+    if "U" not in fs.fields:
+        raise ValueError(f"{who} needs the field U (its grid's depth axis holds the sigma levels)")
+    grid = fs.U.grid
+    if "Z" not in grid.axes:
+        raise ValueError(f"{who}: the velocity grid has no depth axis (the sigma levels s_w)")
+    sigma_levels = np.ascontiguousarray(grid.depth, dtype=np.float64)
+    cs = fs.Cs_w.data
+    d2a = fs.Cs_w.grid.sgrid_metadata.dim_to_axis()
+    arr = np.asarray(cs.data)
+    if any(n != 1 and d2a.get(d) != "Z" for d, n in zip(cs.dims, arr.shape)) or arr.size != sigma_levels.size:
+        raise ValueError(f"{who}: Cs_w must be a field whose only non-singleton axis is the depth axis, of the grid's {sigma_levels.size} "
+                         f"levels; got dims {cs.dims} of shape {arr.shape}")
+    if sigma_levels.size < 2:
+        raise ValueError(f"{who} needs at least two sigma levels")
+    if "time" in fs.h.data.dims and fs.h.data.shape[0] > 1:
+        raise NotImplementedError(f"{who}: a time-varying bathymetry h is not supported (the reference has none either)")
+    for g in fs.gridset:
+        if any(np.asarray(c).dtype == np.float32 for c in (g.lon, g.lat, g.depth)):
+            raise NotImplementedError(f"{who} needs float64 coordinate arrays (lon, lat, depth); a grid of the fieldset stores float32")
+    for vname in ("UV", "UVW"):
+        vf = fs.fields.get(vname)
+        if vf is not None and int(vf.interp_method.kind) not in (0, 1):
+            raise NotImplementedError(f"{who}: the velocity must be interpolated with XLinear_Velocity or CGrid_Velocity, "
+                                      f"{vname} has {type(vf.interp_method).__name__}")
+    dts = {name: np.dtype(np.asarray(fs.fields[name].data.data).dtype if not hasattr(fs.fields[name].data.data, "read_level")
+                          else fs.fields[name].data.data.dtype) for name in ("h", "zeta", "Cs_w", "W") if name in fs.fields}
+    kinds = {np.dtype(np.float32) if dt == np.float32 else np.dtype(np.float64) for dt in dts.values()}
+    if len(kinds) > 1:
+        odd = [n for n, dt in dts.items() if dt != dts["h"]]
+        raise NotImplementedError(f"{who}: the CROCO fields h, zeta, Cs_w and W must share one dtype (float32 or float64); "
+                                  f"field {odd[0]} is {dts[odd[0]]}, h is {dts['h']}")
+    return {"hc": float(fs.context["hc"]), "sigma_levels": sigma_levels, "cs_w": arr.reshape(-1), "cs_w_f32": arr.dtype == np.float32}
+
+
 class KernelWarning(RuntimeWarning):
     pass
 
@@ -72,6 +121,13 @@ class Kernel:
         self.device_variables = []
         names = {v.name: v for v in self._pclass.variables}
         for slot, f in enumerate(kernels):
+            spec = getattr(f, "_pk_sample_sigma", None)
+            if spec is not None:  # SampleFieldCroco: the field and Variable were checked by check_fieldsets_in_kernels
+                fname, vn = spec
+                if vn not in self.device_variables:
+                    self.device_variables.append(vn)
+                self.samples[slot] = (fname, self.device_variables.index(vn))
+                continue
             spec = getattr(f, "_pk_sample", None)
             if spec is None:
                 continue
@@ -160,6 +216,23 @@ class Kernel:
                     raise ValueError(f"{kernel.__name__} needs the field {name}")
             if kernel is not _k.DiffusionUniformKh and not hasattr(fs, "dres"):
                 raise ValueError(f"{kernel.__name__} needs fieldset.add_context('dres', ...)")
+        if _is_croco(kernel):  # (the reference fails with an AttributeError from inside the first step)
+            if _on_uxgrid(fs):
+                raise NotImplementedError(f"{kernel.__name__} is not implemented on a UxGrid (unstructured mesh)")
+            croco_parameters(fs, who=kernel.__name__)
+            if kernel is _k.AdvectionRK2_3D_CROCO and ("W" not in fs.fields or "UVW" not in fs.fields):
+                raise ValueError(f"{kernel.__name__} needs a W field (UVW)")
+            spec = getattr(kernel, "_pk_sample_sigma", None)
+            if spec is not None:
+                fname, vn = spec
+                fld = fs.fields.get(fname)
+                if fld is None or hasattr(fld, "U"):
+                    raise ValueError(f"{kernel.__name__}: '{fname}' is not a scalar field of the fieldset")
+                names = {v.name: v for v in self.pclass.variables}
+                if vn not in names or vn in _RESERVED_COLUMNS:
+                    raise ValueError(f"{kernel.__name__}: the ParticleClass has no user Variable '{vn}' (Particle.add_variable)")
+                if np.dtype(names[vn].dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+                    raise ValueError(f"{kernel.__name__}: Variable '{vn}' must be float32 or float64")
         if kernel in (_k.AdvectionRK4_3D, _k.AdvectionRK2_3D) and "UVW" not in fs.fields:
             raise ValueError(f"{kernel.__name__} needs a W field (UVW)")
 
@@ -276,6 +349,9 @@ class Kernel:
             if _on_uxgrid(self._fieldset):  # no compiled user kernels on a UxGrid: they run in the host loop
                 self._jit_tried = True
                 self.jit_report = "user kernels are not compiled for a UxGrid"
+            elif any(_is_croco(f) for f in self._kernels):  # nor next to a CROCO kernel (csrc/pk_sigma.h)
+                self._jit_tried = True
+                self.jit_report = "user kernels are not compiled next to a CROCO kernel"
             else:
                 self._try_jit(pset)
         engine.device_variables = list(self.device_variables)

@@ -1,4 +1,4 @@
-"""Built-in kernels (names and signatures of src/parcels/kernels/_advection.py and _advectiondiffusion.py).
+"""Built-in kernels (names and signatures of src/parcels/kernels/_advection.py, _advectiondiffusion.py and _sigmagrids.py).
 
 These functions are *tokens*: ``Kernel`` recognises them by identity (the reference does the same for
 AdvectionRK45, kernel.py:129-134) and maps each to the PK_KERNEL_* id of the HIP implementation in
@@ -14,6 +14,7 @@ __all__ = [
     "AdvectionEE",
     "AdvectionRK2",
     "AdvectionRK2_3D",
+    "AdvectionRK2_3D_CROCO",
     "AdvectionRK4",
     "AdvectionRK4_3D",
     "AdvectionRK45",
@@ -24,7 +25,10 @@ __all__ = [
     "MoveEast",
     "MoveNorth",
     "SampleField",
+    "SampleFieldCroco",
+    "SampleOmegaCroco",
     "SubmergeParticle",
+    "convert_z_to_sigma_croco",
 ]
 
 
@@ -139,8 +143,73 @@ def SampleField(field: str, into):
     return token
 
 
+# ---- CROCO sigma grids (src/parcels/kernels/_sigmagrids.py; csrc/pk_sigma.h) ----------------------------------------------------
+def AdvectionRK2_3D_CROCO(particles, fieldset):  # _sigmagrids.py:38-72
+    """Second-order Runge-Kutta advection on CROCO sigma layers with the vertical velocity of the 'W' field (sampled linearly); needs the
+    fields h, zeta, Cs_w, W and fieldset.add_context("hc", ...)."""
+    _device_only("AdvectionRK2_3D_CROCO")
+
+
+def SampleFieldCroco(field: str, into: str):
+    """The reference's SampleOmegaCroco (_sigmagrids.py:28-35) for any scalar field of a CROCO fieldset ("can be adapted to sample any other
+    field on a CROCO sigma grid by replacing 'omega'"):
+
+        sigma = convert_z_to_sigma_croco(fieldset, particles.t, particles.z, particles.y, particles.x, particles)
+        particles.<into> = fieldset.<field>[particles.t, sigma, particles.y, particles.x, particles]
+
+    as a device kernel.  ``into`` is a float32 / float64 particle Variable.  Returns a kernel token named ``Sample<field>Croco``."""
+    if not (isinstance(field, str) and isinstance(into, str)):
+        raise TypeError("SampleFieldCroco(field_name, into=variable_name)")
+
+    def token(particles, fieldset):
+        _device_only(token.__name__)
+
+    token.__name__ = token.__qualname__ = f"Sample{field}Croco"
+    token.__doc__ = f"particles.{into} = fieldset.{field}[particles.t, sigma, particles.y, particles.x, particles]"
+    token._pk_sample_sigma = (field, into)
+    return token
+
+
+SampleOmegaCroco = SampleFieldCroco("omega", "omega")  # _sigmagrids.py:28-35
+SampleOmegaCroco.__name__ = SampleOmegaCroco.__qualname__ = "SampleOmegaCroco"
+
+
+def convert_z_to_sigma_croco(fieldset, t, z, y, x, particle=None):
+    """Local sigma level of the points (t, z, y, x) of a CROCO fieldset (_sigmagrids.py:6-25): NumPy arrays in, sigma out.
+
+    With ``particle=None`` the whole conversion runs on the device (pk_sigma_croco: the two inner samples of h and zeta are detached).
+    With a particle view -- inside a Python kernel on the host path -- h and zeta are sampled attached (``Field.eval(..., particles=)``:
+    the view's ``state`` / ``ei`` are updated like by any such sample) and the level scan runs on the sampled values, so that
+
+        sigma = convert_z_to_sigma_croco(fieldset, particles.t, particles.z, particles.y, particles.x, particles)
+        particles.temp = fieldset.T[particles.t, sigma, particles.y, particles.x, particles]
+
+    works on the host path as in the reference."""
+    import numpy as np
+
+    from .kernel import croco_parameters
+
+    par = croco_parameters(fieldset, who="convert_z_to_sigma_croco")
+    t, z, y, x = np.broadcast_arrays(*(np.atleast_1d(np.asarray(v)) for v in (t, z, y, x)))
+    if particle is None:
+        return fieldset._engine_or_create().sigma_croco(par, t, z, y, x)
+    h = fieldset.h.eval(t, np.zeros_like(z), y, x, particles=particle)
+    zeta = fieldset.zeta.eval(t, np.zeros_like(z), y, x, particles=particle)
+    sigma_levels, cs_w, hc = par["sigma_levels"], par["cs_w"], par["hc"]
+    with np.errstate(all="ignore"):
+        z0 = hc * sigma_levels[None, :] + (h[:, None] - hc) * cs_w[None, :]
+        zvec = z0 + zeta[:, None] * (1.0 + (z0 / h[:, None]))
+        zinds = zvec <= z[:, None]
+        zi = np.argmin(zinds, axis=1) - 1
+        zi = np.where(zinds.all(axis=1), zvec.shape[1] - 2, zi)
+        idx = np.arange(zi.shape[0])
+        return sigma_levels[zi] + (z - zvec[idx, zi]) * (sigma_levels[zi + 1] - sigma_levels[zi]) / (zvec[idx, zi + 1] - zvec[idx, zi])
+
+
 def kernel_id(f):
     """PK_KERNEL_* id of a kernel token, or None for a function this package cannot run."""
+    if getattr(f, "_pk_sample_sigma", None) is not None:
+        return 12  # PK_KERNEL_SAMPLE_SIGMA_CROCO
     if getattr(f, "_pk_sample", None) is not None:
         return 10  # PK_KERNEL_SAMPLE_FIELD
     return KERNEL_IDS.get(f)
@@ -150,6 +219,7 @@ KERNEL_IDS = {
     AdvectionEE: 1,
     AdvectionRK2: 2,
     AdvectionRK2_3D: 3,
+    AdvectionRK2_3D_CROCO: 11,
     AdvectionRK4: 4,
     AdvectionRK4_3D: 5,
     AdvectionRK45: 6,
