@@ -279,8 +279,8 @@ static constexpr int RIGHT_OUT_OF_BOUNDS = -1;
 
 // cos() for latitudes.  |x| <= 1.5 rad (86 deg): Cody-Waite reduction by pi/2 + the classic minimax kernels
 // (error < 0.82 ulp, checked against long-double cosl over 2e7 samples); beyond that sincos_geo.  The reference's
-// cos is NumPy/libm (<= 1 ulp): any <= 1 ulp cosine is as close to it as another libm would be.  ~20 fp64 ops
-// instead of the generic routine's range reduction.
+// cos is NumPy/libm (<= 1 ulp): any <= 1 ulp cosine is as close to it as another libm would be.  25-27 VALU
+// instructions on the two inner regions (gfx950 ISA), each a divergent block, instead of the generic routine's range reduction.
 PK_DEV void sincos_geo(double x, double& s, double& c);
 PK_DEV double cos_lat(double x) {
     const double ax = fabs(x);

@@ -98,6 +98,32 @@ PK_DEV double fast_bary(double x, double a, double a1, double rw) {
     if constexpr (PK_FAST_LEAN != 0) return (x - a) * rw;
     else return div_by_recip(x - a, a1 - a, rw);
 }
+// cos(lat) of the unit conversion (PK_FAST_LEAN builds): with h = lat * pi / 360, cos(2h) = 1 - 2 sin(h)^2 and sin(h) from the minimax kernel cos_lat
+// uses beyond 45 degrees (S1..S6, valid to |h| <= pi/4): ONE region without a branch for |lat * pi / 180| <= 1.5 where cos_lat has three, 12 VALU
+// instructions where the ISA of cos_lat shows 25-27 plus two exec-mask regions.
+//   * The coefficients are handed over in scalar registers at the place of use (an SGPR pair is a legal addend of v_fma_f64).  As loop-invariant
+//     values they sat in VGPRs across the stage loop, each copied (v_mov_b64) in front of the v_fmac_f64 that would have destroyed it.
+//   * Beyond 1.5 rad (unlikely: +-86 degrees, or a stray particle) cos_lat itself, behind a CALL: inlined, the nine coefficients of its two
+//     kernels are kept in 18 VGPRs across the stage loop for a block that almost never runs.  The callee is a leaf without scratch and the call
+//     site saves nothing: advect_fast_kernel<double, 0, false, FAST_LP_CACHE> went from 126 VGPRs + 12 B of scratch to 114 and none.
+// Accuracy: the cancellation in 1 - 2 s^2 leaves an ABSOLUTE error of at most (1 - cos) * 2^-51 + ulp / 2, so more ulps the smaller the cosine.
+// Measured on the device against cosl() of the same argument (tools/cos_lean_check.hip, 4.7e6 latitudes; tests/test_gpu_fast_eval_lean.py holds
+// the bound), maximum in ulps of the result per band of |lat| in degrees:
+//   0-30: 0.76   30-60: 1.07   60-76: 6.1   76-80: 6.6   80-84: 13.7   84-85.94: 14.2 (1.6e-15 relative)   beyond (cos_lat): 0.51
+// and never more than 1.8 * 2^-53 absolute.
+static __device__ __attribute__((noinline)) double cos_lat_far(double x) { return cos_lat(x); }
+PK_DEV double cos_lat_lean(double lat_deg) {
+    const double h = lat_deg * (0.5 * DEG2RAD);  // (halving RN(pi / 180) is exact: h == 0.5 * (lat * DEG2RAD), the argument of cos_lat, halved)
+    if (__builtin_expect(!(fabs(h) <= 0.75), 0)) return cos_lat_far(lat_deg * DEG2RAD);
+    double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
+           S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
+    asm volatile("" : "+s"(S1), "+s"(S2), "+s"(S3), "+s"(S4), "+s"(S5), "+s"(S6));
+    const double z = h * h;
+    const double r = fma(z, fma(z, fma(z, fma(z, fma(z, S6, S5), S4), S3), S2), S1);
+    const double s = fma(z * h, r, h);
+    return fma(-2.0 * s, s, 1.0);
+}
+
 constexpr int FAST_WG = 256;                          // lanes per workgroup of advect_fast_kernel
 constexpr int FAST_BLK_BYTES = FAST_WG * 8 * 8;       // LDS of the corner-block cache per workgroup (8 doubles per lane)
 // Modes of the 2-D kernel's corner cache (template parameter LP of eval_uvw_fast / advect_fast_kernel; pk_set_option "block_cache"):
@@ -351,8 +377,18 @@ PK_DEV void uvw_fast(const FastA& F, int64_t o0, int64_t o1, uint32_t b00, doubl
 // ONE arithmetic whether the values come out of LDS or were just formed (FAST_LP_REGS forms them in every evaluation): a lane's result does
 // not depend on its wavefront's other lanes, on launch splits or on the cache.  Against the reference's order (t first, then z, each
 // a*(1-w) + b*w) the positions move by a few 1e-15 relative (the class of change PK_FAST_LEAN is).
-struct LpField {  // Z0 and D of one field: rows y (0) and y+1 (1) of two x-neighbours
-    pk_tab2 z0, z1, d0, d1;
+// The block is kept in the POLYNOMIAL basis of the bilinear form, not as corner values: with a00, a01, a10, a11 the corners (y, x), (y, x+1),
+// (y+1, x), (y+1, x+1) of Z0,
+//     P0 = a00    Px = a01 - a00    Py = a10 - a00    Pxy = (a11 - a10) - (a01 - a00)
+// and the same four combinations of D.  An evaluation then needs no weights: p* = fma(tau, D*, P*) four times and
+//     value = fma(eta, fma(xsi, pxy, py), fma(xsi, px, p0))
+// -- 7 fused operations per field where the corner form took 4 + 7, plus 6 for the weights U and V shared (28 -> 14 VALU per evaluation).  The
+// differences are formed once per block, where it is fetched.  Against long double the absolute error is 7.6e-16 of the largest corner (the
+// weights form: 4.0e-16): the class of change the level-pair arithmetic itself was.
+// (Folding 1 / deg2m into the eight stored values of V would save one multiplication per evaluation and cost eight per fetch, which runs for
+// the whole wavefront in ~0.2 of the wave-evaluations: not free, not done.)
+struct LpField {  // {P0, Px}, {Py, Pxy} of Z0 and of D
+    pk_tab2 p0, p1, d0, d1;
 };
 template <class FT, bool LT, bool LZ>
 PK_DEV void lp_field(LpField& f, const char* l0, const char* l1, uint32_t bo, uint32_t dyb, uint32_t dzb, double zeta) {
@@ -366,7 +402,7 @@ PK_DEV void lp_field(LpField& f, const char* l0, const char* l1, uint32_t bo, ui
         a00 = fma(zeta, r.d00 - a00, a00); a01 = fma(zeta, r.d01 - a01, a01);
         a10 = fma(zeta, r.d10 - a10, a10); a11 = fma(zeta, r.d11 - a11, a11);
     }
-    f.z0.x = a00; f.z0.y = a01; f.z1.x = a10; f.z1.y = a11;
+    f.p0.x = a00; f.p0.y = a01 - a00; f.p1.x = a10 - a00; f.p1.y = (a11 - a10) - (a01 - a00);
     f.d0.x = f.d0.y = f.d1.x = f.d1.y = 0.0;
     if (LT) {
         double b00 = r.t00, b01 = r.t01, b10 = r.t10, b11 = r.t11;
@@ -374,7 +410,8 @@ PK_DEV void lp_field(LpField& f, const char* l0, const char* l1, uint32_t bo, ui
             b00 = fma(zeta, r.e00 - b00, b00); b01 = fma(zeta, r.e01 - b01, b01);
             b10 = fma(zeta, r.e10 - b10, b10); b11 = fma(zeta, r.e11 - b11, b11);
         }
-        f.d0.x = b00 - a00; f.d0.y = b01 - a01; f.d1.x = b10 - a10; f.d1.y = b11 - a11;
+        const double e00 = b00 - a00, e01 = b01 - a01, e10 = b10 - a10, e11 = b11 - a11;
+        f.d0.x = e00; f.d0.y = e01 - e00; f.d1.x = e10 - e00; f.d1.y = (e11 - e10) - (e01 - e00);
     }
 }
 // Z0 / D of U and V at the lane's cell
@@ -385,9 +422,9 @@ PK_DEV void lp_fetch(const FastA& F, int64_t o0, int64_t o1, uint32_t b00, doubl
     lp_field<FT, LT, LZ>(fu, F.U + o0, F.U + o1, bo, F.dyb, F.dzb, zeta);
     lp_field<FT, LT, LZ>(fv, F.V + o0, F.V + o1, bo, F.dyb, F.dzb, zeta);
 }
-PK_DEV double lp_sum(const LpField& f, double tau, double w00, double w01, double w10, double w11) {
-    const double v00 = fma(tau, f.d0.x, f.z0.x), v01 = fma(tau, f.d0.y, f.z0.y), v10 = fma(tau, f.d1.x, f.z1.x), v11 = fma(tau, f.d1.y, f.z1.y);
-    return w00 * v00 + w01 * v01 + w10 * v10 + w11 * v11;
+PK_DEV double lp_sum(const LpField& f, double tau, double eta, double xsi) {
+    const double p0 = fma(tau, f.d0.x, f.p0.x), px = fma(tau, f.d0.y, f.p0.y), py = fma(tau, f.d1.x, f.p1.x), pxy = fma(tau, f.d1.y, f.p1.y);
+    return fma(eta, fma(xsi, pxy, py), fma(xsi, px, p0));
 }
 
 PK_DEV int uniform_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -401,6 +438,7 @@ struct FCtx {
     int32_t ei;
     int ht, hz, hy, hx;
     int zi;                      // memo: index (or out-of-bounds code) of the last depth searched
+    uint32_t zez;                // ... and its term zi * ez of the ravelled index (wrapped 32-bit product)
     double mt, mtau, mz, mzeta;  // memo keys (bitwise-equal coordinate => same answer) and barycentric values
     // Corner-block cache (2-D kernels): the t / z-lerped corner values c00..c11 of U and V -- 8 doubles in the lane's LDS slot FastTabs::blk
     // -- are a function of the cell and of (t, z) only.  Stages 2 and 3 of a Runge-Kutta step share t, stage 4 and stage 1 of the next
@@ -419,6 +457,7 @@ PK_DEV void fctx_init(FCtx& c, int state, int32_t ei) {
     c.ei = ei;
     c.ht = c.hz = c.hy = c.hx = 0;
     c.zi = 0;
+    c.zez = 0u;
     c.mt = c.mz = __builtin_nan("");  // equal to nothing
     c.mtau = c.mzeta = 0.0;
     c.bei = FAST_NO_BLOCK;
@@ -459,6 +498,7 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
     if (fl & FA_Z) {
         if (!(z == c.mz)) {
             fast_search<true>(T.depth, F.gnz, F.z0, F.z1, z, c.hz, c.zi, c.mzeta, (fl & FA_NZ2) != 0);
+            c.zez = (uint32_t)c.zi * F.ez;
             c.mz = z;
             c.bei = FAST_NO_BLOCK;
         }
@@ -475,9 +515,13 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
         if (fl & FA_Y) fast_search<true>(T.lat, T.gny, F.y0, F.y1, y, c.hy, yi, eta, (fl & FA_NY2) != 0);
         if (fl & FA_X) fast_search<true>(T.lon, T.gnx, F.x0, F.x1, x, c.hx, xi, xsi, (fl & FA_NX2) != 0);
     }
-    // ravel_index (basegrid.py:83-152): the low 32 bits of the int64 sum are the wrapped 32-bit sum
-    c.ei = (int32_t)((uint32_t)xi * F.ex + (uint32_t)yi * F.ey + (uint32_t)zi * F.ez);
+    // ravel_index (basegrid.py:83-152): the low 32 bits of the int64 sum are the wrapped 32-bit sum.  Of its three 32-bit products (v_mul_lo_u32
+    // each) one is left, and that one at full rate: ex == 1 (the fast path needs an x axis: pk_api.hip fill_fast, ravel_strides), zi * ez changes
+    // only with the depth memo (FCtx::zez), and for an in-bounds yi both yi and ey are below the 3840 nodes a 60 KB coordinate table holds, far
+    // inside the 24 bits of v_mad_u32_u24.  An out-of-bounds code (negative) takes the wrapped 32-bit product.
+    c.ei = (int32_t)((uint32_t)xi + __umul24((uint32_t)yi, F.ey) + c.zez);
     if (__builtin_expect((xi | yi | zi) < 0, 0)) {  // some index carries an out-of-bounds code (-1 right, -2 left)
+        c.ei = (int32_t)((uint32_t)xi + (uint32_t)yi * F.ey + c.zez);
         int s = c.state;  // field.py:307-356
         if ((xi == RIGHT_OUT_OF_BOUNDS || yi == RIGHT_OUT_OF_BOUNDS || zi == RIGHT_OUT_OF_BOUNDS) && s < PK_ERROROUTOFBOUNDS) s = PK_ERROROUTOFBOUNDS;
         if (zi == LEFT_OUT_OF_BOUNDS && s < PK_ERRORTHROUGHSURFACE) s = PK_ERRORTHROUGHSURFACE;
@@ -524,18 +568,18 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
             // load batches, 4 VGPRs and 12 B of scratch less -- lanes of a wavefront that spans several level pairs read back other values
             // than they had formed: tests/test_gpu_level_pair_cache.py::test_staggered_release_times_and_ring.)
             if (LP == FAST_LP_CACHE && miss) {
-                T.blk[0] = fu.z0; T.blk[FAST_WG_LP] = fu.z1; T.blk[2 * FAST_WG_LP] = fu.d0; T.blk[3 * FAST_WG_LP] = fu.d1;
-                T.blk[4 * FAST_WG_LP] = fv.z0; T.blk[5 * FAST_WG_LP] = fv.z1; T.blk[6 * FAST_WG_LP] = fv.d0; T.blk[7 * FAST_WG_LP] = fv.d1;
+                T.blk[0] = fu.p0; T.blk[FAST_WG_LP] = fu.p1; T.blk[2 * FAST_WG_LP] = fu.d0; T.blk[3 * FAST_WG_LP] = fu.d1;
+                T.blk[4 * FAST_WG_LP] = fv.p0; T.blk[5 * FAST_WG_LP] = fv.p1; T.blk[6 * FAST_WG_LP] = fv.d0; T.blk[7 * FAST_WG_LP] = fv.d1;
                 c.bei = c.ei;
                 c.bkey = key;
             }
         }
         if (LP == FAST_LP_CACHE) {
-            fu.z0 = T.blk[0]; fu.z1 = T.blk[FAST_WG_LP]; fu.d0 = T.blk[2 * FAST_WG_LP]; fu.d1 = T.blk[3 * FAST_WG_LP];
-            fv.z0 = T.blk[4 * FAST_WG_LP]; fv.z1 = T.blk[5 * FAST_WG_LP]; fv.d0 = T.blk[6 * FAST_WG_LP]; fv.d1 = T.blk[7 * FAST_WG_LP];
+            fu.p0 = T.blk[0]; fu.p1 = T.blk[FAST_WG_LP]; fu.d0 = T.blk[2 * FAST_WG_LP]; fu.d1 = T.blk[3 * FAST_WG_LP];
+            fv.p0 = T.blk[4 * FAST_WG_LP]; fv.p1 = T.blk[5 * FAST_WG_LP]; fv.d0 = T.blk[6 * FAST_WG_LP]; fv.d1 = T.blk[7 * FAST_WG_LP];
         }
-        uu = lp_sum(fu, tau, w00, w01, w10, w11);
-        vv = lp_sum(fv, tau, w00, w01, w10, w11);
+        uu = lp_sum(fu, tau, eta, xsi);
+        vv = lp_sum(fv, tau, eta, xsi);
     } else {
         const bool bc = !D3 && PK_FAST_BLOCK_CACHE && (fl & FA_BLK) != 0;
         // (in-bounds indices ravel to a non-negative `ei` that names the cell; the memo updates above already dropped a block of another (t, z))
@@ -575,6 +619,7 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
     if (fl & FA_SPH) {  // _xinterpolators.py:183-187
         double conv;
         if (PF && pos_f32) conv = (double)((float)F.deg2m * cosf((float)y * DEG2RADF));
+        else if constexpr (PK_FAST_LEAN != 0) conv = F.deg2m * cos_lat_lean(y);
         else conv = F.deg2m * cos_lat(y * DEG2RAD);
         if constexpr (PK_FAST_LEAN != 0) {  // u / conv, v / deg2m within 1.5 ulp: 7 operations instead of 22
             uu = uu * rcp_lean(conv);
@@ -623,6 +668,7 @@ PK_DEV double eval_scalar_fast(const KArgs& a, const FastTabs& T, FCtx& c, int s
     if (F.has_z) {
         if (!(z == c.mz)) {
             fast_search(T.depth, F.gnz, F.z0, F.z1, z, c.hz, c.zi, c.mzeta);
+            c.zez = (uint32_t)c.zi * F.ez;
             c.mz = z;
             c.bei = FAST_NO_BLOCK;
         }

@@ -772,8 +772,17 @@ __global__ void __launch_bounds__(fast_wg(LP), PK_MIN_WAVES_FAST) advect_fast_ke
 #endif
                 // AdvectionRK4(_3D), _advection.py:42-75: (u1 + 2*u2 + 2*u3 + u4) summed left to right
                 double su = 0.0, sv = 0.0, sw = 0.0, lu = 0.0, lv = 0.0, lw = 0.0;
+                // The level-pair kernels evaluate stage 1 OUTSIDE the loop: it samples the particle's own position, so the stage-position
+                // arithmetic, its select and three loop-carried 64-bit copies leave every evaluation (measured: 5.96 -> 5.74 ms on the headline
+                // run, profiles/c2_eval_trim_ab.txt; the other instantiations keep one copy of the evaluation).
+                constexpr bool peel = LP != FAST_LP_OFF;
+                if constexpr (peel) {
+                    double u, v, w;
+                    eval_uvw_fast<FT, pf, D3, LP>(a, ft, c, pt, pz, py, px, pf, u, v, w, it, adv * 1000, 1);
+                    su = lu = u; sv = lv = v; sw = lw = w;
+                }
 #pragma unroll 1
-                for (int stage = 0; stage < 4; stage++) {
+                for (int stage = peel ? 1 : 0; stage < 4; stage++) {
                     double st = pt, sz = pz, sy = py, sx = px;
                     if (stage > 0) {
                         const double cdt = stage == 3 ? 1.0 : 0.5;  // u*1.0 == u and 1.0*dt == dt exactly
