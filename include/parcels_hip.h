@@ -506,6 +506,41 @@ int32_t pk_set_croco(pk_ctx* ctx, int32_t field_h, int32_t field_zeta, double hc
  * both inner samples are detached (no guess, no state: field.py:145-195).  The device function behind the two kernels. */
 int32_t pk_sigma_croco(pk_ctx* ctx, int64_t m, const double* t, const double* z, const double* y, const double* x, double* out_sigma);
 
+/* ---- neighbour search for particle-particle interaction kernels -----------------------------------
+ * The reference has no such primitive: its interaction kernels (docs/user_guide/examples/tutorial_interaction.ipynb: attraction towards marked
+ * particles, merging of mutual nearest neighbours) form dense N x N distance matrices in NumPy.  These calls give the same numbers from a cell
+ * list.  Points are float64, flat Euclidean; for an ordered pair (i, j): dx = x[j] - x[i], dy, dz likewise, dist = sqrt(dx*dx + dy*dy [+ dz*dz])
+ * summed left to right, every operation rounded on its own (np.sqrt(dx**2 + dy**2)).  j is a neighbour of i iff i != j, dist < radius (strict),
+ * sources[j] != 0 when sources is given, and dist > 0 under PK_NEIGHBORS_NO_COINCIDENT.  A point with a non-finite coordinate has no neighbours
+ * and is nobody's neighbour (NumPy's `nan < r`).  All arrays are host arrays; the cell list and its scratch belong to the context, are reused
+ * and regrown across calls and are freed with it. */
+#define PK_NEIGHBORS_NO_COINCIDENT 1
+typedef struct {
+    int64_t n, nvalid;   /* points of the cell list; those with finite coordinates */
+    int64_t ncx, ncy;    /* cells of the uniform (x, y) grid over their bounding box */
+    int64_t total;       /* pairs the last count pass announced, -1 before it */
+    double cell_size;    /* >= radius * (1 + 2^-16); doubled `doublings` times to keep ncx * ncy <= max(2^20, 4 n) */
+    int32_t doublings;
+    int32_t reserved0;
+} pk_neighbors_info_t;
+/* Build the cell list of n points: x, y, z (NULL: 2-D), sources (NULL: every point; else one byte per point).  The tutorial's
+ * `particles.x / .y / .z` of the evaluated particles and its `attractor` column.  Replaces the context's previous cell list. */
+int32_t pk_neighbors_build(pk_ctx* ctx, int64_t n, const double* x, const double* y, const double* z, const uint8_t* sources, double radius,
+                           int32_t flags);
+/* counts[i] (may be NULL) = number of neighbours of i, *total = their sum: the row sums of the tutorial's `distances < radius` matrices.
+ * Keeps the CSR row starts on the device for the pair pass. */
+int32_t pk_neighbors_counts(pk_ctx* ctx, int64_t* counts, int64_t* total);
+/* j[i] = the neighbour of i with the smallest dist, ties to the smallest index, -1 (and dist[i] = inf) without one: the tutorial's
+ * `np.argmin(distances, axis=1)` of the merge kernel. */
+int32_t pk_neighbors_nearest(pk_ctx* ctx, int64_t* j, double* dist);
+/* After the count pass, with the total it announced: starts[n + 1] (CSR), and for every pair in row order, j ascending within a row,
+ * j, dx, dy, dz (NULL for a 2-D cell list), dist[total] -- the non-zero entries of the tutorial's attraction matrices. */
+int32_t pk_neighbors_pairs(pk_ctx* ctx, int64_t total, int64_t* starts, int64_t* j, double* dx, double* dy, double* dz, double* dist);
+/* What the last build chose (the tutorial has no counterpart: diagnostics and tests). */
+int32_t pk_neighbors_info(pk_ctx* ctx, pk_neighbors_info_t* out);
+/* Free the cell list and its scratch now instead of with the context (the tutorial's matrices die with each kernel call). */
+int32_t pk_neighbors_release(pk_ctx* ctx);
+
 /* achieved copy bandwidth probe (device-to-device float4 copy), GB/s; used as a measured roofline denominator */
 int32_t pk_measure_copy_bandwidth(pk_ctx* ctx, int64_t bytes, int32_t iters, double* gbps);
 

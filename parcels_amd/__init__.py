@@ -9,6 +9,7 @@ from . import convert, kernels
 from .dataset import DataArray, Dataset
 from .field import Field, FieldEvalWarning, TimeInterval, VectorField
 from .fieldset import FieldSet
+from .interaction import Neighbors, nearest_neighbor, neighbor_counts, neighbors
 from .interpolators import (
     CGrid_Tracer,
     CGrid_Velocity,

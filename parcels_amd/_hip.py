@@ -216,6 +216,13 @@ class HashInfo(C.Structure):
     _fields_ = [("nkeys", C.c_int64), ("nentries", C.c_int64), ("bitwidth", C.c_int32), ("neighbour_probe", C.c_int32), ("bbox", C.c_double * 6)]
 
 
+class NeighborsInfo(C.Structure):  # pk_neighbors_info_t
+    _fields_ = [("n", C.c_int64), ("nvalid", C.c_int64), ("ncx", C.c_int64), ("ncy", C.c_int64), ("total", C.c_int64),
+                ("cell_size", C.c_double), ("doublings", C.c_int32), ("reserved0", C.c_int32)]
+
+
+PK_NEIGHBORS_NO_COINCIDENT = 1
+
 ABI_SYMBOLS = [
     "pk_abi_version",
     "pk_init",
@@ -258,6 +265,12 @@ ABI_SYMBOLS = [
     "pk_search",
     "pk_set_croco",
     "pk_sigma_croco",
+    "pk_neighbors_build",
+    "pk_neighbors_counts",
+    "pk_neighbors_nearest",
+    "pk_neighbors_pairs",
+    "pk_neighbors_info",
+    "pk_neighbors_release",
     "pk_measure_copy_bandwidth",
     "pk_set_option",
     "pk_upload_stats",
@@ -362,6 +375,12 @@ def load():
     lib.pk_gather_rows_to_root.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_uint32, C.c_void_p]
     lib.pk_allgather_output.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.c_uint32, C.c_void_p]
     lib.pk_gathered_fetch.argtypes = [C.c_void_p, C.POINTER(ParticlesDesc), C.c_int64]
+    lib.pk_neighbors_build.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32]
+    lib.pk_neighbors_counts.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.pk_neighbors_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pk_neighbors_pairs.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6
+    lib.pk_neighbors_info.argtypes = [C.c_void_p, C.POINTER(NeighborsInfo)]
+    lib.pk_neighbors_release.argtypes = [C.c_void_p]
     if lib.pk_abi_version() != PK_ABI_VERSION:
         raise HipLibraryError(f"ABI version mismatch: library {lib.pk_abi_version()}, binding {PK_ABI_VERSION}")
     _lib = lib

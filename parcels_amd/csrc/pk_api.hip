@@ -18,6 +18,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "pk_hashbuild.h"
+#include "pk_neighbors.h"
 #include "pk_host_stage.h"
 #include "pk_kernels.h"
 #include "pk_ux.h"
@@ -193,6 +194,7 @@ struct pk_ctx {
 
     PkSelect sel;                   // write filter on the device rows (pk_select.inc): the filtered snapshot and the multi-GPU exchange use it
     struct PkComm* comm = nullptr;  // the multi-GPU exchange (pk_comm.inc: RCCL communicator + staging), NULL until pk_comm_init
+    pk::Neighbors* nbr = nullptr;   // neighbour search (pk_neighbors.hip: cell list + scratch), NULL until pk_neighbors_build
 
     int32_t fail(const char* where, hipError_t e) {
         err = std::string(where) + ": " + hipGetErrorString(e);
@@ -802,6 +804,7 @@ int32_t pk_destroy(pk_ctx* ctx) {
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->h_summary) (void)hipHostFree(ctx->h_summary);
     (void)pk_comm_destroy(ctx);
+    neighbors_free(ctx->nbr);
     if (ctx->sel.d_flag) (void)hipFree(ctx->sel.d_flag);
     if (ctx->sel.d_offs) (void)hipFree(ctx->sel.d_offs);
     if (ctx->sel.d_tmp) (void)hipFree(ctx->sel.d_tmp);
@@ -3037,6 +3040,68 @@ int32_t pk_measure_copy_bandwidth(pk_ctx* ctx, int64_t bytes, int32_t iters, dou
     *gbps = (2.0 * (double)n16 * 16.0 * iters) / ((double)ms * 1e-3) / 1e9;
     PK_HIP(ctx, hipFree(src));
     PK_HIP(ctx, hipFree(dst));
+    return 0;
+}
+
+// ---- neighbour search (pk_neighbors.hip) ---------------------------------------------------------------
+int32_t pk_neighbors_build(pk_ctx* ctx, int64_t n, const double* x, const double* y, const double* z, const uint8_t* sources, double radius,
+                           int32_t flags) {
+    if (!ctx) return -2;
+    PK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->nbr) ctx->nbr = neighbors_create();
+    std::string msg;
+    if (neighbors_build(ctx->nbr, ctx->compute, n, x, y, z, sources, radius, flags, &msg)) return ctx->fail(msg);
+    return 0;
+}
+
+int32_t pk_neighbors_counts(pk_ctx* ctx, int64_t* counts, int64_t* total) {
+    if (!ctx) return -2;
+    if (!ctx->nbr) return ctx->fail("pk_neighbors_counts: no cell list (pk_neighbors_build first)");
+    PK_HIP(ctx, hipSetDevice(ctx->device));
+    std::string msg;
+    if (neighbors_counts(ctx->nbr, ctx->compute, counts, total, &msg)) return ctx->fail(msg);
+    return 0;
+}
+
+int32_t pk_neighbors_nearest(pk_ctx* ctx, int64_t* j, double* dist) {
+    if (!ctx) return -2;
+    if (!ctx->nbr) return ctx->fail("pk_neighbors_nearest: no cell list (pk_neighbors_build first)");
+    PK_HIP(ctx, hipSetDevice(ctx->device));
+    std::string msg;
+    if (neighbors_nearest(ctx->nbr, ctx->compute, j, dist, &msg)) return ctx->fail(msg);
+    return 0;
+}
+
+int32_t pk_neighbors_pairs(pk_ctx* ctx, int64_t total, int64_t* starts, int64_t* j, double* dx, double* dy, double* dz, double* dist) {
+    if (!ctx) return -2;
+    if (!ctx->nbr) return ctx->fail("pk_neighbors_pairs: no cell list (pk_neighbors_build first)");
+    PK_HIP(ctx, hipSetDevice(ctx->device));
+    std::string msg;
+    if (neighbors_pairs(ctx->nbr, ctx->compute, total, starts, j, dx, dy, dz, dist, &msg)) return ctx->fail(msg);
+    return 0;
+}
+
+int32_t pk_neighbors_info(pk_ctx* ctx, pk_neighbors_info_t* out) {
+    if (!ctx || !out) return -2;
+    NeighborsInfo i;
+    neighbors_info(ctx->nbr, &i);
+    out->n = i.n;
+    out->nvalid = i.nvalid;
+    out->ncx = i.ncx;
+    out->ncy = i.ncy;
+    out->total = i.total;
+    out->cell_size = i.h;
+    out->doublings = i.doublings;
+    out->reserved0 = 0;
+    return 0;
+}
+
+int32_t pk_neighbors_release(pk_ctx* ctx) {
+    if (!ctx) return -2;
+    if (!ctx->nbr) return 0;
+    PK_HIP(ctx, hipSetDevice(ctx->device));
+    PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
+    neighbors_release(ctx->nbr);
     return 0;
 }
 

@@ -1,0 +1,43 @@
+// Fixed-radius neighbour search over the particles themselves: the hot path of particle-particle interaction kernels
+// (reference: docs/user_guide/examples/tutorial_interaction.ipynb, whose kernels build dense N x N distance matrices in NumPy).
+//
+// Semantics.  Points are float64 (x, y[, z]), flat Euclidean.  For an ordered pair (i, j):
+//   dx = x[j] - x[i], dy = y[j] - y[i], dz = z[j] - z[i];  dist = sqrt(dx*dx + dy*dy [+ dz*dz])
+// summed left to right, every operation rounded on its own, correctly rounded square root -- NumPy's np.sqrt(dx**2 + dy**2).
+// j is a neighbour of i iff i != j, dist < radius (strict), sources[j] (when given) and dist > 0 (PK_NEIGHBORS_NO_COINCIDENT).
+// A particle with a non-finite coordinate has no neighbours and is nobody's neighbour.  Rows are ordered by i, j ascends
+// within a row; the nearest neighbour is the smallest dist, ties to the smallest j.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+namespace pk {
+
+struct Neighbors;  // cell list + scratch of one context: grown on demand, reused across calls, freed with the context
+
+struct NeighborsInfo {
+    int64_t n = 0, nvalid = 0;  // points, points with finite coordinates
+    int64_t ncx = 0, ncy = 0;   // cells of the uniform (x, y) grid
+    double h = 0;               // cell size
+    int32_t doublings = 0;      // times the cell size was doubled to get under the cell cap
+    int64_t total = -1;         // pairs of the last count pass, -1 before it
+};
+
+Neighbors* neighbors_create();
+void neighbors_free(Neighbors* nb);     // everything, the object included
+void neighbors_release(Neighbors* nb);  // the device scratch only; the next build allocates again
+
+// Every function returns 0, or a negative code with *err set.  x, y, z (may be NULL), sources (may be NULL; one byte per
+// point, non-zero = source) are HOST arrays of length n; the outputs are host arrays too.
+int neighbors_build(Neighbors* nb, hipStream_t stream, int64_t n, const double* x, const double* y, const double* z, const uint8_t* sources,
+                    double radius, int32_t flags, std::string* err);
+int neighbors_counts(Neighbors* nb, hipStream_t stream, int64_t* counts, int64_t* total, std::string* err);
+int neighbors_nearest(Neighbors* nb, hipStream_t stream, int64_t* j, double* dist, std::string* err);
+// after neighbors_counts; total = what it announced.  starts: n + 1; j, dx, dy, dz (NULL without z), dist: total
+int neighbors_pairs(Neighbors* nb, hipStream_t stream, int64_t total, int64_t* starts, int64_t* j, double* dx, double* dy, double* dz,
+                    double* dist, std::string* err);
+void neighbors_info(const Neighbors* nb, NeighborsInfo* out);
+
+}  // namespace pk

@@ -1,0 +1,616 @@
+// Fixed-radius neighbour search on the device: uniform cell list in (x, y) + one lane per particle scanning 3 x 3 cells.
+// Serves particle-particle interaction kernels (reference: docs/user_guide/examples/tutorial_interaction.ipynb, which forms
+// dense N x N distance matrices in NumPy and says of itself that it "scales as N^2").  Semantics: pk_neighbors.h.
+//
+// Passes (all on the caller's stream, no workgroup waits on another, every loop bounded by a number computed beforehand):
+//   build    bbox of the finite points (block reduction, finished on the host) -> cell size -> key = cy * ncx + cx per point
+//            (non-finite points: the sentinel key `ncells`, which sorts last) -> stable rocPRIM radix sort of (key, index), so
+//            indices ascend within a cell -> coordinates gathered into sorted order + first / one-past-last sorted slot per cell
+//   counts   one lane per sorted slot, result at the ORIGINAL index; rocPRIM exclusive scan -> CSR row starts
+//   nearest  same scan, keeps (smallest dist, then smallest j)
+//   pairs    fill (checks its write index against the end of its row: a mismatch raises a flag and never writes), rocPRIM
+//            segmented radix sort of j within rows, then one lane per pair recomputes dx, dy, dz, dist from the ORIGINAL arrays
+//
+// The distance arithmetic must not be contracted into fused multiply-adds (NumPy rounds every operation): the Makefile builds
+// with -ffp-contract=off and this file repeats it.
+#pragma clang fp contract(off)
+#include "pk_neighbors.h"
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include <rocprim/rocprim.hpp>
+
+namespace pk {
+namespace {
+
+constexpr int NB_BLOCK = 256;
+constexpr int NB_BBOX_BLOCKS = 1024;
+constexpr int64_t NB_MAX_POINTS = 2147483646ll;   // indices and the sentinel fit uint32 / int32
+constexpr int64_t NB_MAX_PAIRS = 2147483647ll;    // rocPRIM's segmented sort counts its items in 32 bits
+constexpr int64_t NB_CELL_CAP_MIN = 1ll << 20;
+constexpr int64_t NB_CELL_CAP_MAX = 1ll << 30;    // keys fit 31 bits; a cell coordinate stays below 2^30 (see cell size)
+
+// ---- cell size -------------------------------------------------------------------------------------------------------------
+// Claim: with h >= radius * (1 + 2^-16) and h >= 2^-500, two points a, b with computed dist < radius have cell coordinates
+// that differ by at most 1 in x and in y.
+//   1. The computed dist bounds the true offset.  dx = fl(xb - xa) = (xb - xa)(1 + e), |e| <= u = 2^-53.  dist =
+//      fl(sqrt(fl(fl(dx*dx) + fl(dy*dy) [+ ...]))) >= |dx| (1 - u)^3 up to an absolute 2^-537 where dx*dx is subnormal (absolute
+//      error 2^-1075 under the root).  So |xb - xa| <= dist (1 + 5u) + 2^-536 < radius (1 + 5u) + 2^-536 <= h (1 - 2^-17):
+//      the 2^-16 margin pays for 5u, and 2^-536 <= h 2^-36.  Overflow makes dist infinite, which is no neighbour.
+//   2. The computed cell coordinate is t~ = fl(fl(x - xmin) / h) = t (1 + e'), |e'| <= 2u + u^2, t = (x - xmin) / h < 2^30
+//      (cell cap).  Hence t~b - t~a <= (tb - ta) + 2 * 2^30 * 3u <= 1 - 2^-17 + 2^-20 < 1, and floor(t~b) - floor(t~a) <= 1;
+//      by symmetry the difference never reaches 2.  Doubling h (exact) only shrinks tb - ta.
+// The host sizes the grid with the same subtraction and division (xmax - xmin) / h the device applies to every point, and
+// rounding is monotonic, so no point's coordinate exceeds the last cell; the clamp in cell_of is a guard, not a correction.
+constexpr double NB_CELL_MARGIN = 1.0 + 0x1p-16;
+constexpr double NB_CELL_MIN = 0x1p-500;
+
+struct NbGrid {
+    double xmin, ymin, h;
+    int32_t ncx, ncy;
+    uint32_t ncells;  // = ncx * ncy, also the sentinel key of a non-finite point
+};
+
+__device__ __forceinline__ bool nb_finite(double v) { return fabs(v) <= DBL_MAX; }  // false for NaN
+
+__device__ __forceinline__ int32_t cell_of(double v, double vmin, double h, int32_t nc) {
+    const double t = (v - vmin) / h;
+    int32_t c = t >= (double)nc ? nc - 1 : (int32_t)t;
+    if (!(t >= 0.0)) c = 0;  // NaN of inf / inf in the one-cell grid of an overflowing extent
+    return c;
+}
+
+// partial[b * 5 + {0..4}] = xmin, xmax, ymin, ymax, number of finite points of block b
+__global__ void __launch_bounds__(NB_BLOCK) nb_bbox_kernel(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z,
+                                                           int64_t n, double* __restrict__ partial) {
+    __shared__ double red[NB_BLOCK];
+    double v[5] = {INFINITY, -INFINITY, INFINITY, -INFINITY, 0.0};
+    for (int64_t i = (int64_t)blockIdx.x * NB_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * NB_BLOCK) {
+        const double xi = x[i], yi = y[i];
+        if (nb_finite(xi) && nb_finite(yi) && (!z || nb_finite(z[i]))) {
+            v[0] = xi < v[0] ? xi : v[0];
+            v[1] = xi > v[1] ? xi : v[1];
+            v[2] = yi < v[2] ? yi : v[2];
+            v[3] = yi > v[3] ? yi : v[3];
+            v[4] += 1.0;  // exact: n < 2^53
+        }
+    }
+    for (int k = 0; k < 5; k++) {
+        red[threadIdx.x] = v[k];
+        __syncthreads();
+        for (int s = NB_BLOCK / 2; s > 0; s >>= 1) {
+            if ((int)threadIdx.x < s) {
+                const double a = red[threadIdx.x], b = red[threadIdx.x + s];
+                red[threadIdx.x] = k == 4 ? a + b : ((k & 1) ? (b > a ? b : a) : (b < a ? b : a));
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) partial[(int64_t)blockIdx.x * 5 + k] = red[0];
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(NB_BLOCK) nb_key_kernel(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z,
+                                                          int64_t n, NbGrid g, uint32_t* __restrict__ key, uint32_t* __restrict__ idx) {
+    const int64_t i = (int64_t)blockIdx.x * NB_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const double xi = x[i], yi = y[i];
+    uint32_t k = g.ncells;
+    if (nb_finite(xi) && nb_finite(yi) && (!z || nb_finite(z[i])))
+        k = (uint32_t)cell_of(yi, g.ymin, g.h, g.ncy) * (uint32_t)g.ncx + (uint32_t)cell_of(xi, g.xmin, g.h, g.ncx);
+    key[i] = k;
+    idx[i] = (uint32_t)i;
+}
+
+// sorted slot k: coordinates of its point, and the slot range [cell_begin[c], cell_end[c]) of every occupied cell c (the two
+// arrays were zeroed: an empty cell has the empty range [0, 0)); both arrays have ncells + 1 entries, the last is the sentinel's
+__global__ void __launch_bounds__(NB_BLOCK) nb_gather_kernel(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z,
+                                                             const uint8_t* __restrict__ src, int64_t n, const uint32_t* __restrict__ key_s,
+                                                             const uint32_t* __restrict__ idx_s, double* __restrict__ xs, double* __restrict__ ys,
+                                                             double* __restrict__ zs, uint8_t* __restrict__ srcs, uint32_t* __restrict__ cell_begin,
+                                                             uint32_t* __restrict__ cell_end) {
+    const int64_t k = (int64_t)blockIdx.x * NB_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t i = idx_s[k];
+    xs[k] = x[i];
+    ys[k] = y[i];
+    if (z) zs[k] = z[i];
+    srcs[k] = src ? (uint8_t)(src[i] != 0) : (uint8_t)1;
+    const uint32_t c = key_s[k];
+    if (k == 0 || key_s[k - 1] != c) cell_begin[c] = (uint32_t)k;
+    if (k == n - 1 || key_s[k + 1] != c) cell_end[c] = (uint32_t)(k + 1);
+}
+
+struct NbQuery {
+    int64_t n;
+    NbGrid g;
+    double radius;
+    int32_t no_coincident;
+    const uint32_t *key_s, *idx_s, *cell_begin, *cell_end;
+    const double *xs, *ys, *zs;
+    const uint8_t* srcs;
+    // outputs, by original index
+    int64_t* count;           // COUNT
+    int64_t* near_j;          // NEAREST
+    double* near_d;
+    const int64_t* starts;    // FILL: n + 1 row starts
+    uint32_t *pair_i, *pair_j;
+    int32_t* flag;
+};
+
+enum { NB_COUNT = 0, NB_NEAREST = 1, NB_FILL = 2 };
+
+template <int MODE, bool HASZ>
+__global__ void __launch_bounds__(NB_BLOCK) nb_query_kernel(NbQuery q) {
+    const int64_t k = (int64_t)blockIdx.x * NB_BLOCK + threadIdx.x;
+    if (k >= q.n) return;
+    const uint32_t i = q.idx_s[k];
+    const uint32_t key = q.key_s[k];
+    int64_t cnt = 0;
+    int64_t best_j = -1;
+    double best_d = INFINITY;
+    int64_t w = 0, w_end = 0;
+    if (MODE == NB_FILL) {
+        w = q.starts[i];
+        w_end = q.starts[i + 1];
+    }
+    if (key != q.g.ncells) {  // a finite point
+        const int32_t cy = (int32_t)(key / (uint32_t)q.g.ncx), cx = (int32_t)(key - (uint32_t)cy * (uint32_t)q.g.ncx);
+        const double xi = q.xs[k], yi = q.ys[k], zi = HASZ ? q.zs[k] : 0.0;
+        for (int32_t oy = -1; oy <= 1; oy++) {
+            const int32_t yy = cy + oy;
+            if (yy < 0 || yy >= q.g.ncy) continue;
+            for (int32_t ox = -1; ox <= 1; ox++) {
+                const int32_t xx = cx + ox;
+                if (xx < 0 || xx >= q.g.ncx) continue;
+                const uint32_t c = (uint32_t)yy * (uint32_t)q.g.ncx + (uint32_t)xx;
+                const int64_t pb = q.cell_begin[c], pe = q.cell_end[c];  // pe <= n: written by nb_gather_kernel from slot numbers
+                for (int64_t p = pb; p < pe; p++) {
+                    if (p == k || !q.srcs[p]) continue;
+                    const double dx = q.xs[p] - xi, dy = q.ys[p] - yi;
+                    double s = dx * dx + dy * dy;
+                    if (HASZ) {
+                        const double dz = q.zs[p] - zi;
+                        s = s + dz * dz;
+                    }
+                    const double d = sqrt(s);
+                    if (!(d < q.radius)) continue;
+                    if (q.no_coincident && !(d > 0.0)) continue;
+                    if (MODE == NB_COUNT) cnt++;
+                    if (MODE == NB_NEAREST) {
+                        const int64_t j = q.idx_s[p];
+                        if (d < best_d || (d == best_d && j < best_j)) {
+                            best_d = d;
+                            best_j = j;
+                        }
+                    }
+                    if (MODE == NB_FILL) {
+                        if (w < w_end) {
+                            q.pair_i[w] = i;
+                            q.pair_j[w] = q.idx_s[p];
+                        } else {
+                            *q.flag = 1;  // more neighbours than the count pass announced: never write past the row
+                        }
+                        w++;
+                    }
+                }
+            }
+        }
+    }
+    if (MODE == NB_COUNT) q.count[i] = cnt;
+    if (MODE == NB_NEAREST) {
+        q.near_j[i] = best_j;
+        q.near_d[i] = best_d;
+    }
+    if (MODE == NB_FILL && w != w_end) *q.flag = 1;
+}
+
+// one lane per pair, rows already ordered by j: the values NumPy computes from the original arrays
+template <bool HASZ>
+__global__ void __launch_bounds__(NB_BLOCK) nb_finish_kernel(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ z,
+                                                             int64_t n, int64_t total, const uint32_t* __restrict__ pair_i,
+                                                             const uint32_t* __restrict__ pair_j, int64_t* __restrict__ out_j, double* __restrict__ out_dx,
+                                                             double* __restrict__ out_dy, double* __restrict__ out_dz, double* __restrict__ out_dist,
+                                                             int32_t* __restrict__ flag) {
+    const int64_t p = (int64_t)blockIdx.x * NB_BLOCK + threadIdx.x;
+    if (p >= total) return;
+    const uint32_t i = pair_i[p], j = pair_j[p];
+    if ((int64_t)i >= n || (int64_t)j >= n) {  // cannot happen after a clean fill; never read out of bounds
+        *flag = 1;
+        return;
+    }
+    const double dx = x[j] - x[i], dy = y[j] - y[i];
+    double s = dx * dx + dy * dy;
+    if (HASZ) {
+        const double dz = z[j] - z[i];
+        s = s + dz * dz;
+        out_dz[p] = dz;
+    }
+    out_j[p] = (int64_t)j;
+    out_dx[p] = dx;
+    out_dy[p] = dy;
+    out_dist[p] = sqrt(s);
+}
+
+struct Buf {  // grow-only device buffer
+    void* p = nullptr;
+    size_t cap = 0;
+    hipError_t need(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    void drop() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T>
+    T* as() const {
+        return (T*)p;
+    }
+};
+
+inline unsigned blocks_for(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + NB_BLOCK - 1) / NB_BLOCK); }
+
+inline unsigned bits_for(uint64_t max_value) {  // radix bits that cover 0 .. max_value
+    unsigned b = 1;
+    while (b < 32 && (max_value >> b) != 0) b++;
+    return b;
+}
+
+#define NB_TRY(call)                                                                   \
+    do {                                                                               \
+        hipError_t e_ = (call);                                                        \
+        if (e_ != hipSuccess) {                                                        \
+            if (err) *err = std::string("neighbors: " #call ": ") + hipGetErrorString(e_); \
+            return -1;                                                                 \
+        }                                                                              \
+    } while (0)
+
+}  // namespace
+
+struct Neighbors {
+    // per point
+    Buf x, y, z, src, key, key_s, idx, idx_s, xs, ys, zs, srcs, count, starts, near_j, near_d;
+    // per cell, per call
+    Buf cell_begin, cell_end, partial, tmp, flag;
+    // per pair
+    Buf pair_i, pair_j, pair_js, out_j, out_dx, out_dy, out_dz, out_dist;
+    bool built = false, has_z = false, has_src = false;
+    int64_t n = 0, nvalid = 0, total = -1;
+    double radius = 0;
+    int32_t flags = 0, doublings = 0;
+    NbGrid g{};
+
+    Buf* all[29] = {&x, &y, &z, &src, &key, &key_s, &idx, &idx_s, &xs, &ys, &zs, &srcs, &count, &starts, &near_j, &near_d,
+                    &cell_begin, &cell_end, &partial, &tmp, &flag, &pair_i, &pair_j, &pair_js, &out_j, &out_dx, &out_dy, &out_dz, &out_dist};
+
+    NbQuery query() const {
+        NbQuery q{};
+        q.n = n;
+        q.g = g;
+        q.radius = radius;
+        q.no_coincident = (flags & 1) != 0;
+        q.key_s = key_s.as<uint32_t>();
+        q.idx_s = idx_s.as<uint32_t>();
+        q.cell_begin = cell_begin.as<uint32_t>();
+        q.cell_end = cell_end.as<uint32_t>();
+        q.xs = xs.as<double>();
+        q.ys = ys.as<double>();
+        q.zs = has_z ? zs.as<double>() : nullptr;
+        q.srcs = srcs.as<uint8_t>();
+        q.flag = flag.as<int32_t>();
+        return q;
+    }
+};
+
+Neighbors* neighbors_create() { return new Neighbors(); }
+
+void neighbors_release(Neighbors* nb) {
+    if (!nb) return;
+    for (Buf* b : nb->all) b->drop();
+    nb->built = false;
+    nb->n = 0;
+    nb->total = -1;
+}
+
+void neighbors_free(Neighbors* nb) {
+    if (!nb) return;
+    neighbors_release(nb);
+    delete nb;
+}
+
+void neighbors_info(const Neighbors* nb, NeighborsInfo* out) {
+    *out = NeighborsInfo();
+    if (!nb || !nb->built) return;
+    out->n = nb->n;
+    out->nvalid = nb->nvalid;
+    out->ncx = nb->g.ncx;
+    out->ncy = nb->g.ncy;
+    out->h = nb->g.h;
+    out->doublings = nb->doublings;
+    out->total = nb->total;
+}
+
+int neighbors_build(Neighbors* nb, hipStream_t stream, int64_t n, const double* x, const double* y, const double* z, const uint8_t* sources,
+                    double radius, int32_t flags, std::string* err) {
+    nb->built = false;
+    nb->total = -1;
+    if (n < 0 || n > NB_MAX_POINTS) {
+        if (err) *err = "neighbors: n must be between 0 and 2147483646";
+        return -2;
+    }
+    if (!(radius > 0.0) || !(radius <= DBL_MAX)) {
+        if (err) *err = "neighbors: radius must be a finite positive number";
+        return -2;
+    }
+    if (n > 0 && (!x || !y)) {
+        if (err) *err = "neighbors: x and y must not be NULL";
+        return -2;
+    }
+    nb->n = n;
+    nb->radius = radius;
+    nb->flags = flags;
+    nb->has_z = z != nullptr;
+    nb->has_src = sources != nullptr;
+    nb->nvalid = 0;
+    nb->doublings = 0;
+    nb->g = NbGrid{0.0, 0.0, radius, 1, 1, 1u};
+    NB_TRY(nb->flag.need(sizeof(int32_t)));
+    if (n == 0) {
+        nb->built = true;
+        return 0;
+    }
+    const size_t nd = (size_t)n * sizeof(double), nu = (size_t)n * sizeof(uint32_t);
+    NB_TRY(nb->x.need(nd));
+    NB_TRY(nb->y.need(nd));
+    NB_TRY(nb->xs.need(nd));
+    NB_TRY(nb->ys.need(nd));
+    if (z) {
+        NB_TRY(nb->z.need(nd));
+        NB_TRY(nb->zs.need(nd));
+    }
+    if (sources) NB_TRY(nb->src.need((size_t)n));
+    NB_TRY(nb->srcs.need((size_t)n));
+    NB_TRY(nb->key.need(nu));
+    NB_TRY(nb->key_s.need(nu));
+    NB_TRY(nb->idx.need(nu));
+    NB_TRY(nb->idx_s.need(nu));
+    NB_TRY(nb->partial.need((size_t)NB_BBOX_BLOCKS * 5 * sizeof(double)));
+    NB_TRY(hipMemcpyAsync(nb->x.p, x, nd, hipMemcpyHostToDevice, stream));
+    NB_TRY(hipMemcpyAsync(nb->y.p, y, nd, hipMemcpyHostToDevice, stream));
+    if (z) NB_TRY(hipMemcpyAsync(nb->z.p, z, nd, hipMemcpyHostToDevice, stream));
+    if (sources) NB_TRY(hipMemcpyAsync(nb->src.p, sources, (size_t)n, hipMemcpyHostToDevice, stream));
+    const double* dz = z ? nb->z.as<double>() : nullptr;
+
+    // 1. bounding box of the finite points
+    const unsigned nbb = std::min<unsigned>(blocks_for(n), NB_BBOX_BLOCKS);
+    hipLaunchKernelGGL(nb_bbox_kernel, dim3(nbb), dim3(NB_BLOCK), 0, stream, nb->x.as<double>(), nb->y.as<double>(), dz, n, nb->partial.as<double>());
+    std::vector<double> partial((size_t)nbb * 5);
+    NB_TRY(hipMemcpyAsync(partial.data(), nb->partial.p, partial.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    NB_TRY(hipStreamSynchronize(stream));
+    double bb[4] = {INFINITY, -INFINITY, INFINITY, -INFINITY}, nvalid = 0;
+    for (unsigned b = 0; b < nbb; b++) {
+        const double* r = &partial[(size_t)b * 5];
+        bb[0] = std::min(bb[0], r[0]);
+        bb[1] = std::max(bb[1], r[1]);
+        bb[2] = std::min(bb[2], r[2]);
+        bb[3] = std::max(bb[3], r[3]);
+        nvalid += r[4];
+    }
+    nb->nvalid = (int64_t)nvalid;
+
+    // 2. cell size (see the argument at NB_CELL_MARGIN): a hair above the radius, doubled until the grid is under the cap
+    NbGrid g{0.0, 0.0, radius, 1, 1, 1u};
+    if (nb->nvalid > 0) {
+        const int64_t cap = std::min(std::max(NB_CELL_CAP_MIN, 4 * n), NB_CELL_CAP_MAX);
+        const double ex = bb[1] - bb[0], ey = bb[3] - bb[2];
+        double h = std::max(radius * NB_CELL_MARGIN, NB_CELL_MIN);
+        bool fits = false;
+        int d = 0;
+        for (; d < 2200 && h <= DBL_MAX; d++) {  // 2200 doublings span every float64 exponent
+            const double fx = std::floor(ex / h) + 1.0, fy = std::floor(ey / h) + 1.0;
+            if (fx * fy <= (double)cap) {  // false for the NaN / inf of an overflowing extent
+                g.ncx = (int32_t)fx;
+                g.ncy = (int32_t)fy;
+                fits = true;
+                break;
+            }
+            h *= 2.0;
+        }
+        g.xmin = bb[0];
+        g.ymin = bb[2];
+        if (fits) {
+            g.h = h;
+            nb->doublings = d;
+        } else {  // xmax - xmin overflows: one cell, every pair is examined
+            g.h = DBL_MAX;
+            g.ncx = g.ncy = 1;
+        }
+        g.ncells = (uint32_t)((int64_t)g.ncx * g.ncy);
+    }
+    nb->g = g;
+
+    // 3. keys, stable sort, gather
+    const size_t cell_bytes = ((size_t)g.ncells + 1) * sizeof(uint32_t);
+    NB_TRY(nb->cell_begin.need(cell_bytes));
+    NB_TRY(nb->cell_end.need(cell_bytes));
+    NB_TRY(hipMemsetAsync(nb->cell_begin.p, 0, cell_bytes, stream));
+    NB_TRY(hipMemsetAsync(nb->cell_end.p, 0, cell_bytes, stream));
+    hipLaunchKernelGGL(nb_key_kernel, dim3(blocks_for(n)), dim3(NB_BLOCK), 0, stream, nb->x.as<double>(), nb->y.as<double>(), dz, n, g,
+                       nb->key.as<uint32_t>(), nb->idx.as<uint32_t>());
+    const unsigned bits = bits_for(g.ncells);
+    size_t tb = 0;
+    NB_TRY(rocprim::radix_sort_pairs(nullptr, tb, nb->key.as<uint32_t>(), nb->key_s.as<uint32_t>(), nb->idx.as<uint32_t>(), nb->idx_s.as<uint32_t>(),
+                                     (size_t)n, 0u, bits, stream));
+    NB_TRY(nb->tmp.need(std::max<size_t>(tb, 16)));
+    NB_TRY(rocprim::radix_sort_pairs(nb->tmp.p, tb, nb->key.as<uint32_t>(), nb->key_s.as<uint32_t>(), nb->idx.as<uint32_t>(), nb->idx_s.as<uint32_t>(),
+                                     (size_t)n, 0u, bits, stream));
+    hipLaunchKernelGGL(nb_gather_kernel, dim3(blocks_for(n)), dim3(NB_BLOCK), 0, stream, nb->x.as<double>(), nb->y.as<double>(), dz,
+                       sources ? nb->src.as<uint8_t>() : nullptr, n, nb->key_s.as<uint32_t>(), nb->idx_s.as<uint32_t>(), nb->xs.as<double>(),
+                       nb->ys.as<double>(), z ? nb->zs.as<double>() : nullptr, nb->srcs.as<uint8_t>(), nb->cell_begin.as<uint32_t>(),
+                       nb->cell_end.as<uint32_t>());
+    NB_TRY(hipGetLastError());
+    NB_TRY(hipStreamSynchronize(stream));
+    nb->built = true;
+    return 0;
+}
+
+namespace {
+int need_built(const Neighbors* nb, std::string* err) {
+    if (nb && nb->built) return 0;
+    if (err) *err = "neighbors: no cell list (build one first)";
+    return -2;
+}
+
+template <int MODE>
+void launch_query(const Neighbors* nb, hipStream_t stream, const NbQuery& q) {
+    if (nb->has_z) hipLaunchKernelGGL((nb_query_kernel<MODE, true>), dim3(blocks_for(q.n)), dim3(NB_BLOCK), 0, stream, q);
+    else hipLaunchKernelGGL((nb_query_kernel<MODE, false>), dim3(blocks_for(q.n)), dim3(NB_BLOCK), 0, stream, q);
+}
+}  // namespace
+
+int neighbors_counts(Neighbors* nb, hipStream_t stream, int64_t* counts, int64_t* total, std::string* err) {
+    if (int rc = need_built(nb, err)) return rc;
+    const int64_t n = nb->n;
+    nb->total = -1;
+    if (n == 0) {
+        nb->total = 0;
+        if (total) *total = 0;
+        return 0;
+    }
+    // count[n] = 0, so that the exclusive scan over n + 1 entries ends with the total
+    const size_t bytes = (size_t)(n + 1) * sizeof(int64_t);
+    NB_TRY(nb->count.need(bytes));
+    NB_TRY(nb->starts.need(bytes));
+    NB_TRY(hipMemsetAsync(nb->count.as<int64_t>() + n, 0, sizeof(int64_t), stream));
+    NbQuery q = nb->query();
+    q.count = nb->count.as<int64_t>();
+    launch_query<NB_COUNT>(nb, stream, q);
+    size_t tb = 0;
+    NB_TRY(rocprim::exclusive_scan(nullptr, tb, nb->count.as<int64_t>(), nb->starts.as<int64_t>(), (int64_t)0, (size_t)(n + 1),
+                                   rocprim::plus<int64_t>(), stream));
+    NB_TRY(nb->tmp.need(std::max<size_t>(tb, 16)));
+    NB_TRY(rocprim::exclusive_scan(nb->tmp.p, tb, nb->count.as<int64_t>(), nb->starts.as<int64_t>(), (int64_t)0, (size_t)(n + 1),
+                                   rocprim::plus<int64_t>(), stream));
+    int64_t t = 0;
+    NB_TRY(hipMemcpyAsync(&t, nb->starts.as<int64_t>() + n, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    if (counts) NB_TRY(hipMemcpyAsync(counts, nb->count.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    NB_TRY(hipGetLastError());
+    NB_TRY(hipStreamSynchronize(stream));
+    nb->total = t;
+    if (total) *total = t;
+    return 0;
+}
+
+int neighbors_nearest(Neighbors* nb, hipStream_t stream, int64_t* j, double* dist, std::string* err) {
+    if (int rc = need_built(nb, err)) return rc;
+    const int64_t n = nb->n;
+    if (n == 0) return 0;
+    if (!j || !dist) {
+        if (err) *err = "neighbors: nearest needs both output arrays";
+        return -2;
+    }
+    NB_TRY(nb->near_j.need((size_t)n * sizeof(int64_t)));
+    NB_TRY(nb->near_d.need((size_t)n * sizeof(double)));
+    NbQuery q = nb->query();
+    q.near_j = nb->near_j.as<int64_t>();
+    q.near_d = nb->near_d.as<double>();
+    launch_query<NB_NEAREST>(nb, stream, q);
+    NB_TRY(hipMemcpyAsync(j, nb->near_j.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    NB_TRY(hipMemcpyAsync(dist, nb->near_d.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    NB_TRY(hipGetLastError());
+    NB_TRY(hipStreamSynchronize(stream));
+    return 0;
+}
+
+int neighbors_pairs(Neighbors* nb, hipStream_t stream, int64_t total, int64_t* starts, int64_t* j, double* dx, double* dy, double* dz,
+                    double* dist, std::string* err) {
+    if (int rc = need_built(nb, err)) return rc;
+    if (nb->total < 0) {
+        if (err) *err = "neighbors: pairs need the count pass first";
+        return -2;
+    }
+    if (total != nb->total) {
+        if (err) *err = "neighbors: pairs asked for " + std::to_string(total) + " pairs, the count pass announced " + std::to_string(nb->total);
+        return -2;
+    }
+    if (total > NB_MAX_PAIRS) {
+        if (err) *err = "neighbors: " + std::to_string(total) + " pairs exceed the 2147483647 one call can list";
+        return -2;
+    }
+    const int64_t n = nb->n;
+    if (!starts || (total > 0 && (!j || !dx || !dy || !dist || (nb->has_z && !dz)))) {
+        if (err) *err = "neighbors: pairs need every output array";
+        return -2;
+    }
+    if (n == 0) {
+        starts[0] = 0;
+        return 0;
+    }
+    NB_TRY(hipMemcpyAsync(starts, nb->starts.p, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    if (total == 0) {
+        NB_TRY(hipStreamSynchronize(stream));
+        return 0;
+    }
+    const size_t pu = (size_t)total * sizeof(uint32_t), pd = (size_t)total * sizeof(double);
+    NB_TRY(nb->pair_i.need(pu));
+    NB_TRY(nb->pair_j.need(pu));
+    NB_TRY(nb->pair_js.need(pu));
+    NB_TRY(nb->out_j.need(pd));
+    NB_TRY(nb->out_dx.need(pd));
+    NB_TRY(nb->out_dy.need(pd));
+    NB_TRY(nb->out_dist.need(pd));
+    if (nb->has_z) NB_TRY(nb->out_dz.need(pd));
+    NB_TRY(hipMemsetAsync(nb->flag.p, 0, sizeof(int32_t), stream));
+    // fill: unordered within a row
+    NbQuery q = nb->query();
+    q.starts = nb->starts.as<int64_t>();
+    q.pair_i = nb->pair_i.as<uint32_t>();
+    q.pair_j = nb->pair_j.as<uint32_t>();
+    launch_query<NB_FILL>(nb, stream, q);
+    // rows ordered by j
+    const int64_t* offs = nb->starts.as<int64_t>();
+    const unsigned bits = bits_for((uint64_t)n);
+    size_t tb = 0;
+    NB_TRY(rocprim::segmented_radix_sort_keys(nullptr, tb, nb->pair_j.as<uint32_t>(), nb->pair_js.as<uint32_t>(), (unsigned)total, (unsigned)n, offs,
+                                              offs + 1, 0u, bits, stream));
+    NB_TRY(nb->tmp.need(std::max<size_t>(tb, 16)));
+    NB_TRY(rocprim::segmented_radix_sort_keys(nb->tmp.p, tb, nb->pair_j.as<uint32_t>(), nb->pair_js.as<uint32_t>(), (unsigned)total, (unsigned)n, offs,
+                                              offs + 1, 0u, bits, stream));
+    const double* zz = nb->has_z ? nb->z.as<double>() : nullptr;
+    if (nb->has_z)
+        hipLaunchKernelGGL((nb_finish_kernel<true>), dim3(blocks_for(total)), dim3(NB_BLOCK), 0, stream, nb->x.as<double>(), nb->y.as<double>(), zz, n,
+                           total, nb->pair_i.as<uint32_t>(), nb->pair_js.as<uint32_t>(), nb->out_j.as<int64_t>(), nb->out_dx.as<double>(),
+                           nb->out_dy.as<double>(), nb->out_dz.as<double>(), nb->out_dist.as<double>(), nb->flag.as<int32_t>());
+    else
+        hipLaunchKernelGGL((nb_finish_kernel<false>), dim3(blocks_for(total)), dim3(NB_BLOCK), 0, stream, nb->x.as<double>(), nb->y.as<double>(), zz, n,
+                           total, nb->pair_i.as<uint32_t>(), nb->pair_js.as<uint32_t>(), nb->out_j.as<int64_t>(), nb->out_dx.as<double>(),
+                           nb->out_dy.as<double>(), (double*)nullptr, nb->out_dist.as<double>(), nb->flag.as<int32_t>());
+    int32_t flag = 0;
+    NB_TRY(hipMemcpyAsync(&flag, nb->flag.p, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    NB_TRY(hipGetLastError());
+    NB_TRY(hipStreamSynchronize(stream));
+    if (flag) {
+        if (err) *err = "neighbors: the fill pass disagreed with the count pass (no pair was written out of its row)";
+        return -3;
+    }
+    NB_TRY(hipMemcpyAsync(j, nb->out_j.p, pd, hipMemcpyDeviceToHost, stream));
+    NB_TRY(hipMemcpyAsync(dx, nb->out_dx.p, pd, hipMemcpyDeviceToHost, stream));
+    NB_TRY(hipMemcpyAsync(dy, nb->out_dy.p, pd, hipMemcpyDeviceToHost, stream));
+    if (nb->has_z) NB_TRY(hipMemcpyAsync(dz, nb->out_dz.p, pd, hipMemcpyDeviceToHost, stream));
+    NB_TRY(hipMemcpyAsync(dist, nb->out_dist.p, pd, hipMemcpyDeviceToHost, stream));
+    NB_TRY(hipStreamSynchronize(stream));
+    return 0;
+}
+
+}  // namespace pk
