@@ -540,6 +540,29 @@ int32_t pk_neighbors_pairs(pk_ctx* ctx, int64_t total, int64_t* starts, int64_t*
 int32_t pk_neighbors_info(pk_ctx* ctx, pk_neighbors_info_t* out);
 /* Free the cell list and its scratch now instead of with the context (the tutorial's matrices die with each kernel call). */
 int32_t pk_neighbors_release(pk_ctx* ctx);
+/* The same search on a spherical mesh (the tutorial runs on a flat one; NEMO, CROCO and FESOM fieldsets are spherical): x = longitude and
+ * y = latitude in degrees, longitudes equivalent modulo 360, z and radius_m in metres, sphere_radius_m = the mesh's radius, radius_m <
+ * (pi / 2) sphere_radius_m.  With rad = pi / 180, every operation rounded on its own:
+ *   dx = d - 360 rint(d / 360), d = x[j] - x[i];  dy = y[j] - y[i];  dz = z[j] - z[i]
+ *   a = sin(0.5 rad dy)^2 + cos(rad y[i]) cos(rad y[j]) sin(0.5 rad dx)^2;  dh = 2 R asin(min(1, sqrt(a)))
+ *   dist = dh, or sqrt(dh dh + dz dz) with z
+ * and the neighbour rule above.  A point with a non-finite coordinate or |y| > 90 has no neighbours and is nobody's neighbour.  dx, dy, dz
+ * are NumPy's bit for bit, dist within the ulps of sin, cos and asin.  Cell list: latitude bands cut into longitude cells that widen
+ * towards the poles, over the extent of the valid points.  Replaces the context's previous cell list; pk_neighbors_counts / _nearest /
+ * _pairs then serve this one (the tutorial's `distances` matrices, in metres along great circles). */
+int32_t pk_neighbors_build_spherical(pk_ctx* ctx, int64_t n, const double* x, const double* y, const double* z, const uint8_t* sources,
+                                     double radius_m, double sphere_radius_m, int32_t flags);
+typedef struct {
+    int64_t n, nvalid;     /* points of the cell list; those with finite coordinates and |y| <= 90 */
+    int64_t bands, cells;  /* latitude bands; longitude cells summed over the bands */
+    int64_t total;         /* pairs the last count pass announced, -1 before it */
+    double band_height;    /* degrees; >= the angular radius (1 + 2^-16), doubled `doublings` times to get under the band and cell caps */
+    int32_t periodic;      /* 1: the bands wrap over 360 degrees; 0: the cells span the arc the valid points lie in */
+    int32_t doublings;
+} pk_neighbors_info_spherical_t;
+/* What the last spherical build chose; zeros after a flat build, as pk_neighbors_info gives zeros after a spherical one (the tutorial has
+ * no counterpart: diagnostics and tests). */
+int32_t pk_neighbors_info_spherical(pk_ctx* ctx, pk_neighbors_info_spherical_t* out);
 
 /* achieved copy bandwidth probe (device-to-device float4 copy), GB/s; used as a measured roofline denominator */
 int32_t pk_measure_copy_bandwidth(pk_ctx* ctx, int64_t bytes, int32_t iters, double* gbps);

@@ -221,6 +221,11 @@ class NeighborsInfo(C.Structure):  # pk_neighbors_info_t
                 ("cell_size", C.c_double), ("doublings", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class NeighborsSphInfo(C.Structure):  # pk_neighbors_info_spherical_t
+    _fields_ = [("n", C.c_int64), ("nvalid", C.c_int64), ("bands", C.c_int64), ("cells", C.c_int64), ("total", C.c_int64),
+                ("band_height", C.c_double), ("periodic", C.c_int32), ("doublings", C.c_int32)]
+
+
 PK_NEIGHBORS_NO_COINCIDENT = 1
 
 ABI_SYMBOLS = [
@@ -271,6 +276,8 @@ ABI_SYMBOLS = [
     "pk_neighbors_pairs",
     "pk_neighbors_info",
     "pk_neighbors_release",
+    "pk_neighbors_build_spherical",
+    "pk_neighbors_info_spherical",
     "pk_measure_copy_bandwidth",
     "pk_set_option",
     "pk_upload_stats",
@@ -381,6 +388,9 @@ def load():
     lib.pk_neighbors_pairs.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 6
     lib.pk_neighbors_info.argtypes = [C.c_void_p, C.POINTER(NeighborsInfo)]
     lib.pk_neighbors_release.argtypes = [C.c_void_p]
+    lib.pk_neighbors_build_spherical.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                                 C.c_int32]
+    lib.pk_neighbors_info_spherical.argtypes = [C.c_void_p, C.POINTER(NeighborsSphInfo)]
     if lib.pk_abi_version() != PK_ABI_VERSION:
         raise HipLibraryError(f"ABI version mismatch: library {lib.pk_abi_version()}, binding {PK_ABI_VERSION}")
     _lib = lib

@@ -3096,6 +3096,31 @@ int32_t pk_neighbors_info(pk_ctx* ctx, pk_neighbors_info_t* out) {
     return 0;
 }
 
+int32_t pk_neighbors_build_spherical(pk_ctx* ctx, int64_t n, const double* x, const double* y, const double* z, const uint8_t* sources,
+                                     double radius_m, double sphere_radius_m, int32_t flags) {
+    if (!ctx) return -2;
+    PK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->nbr) ctx->nbr = neighbors_create();
+    std::string msg;
+    if (neighbors_build_spherical(ctx->nbr, ctx->compute, n, x, y, z, sources, radius_m, sphere_radius_m, flags, &msg)) return ctx->fail(msg);
+    return 0;
+}
+
+int32_t pk_neighbors_info_spherical(pk_ctx* ctx, pk_neighbors_info_spherical_t* out) {
+    if (!ctx || !out) return -2;
+    NeighborsSphInfo i;
+    neighbors_info_spherical(ctx->nbr, &i);
+    out->n = i.n;
+    out->nvalid = i.nvalid;
+    out->bands = i.bands;
+    out->cells = i.cells;
+    out->total = i.total;
+    out->band_height = i.band_height;
+    out->periodic = i.periodic;
+    out->doublings = i.doublings;
+    return 0;
+}
+
 int32_t pk_neighbors_release(pk_ctx* ctx) {
     if (!ctx) return -2;
     if (!ctx->nbr) return 0;

@@ -7,6 +7,20 @@
 // j is a neighbour of i iff i != j, dist < radius (strict), sources[j] (when given) and dist > 0 (PK_NEIGHBORS_NO_COINCIDENT).
 // A particle with a non-finite coordinate has no neighbours and is nobody's neighbour.  Rows are ordered by i, j ascends
 // within a row; the nearest neighbour is the smallest dist, ties to the smallest j.
+//
+// Spherical meshes (neighbors_build_spherical): x = longitude and y = latitude in degrees, any representation of the longitude
+// (values are equivalent modulo 360), z and radius in metres, R = the sphere's radius, radius < (pi / 2) R.  With rad = pi / 180
+// and every operation rounded on its own:
+//   dx   = d - 360*rint(d/360),  d = x[j] - x[i]          degrees, in [-180, 180]
+//   dy   = y[j] - y[i]                                    degrees
+//   dz   = z[j] - z[i]                                    metres
+//   a    = sin(0.5*rad*dy)**2 + cos(rad*y[i])*cos(rad*y[j])*sin(0.5*rad*dx)**2
+//   dh   = 2*R*arcsin(min(1, sqrt(a)))                    metres
+//   dist = dh without z, sqrt(dh*dh + dz*dz) with z
+// The neighbour rule, the row order and the nearest neighbour are those above.  A particle with a non-finite coordinate or with
+// |y| > 90 has no neighbours and is nobody's neighbour.  dx, dy, dz are the NumPy values bit for bit; dist goes through sin, cos
+// and asin, whose device versions differ from NumPy's by ulps.  Points that coincide modulo 360 give a == 0 and dist == 0 exactly;
+// two points mirrored east and west of a third on one latitude give the same dist bit for bit (sin is odd).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,6 +39,15 @@ struct NeighborsInfo {
     int64_t total = -1;         // pairs of the last count pass, -1 before it
 };
 
+struct NeighborsSphInfo {
+    int64_t n = 0, nvalid = 0;    // points, valid points
+    int64_t bands = 0, cells = 0;  // latitude bands, longitude cells summed over them
+    double band_height = 0;       // degrees
+    int32_t periodic = 0;         // the bands wrap over 360 degrees (else: the cells span the arc of the valid points)
+    int32_t doublings = 0;        // times the band height was doubled to get under the band and cell caps
+    int64_t total = -1;           // pairs of the last count pass, -1 before it
+};
+
 Neighbors* neighbors_create();
 void neighbors_free(Neighbors* nb);     // everything, the object included
 void neighbors_release(Neighbors* nb);  // the device scratch only; the next build allocates again
@@ -33,11 +56,15 @@ void neighbors_release(Neighbors* nb);  // the device scratch only; the next bui
 // point, non-zero = source) are HOST arrays of length n; the outputs are host arrays too.
 int neighbors_build(Neighbors* nb, hipStream_t stream, int64_t n, const double* x, const double* y, const double* z, const uint8_t* sources,
                     double radius, int32_t flags, std::string* err);
+// The cell list of a spherical mesh; counts, nearest and pairs then serve it.
+int neighbors_build_spherical(Neighbors* nb, hipStream_t stream, int64_t n, const double* x, const double* y, const double* z,
+                              const uint8_t* sources, double radius, double sphere_radius, int32_t flags, std::string* err);
 int neighbors_counts(Neighbors* nb, hipStream_t stream, int64_t* counts, int64_t* total, std::string* err);
 int neighbors_nearest(Neighbors* nb, hipStream_t stream, int64_t* j, double* dist, std::string* err);
 // after neighbors_counts; total = what it announced.  starts: n + 1; j, dx, dy, dz (NULL without z), dist: total
 int neighbors_pairs(Neighbors* nb, hipStream_t stream, int64_t total, int64_t* starts, int64_t* j, double* dx, double* dy, double* dz,
                     double* dist, std::string* err);
-void neighbors_info(const Neighbors* nb, NeighborsInfo* out);
+void neighbors_info(const Neighbors* nb, NeighborsInfo* out);                    // zeros after a spherical build
+void neighbors_info_spherical(const Neighbors* nb, NeighborsSphInfo* out);      // zeros after a flat build
 
 }  // namespace pk

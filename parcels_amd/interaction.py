@@ -14,6 +14,22 @@ Semantics: points are float64 (float32 columns are widene
 non-finite coordinate has no neighbours and is nobody's neighbour.  Rows are ordered by i, j ascends within a row; the nearest
 neighbour is the smallest dist, ties to the smallest j.  Indices are local to the view passed in.
 
+Spherical meshes: ``mesh="spherical"``, a ``SphericalMesh`` or the ``fieldset`` of a kernel body (``mesh=fieldset``: the mesh of its
+first grid) switch to great-circle distances.  ``x`` is then the longitude and ``y`` the latitude in degrees -- longitudes are
+equivalent modulo 360, so -180..180, 0..360 and values past either end mix freely -- and ``radius``, ``z`` and ``dist`` are in metres;
+``radius`` must stay below a quarter of the circumference.  With ``rad = pi / 180`` and R the mesh's radius::
+
+    dx   = d - 360*rint(d/360),  d = x[j] - x[i]          # degrees, in [-180, 180]: wrapped across the antimeridian
+    dy   = y[j] - y[i]
+    a    = sin(0.5*rad*dy)**2 + cos(rad*y[i])*cos(rad*y[j])*sin(0.5*rad*dx)**2
+    dh   = 2*R*arcsin(min(1, sqrt(a)))
+    dist = dh            (z=False)      sqrt(dh*dh + dz*dz)   (z=True)
+
+``dx``, ``dy``, ``dz`` equal the NumPy expressions bit for bit; ``dist`` passes through ``sin``, ``cos`` and ``arcsin``, whose device
+versions differ from NumPy's by ulps (the package's parity bar of 1e-12 relative holds with room).  A particle with ``|y| > 90`` is
+treated like one with a non-finite coordinate.  ``mesh="flat"``, the default, is the Euclidean search above for every particle set,
+also one on a spherical fieldset: the mesh is never guessed.
+
 There is no CPU path: without a GPU every call raises ``HipLibraryError`` like every other device call of the package.
 """
 
@@ -117,7 +133,7 @@ def _columns(particles, z: bool):
     return cols[0], cols[1], (cols[2] if z else None)
 
 
-def _validate(particles, radius, z, sources, max_pairs=None):
+def _validate(particles, radius, z, sources, max_pairs=None, mesh="flat"):
     if isinstance(radius, bool) or not isinstance(radius, (numbers.Real, np.floating, np.integer)):
         raise TypeError(f"radius: expected a finite positive number, got {type(radius).__name__}")
     radius = float(radius)
@@ -137,51 +153,77 @@ def _validate(particles, radius, z, sources, max_pairs=None):
             raise TypeError(f"max_pairs: expected a non-negative integer or None, got {type(max_pairs).__name__}")
         if max_pairs < 0:
             raise ValueError(f"max_pairs: expected a non-negative integer or None, got {max_pairs}")
-    return radius, x, y, zz, src
+    return radius, x, y, zz, src, _sphere_radius(mesh, radius)
+
+
+def _sphere_radius(mesh, radius):
+    """None for a flat mesh, else the radius of the sphere; checks ``radius`` against a quarter of its circumference."""
+    from .fieldset import FieldSet
+    from .xgrid import FlatMesh, SphericalMesh, get_mesh
+
+    if isinstance(mesh, FieldSet):
+        fields = list(mesh.fields.values())
+        if not fields:
+            raise ValueError("mesh: the FieldSet has no field, so no grid to take the mesh from")
+        mesh = fields[0].grid._mesh  # the first grid of fieldset.gridset
+    if not isinstance(mesh, (str, FlatMesh, SphericalMesh)):  # get_mesh compares with ==, which an array answers element-wise
+        raise ValueError(f"mesh must be 'flat', 'spherical', or a SphericalMesh object. Got {mesh=!r}")
+    mesh = get_mesh(mesh)
+    if not mesh.is_spherical():
+        return None
+    sphere = float(mesh.radius)
+    if not radius < 0.5 * math.pi * sphere:
+        raise ValueError(f"radius: {radius!r} is not below a quarter of the circumference of the mesh's sphere, {0.5 * math.pi * sphere!r} "
+                         f"(sphere radius {sphere!r}); great-circle neighbour search needs radius < (pi / 2) R")
+    return sphere
 
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-def _build(ctx, radius, x, y, z, src, include_coincident):
+def _build(ctx, radius, x, y, z, src, include_coincident, sphere=None):
     from . import _hip
 
     flags = 0 if include_coincident else _hip.PK_NEIGHBORS_NO_COINCIDENT
+    if sphere is not None:
+        ctx.check(ctx.lib.pk_neighbors_build_spherical(ctx.handle, len(x), _ptr(x), _ptr(y), _ptr(z), _ptr(src), radius, sphere, flags),
+                  "pk_neighbors_build_spherical")
+        return
     ctx.check(ctx.lib.pk_neighbors_build(ctx.handle, len(x), _ptr(x), _ptr(y), _ptr(z), _ptr(src), radius, flags), "pk_neighbors_build")
 
 
-def neighbor_counts(particles, radius, *, z=False, sources=None, include_coincident=True):
+def neighbor_counts(particles, radius, *, z=False, sources=None, include_coincident=True, mesh="flat"):
     """Number of neighbours of every particle, int64[n]; builds no pair list."""
-    radius, x, y, zz, src = _validate(particles, radius, z, sources)
+    radius, x, y, zz, src, sphere = _validate(particles, radius, z, sources, mesh=mesh)
     ctx = _context()
-    _build(ctx, radius, x, y, zz, src, include_coincident)
+    _build(ctx, radius, x, y, zz, src, include_coincident, sphere)
     count = np.zeros(len(x), dtype=np.int64)
     total = C.c_int64()
     ctx.check(ctx.lib.pk_neighbors_counts(ctx.handle, _ptr(count), C.byref(total)), "pk_neighbors_counts")
     return count
 
 
-def nearest_neighbor(particles, radius, *, z=False, sources=None, include_coincident=True):
+def nearest_neighbor(particles, radius, *, z=False, sources=None, include_coincident=True, mesh="flat"):
     """(j, dist): index (int64[n], -1 without a neighbour) and distance (float64[n], inf without one) of the nearest neighbour
     within ``radius``; ties go to the smallest index."""
-    radius, x, y, zz, src = _validate(particles, radius, z, sources)
+    radius, x, y, zz, src, sphere = _validate(particles, radius, z, sources, mesh=mesh)
     ctx = _context()
-    _build(ctx, radius, x, y, zz, src, include_coincident)
+    _build(ctx, radius, x, y, zz, src, include_coincident, sphere)
     j = np.full(len(x), -1, dtype=np.int64)
     dist = np.full(len(x), np.inf, dtype=np.float64)
     ctx.check(ctx.lib.pk_neighbors_nearest(ctx.handle, _ptr(j), _ptr(dist)), "pk_neighbors_nearest")
     return j, dist
 
 
-def neighbors(particles, radius, *, z=False, sources=None, include_coincident=True, max_pairs=None):
+def neighbors(particles, radius, *, z=False, sources=None, include_coincident=True, max_pairs=None, mesh="flat"):
     """Every ordered pair (i, j) with j a neighbour of i, as a ``Neighbors`` CSR list.
 
     The total is known after the count pass; when it exceeds ``max_pairs`` a ``ValueError`` states the total and the cap, and
     nothing is allocated or fetched.  Default cap: what fits in ``MAX_PAIRS_MEMORY_SHARE`` of the free device memory."""
-    radius, x, y, zz, src = _validate(particles, radius, z, sources, max_pairs)
+    radius, x, y, zz, src, sphere = _validate(particles, radius, z, sources, max_pairs, mesh)
     ctx = _context()
-    _build(ctx, radius, x, y, zz, src, include_coincident)
+    _build(ctx, radius, x, y, zz, src, include_coincident, sphere)
     n = len(x)
     count = np.zeros(n, dtype=np.int64)
     total = C.c_int64()
@@ -216,6 +258,19 @@ def cell_list_info() -> dict:
     info = _hip.NeighborsInfo()
     ctx.check(ctx.lib.pk_neighbors_info(ctx.handle, C.byref(info)), "pk_neighbors_info")
     return {k: getattr(info, k) for k in ("n", "nvalid", "ncx", "ncy", "total", "cell_size", "doublings")}
+
+
+def cell_list_info_spherical() -> dict:
+    """What the last spherical build on the default context chose: points, valid points, latitude bands, longitude cells summed over
+    them, band height in degrees, whether the bands wrap over 360 degrees, doublings, announced total.  Zeros after a flat build."""
+    from . import _hip
+
+    ctx = _context()
+    info = _hip.NeighborsSphInfo()
+    ctx.check(ctx.lib.pk_neighbors_info_spherical(ctx.handle, C.byref(info)), "pk_neighbors_info_spherical")
+    out = {k: getattr(info, k) for k in ("n", "nvalid", "bands", "cells", "total", "band_height", "doublings")}
+    out["periodic"] = bool(info.periodic)
+    return out
 
 
 def release():

@@ -2,6 +2,7 @@
 """Time of the neighbour search behind particle-particle interaction kernels (parcels_amd/interaction.py, csrc/pk_neighbors.hip).
 
     python tools/bench_interaction.py [--particles 1e5,1e6,1e7] [--repeats 5] [--brute 2e4] [--out profiles/interaction_bench.json]
+    python tools/bench_interaction.py --mesh spherical [--regional 1e6] [--out profiles/interaction_sph_bench.json]
 
 Workload: uniform points in the unit square, radius chosen for a mean of about 8 neighbours (pi r^2 n = 8).  Per size the four
 passes of the C ABI are timed on their own -- build (upload + cell list), counts, nearest, pairs (fill + row sort + download; the
@@ -13,6 +14,11 @@ There is no earlier device implementation to compare with.  The yardstick is wha
 matrices at --brute points (the same box, one run: it takes seconds and gigabytes), with the device time at that size beside it and
 the counts of both compared.  Where scipy is installed, cKDTree.query_pairs at 1e6 is reported too (unordered pairs: half the list).
 Prints one JSON line per leg and writes them all to --out.
+
+--mesh spherical times the great-circle search with the same method: points uniform on the sphere, radius in metres chosen for a
+mean of 8 neighbours (n (1 - cos(radius / R)) / 2 = 8), and a regional leg of --regional points uniform in a 10 x 10 degree box at
+(30 W - 20 W, 40 N - 50 N) with the same mean.  Its yardstick is the flat table at the same n and mean neighbour count (run both
+on one machine); the NumPy and scipy legs belong to the flat run only.
 """
 
 from __future__ import annotations
@@ -33,6 +39,7 @@ if ROOT not in sys.path:
 
 import parcels_amd as pa  # noqa: E402
 from parcels_amd import interaction  # noqa: E402
+from parcels_amd.xgrid import EARTH_RADIUS  # noqa: E402
 
 MEAN_NEIGHBOURS = 8.0
 
@@ -42,12 +49,26 @@ def points(n, seed=1):
     return rng.random(n), rng.random(n), float(np.sqrt(MEAN_NEIGHBOURS / (np.pi * n)))
 
 
+def sphere_points(n, seed=1):
+    rng = np.random.default_rng(seed)
+    x, y = rng.uniform(-180.0, 180.0, n), np.degrees(np.arcsin(rng.uniform(-1.0, 1.0, n)))
+    return x, y, float(EARTH_RADIUS * np.arccos(1.0 - 2.0 * MEAN_NEIGHBOURS / n))
+
+
+def regional_points(n, seed=3):
+    rng = np.random.default_rng(seed)
+    s0, s1 = np.sin(np.radians(40.0)), np.sin(np.radians(50.0))
+    x, y = rng.uniform(-30.0, -20.0, n), np.degrees(np.arcsin(rng.uniform(s0, s1, n)))  # uniform in area
+    area = EARTH_RADIUS**2 * np.radians(10.0) * (s1 - s0)
+    return x, y, float(np.sqrt(MEAN_NEIGHBOURS * area / (np.pi * n)))
+
+
 def stats(ms):
     return {"median_ms": round(statistics.median(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3)}
 
 
-def device_leg(n, repeats):
-    x, y, radius = points(n)
+def device_leg(n, repeats, make_points=points, spherical=False, name="device"):
+    x, y, radius = make_points(n)
     ctx = interaction._context()
     lib, h = ctx.lib, ctx.handle
     p = interaction._ptr
@@ -58,7 +79,10 @@ def device_leg(n, repeats):
     out = None
     for rep in range(repeats + 1):  # the first round is cold (code objects, first allocations)
         t0 = time.perf_counter()
-        ctx.check(lib.pk_neighbors_build(h, n, p(x), p(y), None, None, radius, 0), "pk_neighbors_build")
+        if spherical:
+            ctx.check(lib.pk_neighbors_build_spherical(h, n, p(x), p(y), None, None, radius, EARTH_RADIUS, 0), "pk_neighbors_build_spherical")
+        else:
+            ctx.check(lib.pk_neighbors_build(h, n, p(x), p(y), None, None, radius, 0), "pk_neighbors_build")
         t1 = time.perf_counter()
         ctx.check(lib.pk_neighbors_counts(h, p(count), C.byref(total)), "pk_neighbors_counts")
         t2 = time.perf_counter()
@@ -70,15 +94,20 @@ def device_leg(n, repeats):
         t4 = time.perf_counter()
         ctx.check(lib.pk_neighbors_pairs(h, total.value, p(out[0]), p(out[1]), p(out[2]), p(out[3]), None, p(out[4])), "pk_neighbors_pairs")
         t5 = time.perf_counter()
-        nb = pa.neighbors((x, y), radius)
+        nb = pa.neighbors((x, y), radius, mesh="spherical" if spherical else "flat")
         t6 = time.perf_counter()
         assert nb.total == total.value and np.array_equal(nb.j, out[1])
         del nb
         for k, v in zip(t, (t1 - t0, t2 - t1, t3 - t2, t5 - t4, t6 - t5)):
             t[k].append(v * 1e3)
-    info = interaction.cell_list_info()
-    leg = {"leg": "device", "n": n, "radius": radius, "pairs": int(total.value), "mean_neighbours": total.value / n,
-           "cells": [info["ncx"], info["ncy"]], "doublings": info["doublings"], "repeats": repeats}
+    if spherical:
+        info = interaction.cell_list_info_spherical()
+        grid = {"bands": info["bands"], "cells": info["cells"], "band_height_deg": info["band_height"], "periodic": info["periodic"]}
+    else:
+        info = interaction.cell_list_info()
+        grid = {"cells": [info["ncx"], info["ncy"]]}
+    leg = {"leg": name, "n": n, "radius": radius, "pairs": int(total.value), "mean_neighbours": total.value / n, **grid,
+           "doublings": info["doublings"], "repeats": repeats}
     for k, v in t.items():
         leg[k] = dict(stats(v[1:]), cold_ms=round(v[0], 3))
     return leg
@@ -128,8 +157,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--brute", default="2e4")
     ap.add_argument("--scipy-particles", default="1e6")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "interaction_bench.json"))
+    ap.add_argument("--mesh", choices=["flat", "spherical"], default="flat")
+    ap.add_argument("--regional", default="1e6", help="points of the regional leg of --mesh spherical (0: none)")
+    ap.add_argument("--out", default=None, help="default: profiles/interaction_bench.json, interaction_sph_bench.json for --mesh spherical")
     a = ap.parse_args()
+    sph = a.mesh == "spherical"
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "interaction_sph_bench.json" if sph else "interaction_bench.json")
     sizes = [int(float(s)) for s in a.particles.split(",") if s]
     legs = []
     dev = interaction._context().device_info()
@@ -138,7 +172,9 @@ def main():
     def emit(leg):  # the file is complete after every leg
         legs.append(leg)
         print(json.dumps(leg), flush=True)
-        res = {"device": dev["name"], "arch": dev["arch"], "workload": "uniform points in the unit square, pi r^2 n = 8, float64, 2-D",
+        workload = ("points uniform on the sphere, n (1 - cos(radius / R)) / 2 = 8, great-circle distances in metres, float64, 2-D; regional: "
+                    "uniform in a 10 x 10 degree box, same mean") if sph else "uniform points in the unit square, pi r^2 n = 8, float64, 2-D"
+        res = {"device": dev["name"], "arch": dev["arch"], "workload": workload,
                "timing": "host clock around calls that end in a stream synchronise (PCIe transfers included); median of the timed calls, "
                          "min / max beside it",
                "device_bytes_per_pair": interaction.device_bytes_per_pair(False), "legs": legs}
@@ -147,12 +183,16 @@ def main():
             f.write("\n")
 
     for n in sizes:
-        emit(device_leg(n, a.repeats))
+        emit(device_leg(n, a.repeats, sphere_points, True) if sph else device_leg(n, a.repeats))
     if len(sizes) >= 2:
         big, small = legs[len(sizes) - 1], legs[len(sizes) - 2]
         emit({"leg": "scaling", "n": [small["n"], big["n"]],
               **{k: round(big[k]["median_ms"] / small[k]["median_ms"], 2) for k in ("build", "counts", "nearest", "pairs", "neighbors_call")}})
+    if sph and float(a.regional) > 0:
+        emit(device_leg(int(float(a.regional)), a.repeats, regional_points, True, name="device_regional"))
     interaction.release()
+    if sph:
+        return
     if a.brute and float(a.brute) > 0:
         emit(brute_leg(int(float(a.brute))))
     if a.scipy_particles and float(a.scipy_particles) > 0:
