@@ -1137,6 +1137,7 @@ class DeviceEngine:
             self.lib.pk_eval(self.ctx.handle, C.byref(prm), what, m, _ptr(t), _ptr(z), _ptr(y), _ptr(x), _ptr(u), _ptr(v), _ptr(w), _ptr(st)),
             "pk_eval",
         )
+        self.last_sample_masked = (st & _hip.PK_EVAL_MASKED) != 0  # the rows whose value was zeroed for an out-of-bounds index
         self.last_sample_state = self._finish_sample_state(st)
         return u, v, w
 
@@ -1160,6 +1161,7 @@ def _sample_streamed(self, name, t, z, y, x):
     ts = t[order]
     u, v, w = np.zeros(m), np.zeros(m), np.zeros(m)
     st = np.zeros(m, np.int32)
+    masked = np.zeros(m, bool)
     wf = self._windowed_fields()
     was = self.windowed
     i = 0
@@ -1182,10 +1184,12 @@ def _sample_streamed(self, name, t, z, y, x):
             self.windowed = was
             u[sel], v[sel], w[sel] = cu, cv, cw
             st[sel] = self.last_sample_state
+            masked[sel] = self.last_sample_masked
             i = j
     finally:
         self.windowed = was
     self.last_sample_state = st
+    self.last_sample_masked = masked
     return u, v, w
 
 
