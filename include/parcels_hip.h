@@ -564,6 +564,45 @@ typedef struct {
  * no counterpart: diagnostics and tests). */
 int32_t pk_neighbors_info_spherical(pk_ctx* ctx, pk_neighbors_info_spherical_t* out);
 
+/* ---- built-in interaction kernels on the device-resident particle columns (csrc/pk_interact.hip) -------------------------------------
+ * One iteration of the loop of Kernel.execute (kernel.py:190-230; parcels_amd/hostkernels.py restates it on the host columns), driven by
+ * the host with every column staying on the device: pk_interact_prologue, then pk_execute launches with body_only = 1 and the interaction
+ * kernels in list order, then pk_interact_epilogue.  All of them work on the bound rows in HOST row order and change the columns in place
+ * (a pk_execute_rerun or pk_particles_restore across them is refused).  Rows outside the mask of the iteration take no part in a search:
+ * they have no neighbours and are nobody's neighbour; indices are row numbers, which order the rows of the mask as the positions within
+ * the view of a Python kernel do. */
+/* Undo the cell sort of an earlier launch on the device (what pk_particles_d2h does on its way out, without leaving the device): body_only
+ * launches, pk_particles_set_mask and the calls below need host-ordered rows.  No-op on host-ordered rows. */
+int32_t pk_interact_host_order(pk_ctx* ctx);
+/* The tutorial's `attractor` column (tutorial_interaction.ipynb, the Pull kernel: `particles.attractor`): one byte per bound row, non-zero =
+ * source, copied from the host once per launch; pk_interact_attract reads the copy. */
+int32_t pk_interact_sources(pk_ctx* ctx, const uint8_t* sources);
+/* kernel.py:188 with reset_state = 1 (state[:] = Evaluate).  *n_evaluated = rows with state in {Success, Evaluate} and sign (endtime - t) >= 0
+ * (kernel.py:193-195), *n_active = rows in Evaluate or Repeat (the loop condition, kernel.py:190).  clip = 1: the iteration goes ahead -- the
+ * mask is written where body_only launches read it (what pk_particles_set_mask uploads) and dt is clipped for EVERY row (kernel.py:199-203);
+ * clip = 0 only counts (the reference leaves the loop before clipping when nothing is evaluated, kernel.py:196-197). */
+int32_t pk_interact_prologue(pk_ctx* ctx, double endtime, double dt0, int32_t reset_state, int32_t clip, int64_t* n_evaluated, int64_t* n_active);
+/* The tutorial's attraction kernel (the Pull kernel: distances to the attractors, `particles.dx += velocity * dx / distance * dt`) for the rows
+ * of the mask: cell list from the device columns x, y (z with use_z; float32 widened), sources = the flags of pk_interact_sources when
+ * use_sources, coincident points excluded; sphere_radius_m = 0: flat, else great-circle distances as pk_neighbors_build_spherical.  Count,
+ * scan, fill, row sort and finish as pk_neighbors_counts / _pairs; then per row s = 0.0, s += dx / dist over its pairs in ascending j, and
+ * the dx column becomes (storage dtype)(dx + (s * velocity) * dt); the same for dy, and dz with use_z.  *total = the pairs the count pass
+ * announced; when it exceeds max_pairs nothing is allocated and nothing is added (the caller raises).  phase_ms (may be NULL): host clock
+ * of build | count, fill, sort, finish | reduce, in milliseconds. */
+int32_t pk_interact_attract(pk_ctx* ctx, double radius, double velocity, double sphere_radius_m, int32_t use_z, int32_t use_sources, int64_t max_pairs,
+                            int64_t* total, double* phase_ms);
+/* The tutorial's merge kernel (the Merge kernel: `np.argmin(distances, axis=1)`, mutual nearest neighbours merge, the heavier keeps the mass)
+ * for the rows of the mask: nearest pass as pk_neighbors_nearest (coincident points excluded); row i goes on iff j = nn[i] > i and
+ * nn[j] == i; the heavier of the two (equal masses: i) receives the sum in the storage dtype of the device Variable extra[mass_extra], the
+ * other row's state becomes PK_DELETE.  phase_ms (may be NULL): build | nearest and merge. */
+int32_t pk_interact_merge(pk_ctx* ctx, double radius, double sphere_radius_m, int32_t use_z, int32_t mass_extra, double* phase_ms);
+/* kernel.py:219-230: for the rows of the mask in Evaluate or Success the position update in the storage dtype (kernel.py:108-120), t += dt,
+ * dx = dy = dz = 0; for every row dt = dt0 and Evaluate -> EndofLoop at t == endtime.  A step with t + dt == t before endtime becomes PK_ERROR
+ * (the guard of the fused kernels: the loop must not spin).  *steps = rows updated, state_counts[PK_NUM_STATE_CODES] = histogram of the states,
+ * *next_evaluated / *next_active = what pk_interact_prologue would count now. */
+int32_t pk_interact_epilogue(pk_ctx* ctx, double endtime, double dt0, int64_t* steps, int64_t* state_counts, int64_t* next_evaluated,
+                             int64_t* next_active);
+
 /* achieved copy bandwidth probe (device-to-device float4 copy), GB/s; used as a measured roofline denominator */
 int32_t pk_measure_copy_bandwidth(pk_ctx* ctx, int64_t bytes, int32_t iters, double* gbps);
 

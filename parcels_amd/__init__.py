@@ -37,10 +37,12 @@ from .kernels import (
     AdvectionRK4,
     AdvectionRK4_3D,
     AdvectionRK45,
+    AttractTowards,
     DeleteOutOfBounds,
     DeleteParticle,
     DiffusionUniformKh,
     DoNothing,
+    MergeNearest,
     MoveEast,
     MoveNorth,
     SampleField,

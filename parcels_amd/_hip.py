@@ -278,6 +278,12 @@ ABI_SYMBOLS = [
     "pk_neighbors_release",
     "pk_neighbors_build_spherical",
     "pk_neighbors_info_spherical",
+    "pk_interact_host_order",
+    "pk_interact_sources",
+    "pk_interact_prologue",
+    "pk_interact_attract",
+    "pk_interact_merge",
+    "pk_interact_epilogue",
     "pk_measure_copy_bandwidth",
     "pk_set_option",
     "pk_upload_stats",
@@ -391,6 +397,14 @@ def load():
     lib.pk_neighbors_build_spherical.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                                  C.c_int32]
     lib.pk_neighbors_info_spherical.argtypes = [C.c_void_p, C.POINTER(NeighborsSphInfo)]
+    lib.pk_interact_host_order.argtypes = [C.c_void_p]
+    lib.pk_interact_sources.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pk_interact_prologue.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.pk_interact_attract.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_double)]
+    lib.pk_interact_merge.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
+    lib.pk_interact_epilogue.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64)]
     if lib.pk_abi_version() != PK_ABI_VERSION:
         raise HipLibraryError(f"ABI version mismatch: library {lib.pk_abi_version()}, binding {PK_ABI_VERSION}")
     _lib = lib

@@ -19,6 +19,7 @@
 
 #include "pk_hashbuild.h"
 #include "pk_neighbors.h"
+#include "pk_interact.h"
 #include "pk_host_stage.h"
 #include "pk_kernels.h"
 #include "pk_ux.h"
@@ -195,6 +196,7 @@ struct pk_ctx {
     PkSelect sel;                   // write filter on the device rows (pk_select.inc): the filtered snapshot and the multi-GPU exchange use it
     struct PkComm* comm = nullptr;  // the multi-GPU exchange (pk_comm.inc: RCCL communicator + staging), NULL until pk_comm_init
     pk::Neighbors* nbr = nullptr;   // neighbour search (pk_neighbors.hip: cell list + scratch), NULL until pk_neighbors_build
+    pk::Interact* inter = nullptr;  // counters of the interaction loop (pk_interact.hip), NULL until pk_interact_prologue
 
     int32_t fail(const char* where, hipError_t e) {
         err = std::string(where) + ": " + hipGetErrorString(e);
@@ -805,6 +807,7 @@ int32_t pk_destroy(pk_ctx* ctx) {
     if (ctx->h_summary) (void)hipHostFree(ctx->h_summary);
     (void)pk_comm_destroy(ctx);
     neighbors_free(ctx->nbr);
+    interact_free(ctx->inter);
     if (ctx->sel.d_flag) (void)hipFree(ctx->sel.d_flag);
     if (ctx->sel.d_offs) (void)hipFree(ctx->sel.d_offs);
     if (ctx->sel.d_tmp) (void)hipFree(ctx->sel.d_tmp);
@@ -3127,6 +3130,111 @@ int32_t pk_neighbors_release(pk_ctx* ctx) {
     PK_HIP(ctx, hipSetDevice(ctx->device));
     PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
     neighbors_release(ctx->nbr);
+    return 0;
+}
+
+// ---- built-in interaction kernels on the device-resident columns (pk_interact.hip) ------------------------
+static int32_t interact_ready(pk_ctx* ctx, const char* who, bool host_order) {
+    if (!ctx->bound) return ctx->fail(std::string(who) + ": no particles bound");
+    if (ctx->in_flight) return ctx->fail(std::string(who) + ": a launch is in flight (call pk_execute_end)");
+    if (host_order && ctx->has_perm) return ctx->fail(std::string(who) + ": the device rows are cell-sorted (pk_interact_host_order first)");
+    PK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->nbr) ctx->nbr = neighbors_create();
+    if (!ctx->inter) ctx->inter = interact_create();
+    ctx->rerun_valid = false;  // the columns change in place
+    ctx->chk_valid = false;
+    return 0;
+}
+static InteractColumns interact_columns(const pk_ctx* ctx) {
+    const DParticles& d = ctx->dev;
+    InteractColumns c;
+    c.n = d.n;
+    c.f32 = d.spatial_f32;
+    c.t = d.t;
+    c.x = d.x; c.y = d.y; c.z = d.z;
+    c.dx = d.dx; c.dy = d.dy; c.dz = d.dz;
+    c.dt = d.dt;
+    c.state = d.state;
+    c.mask = d.iter;
+    return c;
+}
+
+int32_t pk_interact_host_order(pk_ctx* ctx) {
+    if (!ctx) return -2;
+    int32_t rc = interact_ready(ctx, "pk_interact_host_order", false);
+    if (rc) return rc;
+    const int64_t n = ctx->dev.n;
+    if (!ctx->has_perm) return 0;
+    if (n > 0) {
+        rc = ensure_alt(ctx);
+        if (rc) return rc;
+        for (const ColRef& c : particle_columns(ctx)) {  // host row perm[i] <- device row i, as pk_particles_d2h does on its way out
+            if (!c.d || !c.a) continue;
+            if (c.elem == 8) launch_scatter<unsigned long long>(ctx, c.d, c.a, ctx->d_perm, n, c.width);
+            else launch_scatter<uint32_t>(ctx, c.d, c.a, ctx->d_perm, n, c.width);
+        }
+        PK_HIP(ctx, hipGetLastError());
+        PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
+        swap_column_sets(ctx);
+    }
+    ctx->has_perm = false;
+    return 0;
+}
+
+int32_t pk_interact_sources(pk_ctx* ctx, const uint8_t* sources) {
+    if (!ctx) return -2;
+    int32_t rc = interact_ready(ctx, "pk_interact_sources", false);
+    if (rc) return rc;
+    std::string msg;
+    if (neighbors_set_sources(ctx->nbr, ctx->compute, ctx->dev.n, sources, &msg)) return ctx->fail(msg);
+    return 0;
+}
+
+int32_t pk_interact_prologue(pk_ctx* ctx, double endtime, double dt0, int32_t reset_state, int32_t clip, int64_t* n_evaluated, int64_t* n_active) {
+    if (!ctx || !n_evaluated || !n_active) return -2;
+    int32_t rc = interact_ready(ctx, "pk_interact_prologue", true);
+    if (rc) return rc;
+    std::string msg;
+    if (interact_prologue(ctx->inter, ctx->compute, interact_columns(ctx), endtime, dt0, reset_state, clip, n_evaluated, n_active, &msg))
+        return ctx->fail(msg);
+    return 0;
+}
+
+int32_t pk_interact_epilogue(pk_ctx* ctx, double endtime, double dt0, int64_t* steps, int64_t* state_counts, int64_t* next_evaluated,
+                             int64_t* next_active) {
+    if (!ctx || !steps || !state_counts || !next_evaluated || !next_active) return -2;
+    int32_t rc = interact_ready(ctx, "pk_interact_epilogue", true);
+    if (rc) return rc;
+    std::string msg;
+    if (interact_epilogue(ctx->inter, ctx->compute, interact_columns(ctx), endtime, dt0, steps, state_counts, next_evaluated, next_active, &msg))
+        return ctx->fail(msg);
+    return 0;
+}
+
+int32_t pk_interact_attract(pk_ctx* ctx, double radius, double velocity, double sphere_radius_m, int32_t use_z, int32_t use_sources, int64_t max_pairs,
+                            int64_t* total, double* phase_ms) {
+    if (!ctx || !total) return -2;
+    int32_t rc = interact_ready(ctx, "pk_interact_attract", true);
+    if (rc) return rc;
+    if (!(velocity == velocity) || std::isinf(velocity)) return ctx->fail("pk_interact_attract: velocity must be finite");
+    if (max_pairs < 0) return ctx->fail("pk_interact_attract: max_pairs must not be negative");
+    std::string msg;
+    if (interact_attract(ctx->nbr, ctx->compute, interact_columns(ctx), radius, velocity, sphere_radius_m, use_z, use_sources, max_pairs, total, phase_ms,
+                         &msg))
+        return ctx->fail(msg);
+    return 0;
+}
+
+int32_t pk_interact_merge(pk_ctx* ctx, double radius, double sphere_radius_m, int32_t use_z, int32_t mass_extra, double* phase_ms) {
+    if (!ctx) return -2;
+    int32_t rc = interact_ready(ctx, "pk_interact_merge", true);
+    if (rc) return rc;
+    if (mass_extra < 0 || mass_extra >= PK_MAX_EXTRA || !ctx->dev.extra[mass_extra])
+        return ctx->fail("pk_interact_merge: mass_extra must name a device Variable of the bound particles (pk_particles_desc.extra)");
+    std::string msg;
+    if (interact_merge(ctx->nbr, ctx->compute, interact_columns(ctx), ctx->dev.extra[mass_extra], ctx->dev.extra_f32[mass_extra], radius, sphere_radius_m,
+                       use_z, phase_ms, &msg))
+        return ctx->fail(msg);
     return 0;
 }
 

@@ -67,4 +67,35 @@ int neighbors_pairs(Neighbors* nb, hipStream_t stream, int64_t total, int64_t* s
 void neighbors_info(const Neighbors* nb, NeighborsInfo* out);                    // zeros after a spherical build
 void neighbors_info_spherical(const Neighbors* nb, NeighborsSphInfo* out);      // zeros after a flat build
 
+// ---- device-resident input and output (pk_interact.hip: built-in interaction kernels on the particle columns) ----------------
+// The points are DEVICE columns of n rows, float32 (widened, which is exact) or float64; nothing crosses PCIe but the bounding
+// box partials the build finishes on the host.  mask (may be NULL): row i takes part iff mask[i] != 0 -- a row that does not is
+// given a NaN x, so it is a point with a non-finite coordinate: it has no neighbours and is nobody's neighbour, and every index
+// stays a row number.  (Row numbers order the rows that take part as their positions among themselves do, so row order, ties
+// and sums are those of a search over the selected rows alone.)  use_sources: the flags of neighbors_set_sources.
+struct NeighborsDeviceInput {
+    const void *x = nullptr, *y = nullptr, *z = nullptr;  // z: NULL for a 2-D search
+    int32_t f32 = 0;                                      // 1: the columns are float32
+    const int32_t* mask = nullptr;
+    int32_t use_sources = 0;
+};
+// One byte per row (non-zero = source), copied from the HOST array into a device buffer the cell list keeps until the next call,
+// neighbors_release or neighbors_free.
+int neighbors_set_sources(Neighbors* nb, hipStream_t stream, int64_t n, const uint8_t* sources, std::string* err);
+// sphere_radius == 0: flat, else the spherical build
+int neighbors_build_device(Neighbors* nb, hipStream_t stream, int64_t n, const NeighborsDeviceInput& in, double radius, double sphere_radius,
+                           int32_t flags, std::string* err);
+// The nearest pass and the pair passes (fill, row sort, finish) of neighbors_nearest / neighbors_pairs without the copies to the
+// host: the results stay in the scratch that neighbors_device_view describes.
+int neighbors_nearest_device(Neighbors* nb, hipStream_t stream, std::string* err);
+int neighbors_pairs_device(Neighbors* nb, hipStream_t stream, int64_t total, std::string* err);
+struct NeighborsDeviceView {
+    int64_t n = 0, total = 0;
+    const int64_t* starts = nullptr;  // n + 1 CSR row starts (after neighbors_counts)
+    const double *dx = nullptr, *dy = nullptr, *dz = nullptr, *dist = nullptr;  // per pair, rows ordered by j (after neighbors_pairs_device)
+    const int64_t* near_j = nullptr;  // per row (after neighbors_nearest_device)
+    int32_t* flag = nullptr;          // the library-error flag of the fill pass, for a pass that walks the rows
+};
+void neighbors_device_view(const Neighbors* nb, NeighborsDeviceView* out);
+
 }  // namespace pk

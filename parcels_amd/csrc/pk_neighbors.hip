@@ -471,6 +471,21 @@ __global__ void __launch_bounds__(NB_BLOCK) nb_sph_finish_kernel(const double* _
     out_dist[p] = d;
 }
 
+// device-resident input (NeighborsDeviceInput): the columns widened into the build's own float64 arrays; a row outside the mask gets a
+// NaN x, which every later pass treats as a non-finite point
+template <class T>
+__global__ void __launch_bounds__(NB_BLOCK) nb_load_kernel(const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ z,
+                                                           const int32_t* __restrict__ mask, const uint8_t* __restrict__ src_in, int64_t n,
+                                                           double* __restrict__ ox, double* __restrict__ oy, double* __restrict__ oz,
+                                                           uint8_t* __restrict__ osrc) {
+    const int64_t i = (int64_t)blockIdx.x * NB_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    ox[i] = (!mask || mask[i] != 0) ? (double)x[i] : (double)NAN;
+    oy[i] = (double)y[i];
+    if (z) oz[i] = (double)z[i];
+    if (src_in) osrc[i] = src_in[i];
+}
+
 struct Buf {  // grow-only device buffer
     void* p = nullptr;
     size_t cap = 0;
@@ -520,6 +535,9 @@ struct Neighbors {
     Buf cell_begin, cell_end, partial, tmp, flag;
     // spherical builds: per band, per point
     Buf band, cs;
+    // one byte per row, kept between builds (neighbors_set_sources)
+    Buf src_in;
+    int64_t src_in_n = -1;
     // per pair
     Buf pair_i, pair_j, pair_js, out_j, out_dx, out_dy, out_dz, out_dist;
     bool built = false, has_z = false, has_src = false, spherical = false;
@@ -529,9 +547,9 @@ struct Neighbors {
     NbGrid g{};   // flat builds
     NbSph sg{};   // spherical builds
 
-    Buf* all[31] = {&x, &y, &z, &src, &key, &key_s, &idx, &idx_s, &xs, &ys, &zs, &srcs, &count, &starts, &near_j, &near_d,
+    Buf* all[32] = {&x, &y, &z, &src, &key, &key_s, &idx, &idx_s, &xs, &ys, &zs, &srcs, &count, &starts, &near_j, &near_d,
                     &cell_begin, &cell_end, &partial, &tmp, &flag, &band, &cs, &pair_i, &pair_j, &pair_js, &out_j, &out_dx, &out_dy, &out_dz,
-                    &out_dist};
+                    &out_dist, &src_in};
 
     NbQuery query() const {
         NbQuery q{};
@@ -557,6 +575,7 @@ Neighbors* neighbors_create() { return new Neighbors(); }
 void neighbors_release(Neighbors* nb) {
     if (!nb) return;
     for (Buf* b : nb->all) b->drop();
+    nb->src_in_n = -1;
     nb->built = false;
     nb->n = 0;
     nb->total = -1;
@@ -583,8 +602,9 @@ void neighbors_info(const Neighbors* nb, NeighborsInfo* out) {
 namespace {
 // What both builds begin with: argument checks, the per-point buffers and the upload.  Returns 1 for n == 0 (an empty list is
 // built, nothing else to do), 0 to go on, a negative code with *err set.
+// din: the points are device columns (NeighborsDeviceInput) instead of the host arrays x, y, z, sources.
 int build_begin(Neighbors* nb, hipStream_t stream, int64_t n, const double* x, const double* y, const double* z, const uint8_t* sources,
-                double radius, int32_t flags, bool spherical, std::string* err) {
+                const NeighborsDeviceInput* din, double radius, int32_t flags, bool spherical, std::string* err) {
     nb->built = false;
     nb->total = -1;
     if (n < 0 || n > NB_MAX_POINTS) {
@@ -595,15 +615,21 @@ int build_begin(Neighbors* nb, hipStream_t stream, int64_t n, const double* x, c
         if (err) *err = "neighbors: radius must be a finite positive number";
         return -2;
     }
-    if (n > 0 && (!x || !y)) {
+    if (n > 0 && (din ? (!din->x || !din->y) : (!x || !y))) {
         if (err) *err = "neighbors: x and y must not be NULL";
         return -2;
     }
+    if (din && din->use_sources && nb->src_in_n != n) {
+        if (err) *err = "neighbors: the source flags were set for another number of rows (neighbors_set_sources)";
+        return -2;
+    }
+    const bool has_z = din ? din->z != nullptr : z != nullptr;
+    const bool has_src = din ? din->use_sources != 0 : sources != nullptr;
     nb->n = n;
     nb->radius = radius;
     nb->flags = flags;
-    nb->has_z = z != nullptr;
-    nb->has_src = sources != nullptr;
+    nb->has_z = has_z;
+    nb->has_src = has_src;
     nb->spherical = spherical;
     nb->nvalid = 0;
     nb->doublings = 0;
@@ -619,18 +645,30 @@ int build_begin(Neighbors* nb, hipStream_t stream, int64_t n, const double* x, c
     NB_TRY(nb->y.need(nd));
     NB_TRY(nb->xs.need(nd));
     NB_TRY(nb->ys.need(nd));
-    if (z) {
+    if (has_z) {
         NB_TRY(nb->z.need(nd));
         NB_TRY(nb->zs.need(nd));
     }
     if (spherical) NB_TRY(nb->cs.need(nd));
-    if (sources) NB_TRY(nb->src.need((size_t)n));
+    if (has_src) NB_TRY(nb->src.need((size_t)n));
     NB_TRY(nb->srcs.need((size_t)n));
     NB_TRY(nb->key.need(nu));
     NB_TRY(nb->key_s.need(nu));
     NB_TRY(nb->idx.need(nu));
     NB_TRY(nb->idx_s.need(nu));
     NB_TRY(nb->partial.need((size_t)NB_BBOX_BLOCKS * 8 * sizeof(double)));
+    if (din) {
+        double* oz = has_z ? nb->z.as<double>() : nullptr;
+        const uint8_t* si = has_src ? nb->src_in.as<uint8_t>() : nullptr;
+        if (din->f32)
+            hipLaunchKernelGGL((nb_load_kernel<float>), dim3(blocks_for(n)), dim3(NB_BLOCK), 0, stream, (const float*)din->x, (const float*)din->y,
+                               (const float*)din->z, din->mask, si, n, nb->x.as<double>(), nb->y.as<double>(), oz, nb->src.as<uint8_t>());
+        else
+            hipLaunchKernelGGL((nb_load_kernel<double>), dim3(blocks_for(n)), dim3(NB_BLOCK), 0, stream, (const double*)din->x, (const double*)din->y,
+                               (const double*)din->z, din->mask, si, n, nb->x.as<double>(), nb->y.as<double>(), oz, nb->src.as<uint8_t>());
+        NB_TRY(hipGetLastError());
+        return 0;
+    }
     NB_TRY(hipMemcpyAsync(nb->x.p, x, nd, hipMemcpyHostToDevice, stream));
     NB_TRY(hipMemcpyAsync(nb->y.p, y, nd, hipMemcpyHostToDevice, stream));
     if (z) NB_TRY(hipMemcpyAsync(nb->z.p, z, nd, hipMemcpyHostToDevice, stream));
@@ -667,10 +705,11 @@ int build_sort_gather(Neighbors* nb, hipStream_t stream, uint32_t ncells, std::s
 }
 }  // namespace
 
-int neighbors_build(Neighbors* nb, hipStream_t stream, int64_t n, const double* x, const double* y, const double* z, const uint8_t* sources,
-                    double radius, int32_t flags, std::string* err) {
-    if (int rc = build_begin(nb, stream, n, x, y, z, sources, radius, flags, false, err)) return rc < 0 ? rc : 0;
-    const double* dz = z ? nb->z.as<double>() : nullptr;
+namespace {
+int build_flat(Neighbors* nb, hipStream_t stream, int64_t n, const double* x, const double* y, const double* z, const uint8_t* sources,
+               const NeighborsDeviceInput* din, double radius, int32_t flags, std::string* err) {
+    if (int rc = build_begin(nb, stream, n, x, y, z, sources, din, radius, flags, false, err)) return rc < 0 ? rc : 0;
+    const double* dz = nb->has_z ? nb->z.as<double>() : nullptr;
 
     // 1. bounding box of the finite points
     const unsigned nbb = std::min<unsigned>(blocks_for(n), NB_BBOX_BLOCKS);
@@ -730,6 +769,12 @@ int neighbors_build(Neighbors* nb, hipStream_t stream, int64_t n, const double* 
     nb->built = true;
     return 0;
 }
+}  // namespace
+
+int neighbors_build(Neighbors* nb, hipStream_t stream, int64_t n, const double* x, const double* y, const double* z, const uint8_t* sources,
+                    double radius, int32_t flags, std::string* err) {
+    return build_flat(nb, stream, n, x, y, z, sources, nullptr, radius, flags, err);
+}
 
 namespace {
 // The band table of one band height (NB_SPH_MARGIN, step 2).  Returns the total number of cells, or -1 as soon as it passes cap.
@@ -751,17 +796,16 @@ int64_t sph_bands(std::vector<NbBand>& table, int64_t nbands, double ymin, doubl
     }
     return cells;
 }
-}  // namespace
 
-int neighbors_build_spherical(Neighbors* nb, hipStream_t stream, int64_t n, const double* x, const double* y, const double* z,
-                              const uint8_t* sources, double radius, double sphere_radius, int32_t flags, std::string* err) {
+int build_spherical(Neighbors* nb, hipStream_t stream, int64_t n, const double* x, const double* y, const double* z, const uint8_t* sources,
+                    const NeighborsDeviceInput* din, double radius, double sphere_radius, int32_t flags, std::string* err) {
     if (!(sphere_radius > 0.0) || !(sphere_radius <= DBL_MAX) || !(radius < M_PI_2 * sphere_radius)) {
         nb->built = false;
         if (err) *err = "neighbors: the sphere radius must be finite and positive, and radius below a quarter of its circumference";
         return -2;
     }
-    if (int rc = build_begin(nb, stream, n, x, y, z, sources, radius, flags, true, err)) return rc < 0 ? rc : 0;
-    const double* dz = z ? nb->z.as<double>() : nullptr;
+    if (int rc = build_begin(nb, stream, n, x, y, z, sources, din, radius, flags, true, err)) return rc < 0 ? rc : 0;
+    const double* dz = nb->has_z ? nb->z.as<double>() : nullptr;
 
     // 1. extent of the valid points: latitude, longitude in both normalisations, max |x|
     const unsigned nbb = std::min<unsigned>(blocks_for(n), NB_BBOX_BLOCKS);
@@ -838,6 +882,47 @@ int neighbors_build_spherical(Neighbors* nb, hipStream_t stream, int64_t n, cons
     nb->built = true;
     return 0;
 }
+}  // namespace
+
+int neighbors_build_spherical(Neighbors* nb, hipStream_t stream, int64_t n, const double* x, const double* y, const double* z,
+                              const uint8_t* sources, double radius, double sphere_radius, int32_t flags, std::string* err) {
+    return build_spherical(nb, stream, n, x, y, z, sources, nullptr, radius, sphere_radius, flags, err);
+}
+
+int neighbors_set_sources(Neighbors* nb, hipStream_t stream, int64_t n, const uint8_t* sources, std::string* err) {
+    nb->src_in_n = -1;
+    if (n < 0 || n > NB_MAX_POINTS || (n > 0 && !sources)) {
+        if (err) *err = "neighbors: source flags need one byte per row";
+        return -2;
+    }
+    if (n > 0) {
+        NB_TRY(nb->src_in.need((size_t)n));
+        NB_TRY(hipMemcpyAsync(nb->src_in.p, sources, (size_t)n, hipMemcpyHostToDevice, stream));
+        NB_TRY(hipStreamSynchronize(stream));  // the host array is the caller's
+    }
+    nb->src_in_n = n;
+    return 0;
+}
+
+int neighbors_build_device(Neighbors* nb, hipStream_t stream, int64_t n, const NeighborsDeviceInput& in, double radius, double sphere_radius,
+                           int32_t flags, std::string* err) {
+    if (sphere_radius != 0.0) return build_spherical(nb, stream, n, nullptr, nullptr, nullptr, nullptr, &in, radius, sphere_radius, flags, err);
+    return build_flat(nb, stream, n, nullptr, nullptr, nullptr, nullptr, &in, radius, flags, err);
+}
+
+void neighbors_device_view(const Neighbors* nb, NeighborsDeviceView* out) {
+    *out = NeighborsDeviceView();
+    if (!nb || !nb->built) return;
+    out->n = nb->n;
+    out->total = nb->total < 0 ? 0 : nb->total;
+    out->starts = nb->starts.as<int64_t>();
+    out->dx = nb->out_dx.as<double>();
+    out->dy = nb->out_dy.as<double>();
+    out->dz = nb->has_z ? nb->out_dz.as<double>() : nullptr;
+    out->dist = nb->out_dist.as<double>();
+    out->near_j = nb->near_j.as<int64_t>();
+    out->flag = nb->flag.as<int32_t>();
+}
 
 void neighbors_info_spherical(const Neighbors* nb, NeighborsSphInfo* out) {
     *out = NeighborsSphInfo();
@@ -906,6 +991,20 @@ int neighbors_counts(Neighbors* nb, hipStream_t stream, int64_t* counts, int64_t
     return 0;
 }
 
+int neighbors_nearest_device(Neighbors* nb, hipStream_t stream, std::string* err) {
+    if (int rc = need_built(nb, err)) return rc;
+    const int64_t n = nb->n;
+    if (n == 0) return 0;
+    NB_TRY(nb->near_j.need((size_t)n * sizeof(int64_t)));
+    NB_TRY(nb->near_d.need((size_t)n * sizeof(double)));
+    NbQuery q = nb->query();
+    q.near_j = nb->near_j.as<int64_t>();
+    q.near_d = nb->near_d.as<double>();
+    launch_query<NB_NEAREST>(nb, stream, q);
+    NB_TRY(hipGetLastError());
+    return 0;
+}
+
 int neighbors_nearest(Neighbors* nb, hipStream_t stream, int64_t* j, double* dist, std::string* err) {
     if (int rc = need_built(nb, err)) return rc;
     const int64_t n = nb->n;
@@ -914,12 +1013,7 @@ int neighbors_nearest(Neighbors* nb, hipStream_t stream, int64_t* j, double* dis
         if (err) *err = "neighbors: nearest needs both output arrays";
         return -2;
     }
-    NB_TRY(nb->near_j.need((size_t)n * sizeof(int64_t)));
-    NB_TRY(nb->near_d.need((size_t)n * sizeof(double)));
-    NbQuery q = nb->query();
-    q.near_j = nb->near_j.as<int64_t>();
-    q.near_d = nb->near_d.as<double>();
-    launch_query<NB_NEAREST>(nb, stream, q);
+    if (int rc = neighbors_nearest_device(nb, stream, err)) return rc;
     NB_TRY(hipMemcpyAsync(j, nb->near_j.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
     NB_TRY(hipMemcpyAsync(dist, nb->near_d.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
     NB_TRY(hipGetLastError());
@@ -927,8 +1021,8 @@ int neighbors_nearest(Neighbors* nb, hipStream_t stream, int64_t* j, double* dis
     return 0;
 }
 
-int neighbors_pairs(Neighbors* nb, hipStream_t stream, int64_t total, int64_t* starts, int64_t* j, double* dx, double* dy, double* dz,
-                    double* dist, std::string* err) {
+namespace {
+int pairs_check(const Neighbors* nb, int64_t total, std::string* err) {
     if (int rc = need_built(nb, err)) return rc;
     if (nb->total < 0) {
         if (err) *err = "neighbors: pairs need the count pass first";
@@ -942,6 +1036,13 @@ int neighbors_pairs(Neighbors* nb, hipStream_t stream, int64_t total, int64_t* s
         if (err) *err = "neighbors: " + std::to_string(total) + " pairs exceed the 2147483647 one call can list";
         return -2;
     }
+    return 0;
+}
+}  // namespace
+
+int neighbors_pairs(Neighbors* nb, hipStream_t stream, int64_t total, int64_t* starts, int64_t* j, double* dx, double* dy, double* dz,
+                    double* dist, std::string* err) {
+    if (int rc = pairs_check(nb, total, err)) return rc;
     const int64_t n = nb->n;
     if (!starts || (total > 0 && (!j || !dx || !dy || !dist || (nb->has_z && !dz)))) {
         if (err) *err = "neighbors: pairs need every output array";
@@ -956,6 +1057,21 @@ int neighbors_pairs(Neighbors* nb, hipStream_t stream, int64_t total, int64_t* s
         NB_TRY(hipStreamSynchronize(stream));
         return 0;
     }
+    if (int rc = neighbors_pairs_device(nb, stream, total, err)) return rc;
+    const size_t pd = (size_t)total * sizeof(double);
+    NB_TRY(hipMemcpyAsync(j, nb->out_j.p, pd, hipMemcpyDeviceToHost, stream));
+    NB_TRY(hipMemcpyAsync(dx, nb->out_dx.p, pd, hipMemcpyDeviceToHost, stream));
+    NB_TRY(hipMemcpyAsync(dy, nb->out_dy.p, pd, hipMemcpyDeviceToHost, stream));
+    if (nb->has_z) NB_TRY(hipMemcpyAsync(dz, nb->out_dz.p, pd, hipMemcpyDeviceToHost, stream));
+    NB_TRY(hipMemcpyAsync(dist, nb->out_dist.p, pd, hipMemcpyDeviceToHost, stream));
+    NB_TRY(hipStreamSynchronize(stream));
+    return 0;
+}
+
+int neighbors_pairs_device(Neighbors* nb, hipStream_t stream, int64_t total, std::string* err) {
+    if (int rc = pairs_check(nb, total, err)) return rc;
+    const int64_t n = nb->n;
+    if (n == 0 || total == 0) return 0;
     const size_t pu = (size_t)total * sizeof(uint32_t), pd = (size_t)total * sizeof(double);
     NB_TRY(nb->pair_i.need(pu));
     NB_TRY(nb->pair_j.need(pu));
@@ -1006,12 +1122,6 @@ int neighbors_pairs(Neighbors* nb, hipStream_t stream, int64_t total, int64_t* s
         if (err) *err = "neighbors: the fill pass disagreed with the count pass (no pair was written out of its row)";
         return -3;
     }
-    NB_TRY(hipMemcpyAsync(j, nb->out_j.p, pd, hipMemcpyDeviceToHost, stream));
-    NB_TRY(hipMemcpyAsync(dx, nb->out_dx.p, pd, hipMemcpyDeviceToHost, stream));
-    NB_TRY(hipMemcpyAsync(dy, nb->out_dy.p, pd, hipMemcpyDeviceToHost, stream));
-    if (nb->has_z) NB_TRY(hipMemcpyAsync(dz, nb->out_dz.p, pd, hipMemcpyDeviceToHost, stream));
-    NB_TRY(hipMemcpyAsync(dist, nb->out_dist.p, pd, hipMemcpyDeviceToHost, stream));
-    NB_TRY(hipStreamSynchronize(stream));
     return 0;
 }
 

@@ -105,7 +105,8 @@ class Kernel:
             raise ValueError("List of `kernels` should have at least one function.")
         # Python functions that are not built-in device kernels: the loop of Kernel.execute then runs on the host columns and only
         # the built-in kernels' bodies on the GPU (parcels_amd/hostkernels.py) -- correct, and slow by construction
-        self.host_functions = [f.__name__ for f in kernels if _k.kernel_id(f) is None]
+        # (AttractTowards / MergeNearest tokens have a Python body AND a device form: which one runs is decided below)
+        self.host_functions = [f.__name__ for f in kernels if _k.kernel_id(f) is None and _k.interaction_spec(f) is None]
         self.user_program = None   # parcels_amd.jit.UserProgram once the Python functions of the list were compiled for the device
         self.jit_report = None     # why they were not (the host path runs them then)
         self._jit_tried = False
@@ -157,7 +158,52 @@ class Kernel:
                 warnings.warn("Sampling of velocities should normally be done using fieldset.UV or fieldset.UVW object; tread carefully",
                               RuntimeWarning, stacklevel=3)
             self.samples[slot] = (fname, sum(c << (8 * j) for j, c in enumerate(cols)) if vector else cols[0])
+        # AttractTowards / MergeNearest tokens: the Variables they name, their radius against the mesh; `mass` becomes a device Variable
+        self.interactions = {}
+        for slot, f in enumerate(kernels):
+            spec = _k.interaction_spec(f)
+            if spec is None:
+                continue
+            who = f.__name__
+            vn = spec["mass"] if spec["kind"] == "merge" else spec["sources"]
+            if vn not in names or vn in _RESERVED_COLUMNS:
+                raise ValueError(f"{who}: the ParticleClass has no user Variable '{vn}' (Particle.add_variable)")
+            vdt = np.dtype(names[vn].dtype)
+            from .interaction import _sphere_radius
+
+            if not (np.isfinite(spec["radius"]) and spec["radius"] > 0):
+                raise ValueError(f"{who}: radius must be a finite positive number, got {spec['radius']!r}")
+            try:
+                sphere = _sphere_radius(spec["mesh"], spec["radius"])
+            except ValueError as e:
+                raise ValueError(f"{who}: {e}") from None
+            if spec["kind"] == "merge":
+                if vdt not in (np.dtype(np.float32), np.dtype(np.float64)):
+                    raise TypeError(f"{who}: Variable '{vn}' must be float32 or float64, it is {vdt}")
+                if vn not in self.device_variables:
+                    self.device_variables.append(vn)
+            else:
+                if vdt.kind not in "biuf":
+                    raise TypeError(f"{who}: Variable '{vn}' must have a bool or numeric dtype, it is {vdt}")
+                if not np.isfinite(spec["velocity"]):
+                    raise ValueError(f"{who}: velocity must be a finite number, got {spec['velocity']!r}")
+            self.interactions[slot] = dict(spec, sphere=sphere)
+        for slot, spec in self.interactions.items():  # (after the loop: a later MergeNearest or SampleField may claim the Variable)
+            if spec["kind"] == "attract" and spec["sources"] in self.device_variables:
+                raise ValueError(f"{kernels[slot].__name__}: Variable '{spec['sources']}' is written by a device kernel of the list; the sources "
+                                 "flags stay on the host and are uploaded once per launch, so no device kernel may write them")
         from . import _hip as _h
+        from .interactkernels import interaction_route
+
+        shard = getattr(pset, "_shard", None)
+        # "device": the loop of Kernel.execute runs on the device-resident columns (interactkernels.launch_device); "host": the tokens'
+        # Python bodies run in the host loop like any user kernel (and nothing of the list is handed to the translator); None: no token
+        self.interaction_route = interaction_route(kernels, rk45_mode="RK45_tol" in self._fieldset.context, on_uxgrid=_on_uxgrid(self._fieldset),
+                                                   multi_process=bool(shard and shard[1] > 1))
+        if self.interaction_route == "host":
+            self.host_functions = [f.__name__ for f in kernels if _k.kernel_id(f) is None]
+            self._jit_tried = True
+            self.jit_report = "a kernel list with interaction kernels is not translated: it runs in the host loop"
 
         if len(self.device_variables) > _h.PK_MAX_EXTRA:
             raise ValueError(f"at most {_h.PK_MAX_EXTRA} particle Variables can be written by device kernels")
@@ -283,6 +329,12 @@ class Kernel:
         No host<->device copies; returns the engine statistics (steps, state histogram, kernel time)."""
         if self.host_functions:
             return self._launch_hosted(pset, endtime, dt)
+        if self.interaction_route == "device":
+            from .interactkernels import launch_device
+
+            stats = launch_device(self, pset, endtime, dt, have_guess0=have_guess0)
+            pset._last_stats = stats
+            return stats
         engine = pset._engine()
         engine.set_user_program(self.user_program)
         data = pset._data

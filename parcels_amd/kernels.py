@@ -3,7 +3,8 @@
 These functions are *tokens*: ``Kernel`` recognises them by identity (the reference does the same for
 AdvectionRK45, kernel.py:129-134) and maps each to the PK_KERNEL_* id of the HIP implementation in
 csrc/pk_kernels.h.  Their bodies never run; calling one directly is an error, because this package has no
-NumPy execution path.
+NumPy execution path.  The interaction kernels AttractTowards / MergeNearest are the exception: their tokens have a real Python body on
+the device neighbour search, which the host loop runs when the list does not take the device route (parcels_amd/interactkernels.py).
 """
 
 from __future__ import annotations
@@ -18,10 +19,12 @@ __all__ = [
     "AdvectionRK4",
     "AdvectionRK4_3D",
     "AdvectionRK45",
+    "AttractTowards",
     "DeleteOutOfBounds",
     "DeleteParticle",
     "DiffusionUniformKh",
     "DoNothing",
+    "MergeNearest",
     "MoveEast",
     "MoveNorth",
     "SampleField",
@@ -204,6 +207,132 @@ def convert_z_to_sigma_croco(fieldset, t, z, y, x, particle=None):
         zi = np.where(zinds.all(axis=1), zvec.shape[1] - 2, zi)
         idx = np.arange(zi.shape[0])
         return sigma_levels[zi] + (z - zvec[idx, zi]) * (sigma_levels[zi + 1] - sigma_levels[zi]) / (zvec[idx, zi + 1] - zvec[idx, zi])
+
+
+# ---- particle-particle interaction (docs/user_guide/examples/tutorial_interaction.ipynb; csrc/pk_interact.hip) -------------------------
+def _check_number(who, name, value, positive):
+    import math
+    import numbers
+
+    import numpy as np
+
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (numbers.Real, np.floating, np.integer)):
+        raise TypeError(f"{who}: {name} must be a {'finite positive' if positive else 'finite'} number, got {type(value).__name__}")
+    value = float(value)
+    if not math.isfinite(value) or (positive and not value > 0.0):
+        raise ValueError(f"{who}: {name} must be a {'finite positive' if positive else 'finite'} number, got {value!r}")
+    return value
+
+
+def _check_interaction_options(who, z, mesh):
+    from .fieldset import FieldSet
+    from .xgrid import FlatMesh, SphericalMesh
+
+    if not isinstance(z, bool):
+        raise TypeError(f"{who}: z must be True or False, got {type(z).__name__}")
+    if not isinstance(mesh, (FieldSet, FlatMesh, SphericalMesh)) and not (isinstance(mesh, str) and mesh in ("flat", "spherical")):
+        raise ValueError(f"{who}: mesh must be 'flat', 'spherical', a SphericalMesh or a FieldSet. Got {mesh=!r}")
+
+
+def AttractTowards(sources: str, radius, velocity, *, z=False, mesh="flat", max_pairs=None):
+    """The attraction kernel of the interaction tutorial as a built-in kernel: every particle moves with speed ``velocity`` towards each
+    source particle closer than ``radius``.  ``sources`` names a particle Variable of any bool or numeric dtype (non-zero = source; it
+    stays on the host and no device kernel of the list may write it).  Returns a kernel token named ``AttractTowards_<sources>`` whose
+    body is the definition::
+
+        nb = pa.neighbors(particles, radius, z=z, mesh=mesh, max_pairs=max_pairs,
+                          sources=np.asarray(particles.<sources>) != 0, include_coincident=False)
+        particles.dx += nb.sum(nb.dx / nb.dist) * velocity * particles.dt        # (S * velocity) * dt, left to right
+        particles.dy += nb.sum(nb.dy / nb.dist) * velocity * particles.dt
+        particles.dz += nb.sum(nb.dz / nb.dist) * velocity * particles.dt        # with z=True
+
+    ``mesh`` takes what ``pa.neighbors`` takes ("flat", "spherical", a SphericalMesh, a FieldSet) and is never guessed.  On a spherical
+    mesh the same formula is correct: ``nb.dx`` is in degrees and already wrapped across the antimeridian, ``nb.dist`` is in metres and
+    ``velocity`` in m/s, and cos(lat) cancels between the two, so the displacement comes out in degrees.  ``max_pairs`` has the meaning
+    and the error of ``pa.neighbors``.
+
+    A kernel list of built-in kernels and these tokens runs on the device-resident particle columns (parcels_amd/interactkernels.py);
+    next to a Python function, in RK45 mode, on a UxGrid, next to a CROCO kernel or in a multi-process run the body above runs in the
+    host loop like any user kernel."""
+    who = "AttractTowards"
+    if not isinstance(sources, str):
+        raise TypeError(f"{who}: sources must be the name of a particle Variable, got {type(sources).__name__}")
+    radius = _check_number(who, "radius", radius, positive=True)
+    velocity = _check_number(who, "velocity", velocity, positive=False)
+    _check_interaction_options(who, z, mesh)
+    if max_pairs is not None:
+        import numbers
+
+        if isinstance(max_pairs, bool) or not isinstance(max_pairs, numbers.Integral):
+            raise TypeError(f"{who}: max_pairs must be a non-negative integer or None, got {type(max_pairs).__name__}")
+        if max_pairs < 0:
+            raise ValueError(f"{who}: max_pairs must be a non-negative integer or None, got {max_pairs}")
+        max_pairs = int(max_pairs)
+
+    def token(particles, fieldset):
+        import numpy as np
+
+        from . import interaction
+
+        nb = interaction.neighbors(particles, radius, z=z, mesh=mesh, max_pairs=max_pairs,
+                                   sources=np.asarray(getattr(particles, sources)) != 0, include_coincident=False)
+        particles.dx += nb.sum(nb.dx / nb.dist) * velocity * particles.dt
+        particles.dy += nb.sum(nb.dy / nb.dist) * velocity * particles.dt
+        if z:
+            particles.dz += nb.sum(nb.dz / nb.dist) * velocity * particles.dt
+
+    token.__name__ = token.__qualname__ = f"AttractTowards_{sources}"
+    token.__doc__ = (f"particles.dx, .dy{', .dz' if z else ''} += sum over the particles.{sources} != 0 within {radius!r} of (d / dist) "
+                     f"* {velocity!r} * particles.dt")
+    token._pk_interact = {"kind": "attract", "sources": sources, "radius": radius, "velocity": velocity, "z": z, "mesh": mesh, "max_pairs": max_pairs}
+    return token
+
+
+def MergeNearest(mass: str, radius, *, z=False, mesh="flat"):
+    """The merge kernel of the interaction tutorial as a built-in kernel: two particles that are each other's nearest neighbour within
+    ``radius`` merge -- the heavier keeps the summed mass (equal masses: the lower index keeps), the other is deleted.  ``mass`` names a
+    float32 or float64 particle Variable; it becomes a device Variable.  Returns a kernel token named ``MergeNearest_<mass>`` whose body
+    is the definition::
+
+        j, _ = pa.nearest_neighbor(particles, radius, z=z, mesh=mesh, include_coincident=False)
+        i = np.arange(len(j)); mutual = (j >= 0) & (j[np.where(j >= 0, j, 0)] == i) & (i < j)
+        pi, pj = i[mutual], j[mutual]; m = particles.<mass>
+        big = np.where(m[pj] > m[pi], pj, pi); small = np.where(m[pj] > m[pi], pi, pj)
+        m[big] += m[small]                      # in the Variable's storage dtype
+        particles.state[small] = StatusCode.Delete
+
+    ``mesh`` as for ``AttractTowards``; where the list runs: see there."""
+    who = "MergeNearest"
+    if not isinstance(mass, str):
+        raise TypeError(f"{who}: mass must be the name of a particle Variable, got {type(mass).__name__}")
+    radius = _check_number(who, "radius", radius, positive=True)
+    _check_interaction_options(who, z, mesh)
+
+    def token(particles, fieldset):
+        import numpy as np
+
+        from . import interaction
+        from .statuscodes import StatusCode
+
+        j, _ = interaction.nearest_neighbor(particles, radius, z=z, mesh=mesh, include_coincident=False)
+        i = np.arange(len(j))
+        mutual = (j >= 0) & (j[np.where(j >= 0, j, 0)] == i) & (i < j)
+        pi, pj = i[mutual], j[mutual]
+        m = getattr(particles, mass)
+        heavier = m[pj] > m[pi]
+        big, small = np.where(heavier, pj, pi), np.where(heavier, pi, pj)
+        m[big] += m[small]
+        particles.state[small] = int(StatusCode.Delete)
+
+    token.__name__ = token.__qualname__ = f"MergeNearest_{mass}"
+    token.__doc__ = f"mutual nearest neighbours within {radius!r} merge: the heavier keeps particles.{mass}, the other is deleted"
+    token._pk_interact = {"kind": "merge", "mass": mass, "radius": radius, "z": z, "mesh": mesh}
+    return token
+
+
+def interaction_spec(f):
+    """The parameters of an AttractTowards / MergeNearest token, or None."""
+    return getattr(f, "_pk_interact", None)
 
 
 def kernel_id(f):
