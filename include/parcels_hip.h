@@ -464,10 +464,14 @@ int32_t pk_execute_twe_report(pk_ctx* ctx, int64_t* found, int32_t cap, int32_t*
  *   void launcher(const void* kargs, int32_t prog, int32_t key, int32_t lds, uint64_t lds_bytes, void* hip_stream)
  * prog 0: the interpreter variant (key, lds); prog 1 / 2 (3 / 4): the dedicated A-grid (C-grid) kernel 2-D / 3-D with key = float32 fields
  * * 2 + float32 particles; it must refuse (abort) what it was not built for.  flags: PK_USER_RIDE = the module carries the dedicated kernel
- * pk_generic_variant named, PK_USER_SAMPLES_* and sample_fids as above.  NULL unregisters.  A list with a user id and no launcher fails. */
+ * pk_generic_variant named, PK_USER_SAMPLES_* and sample_fids as above.  NULL unregisters.  A list with a user id and no launcher fails.
+ * On a context with a UxGrid the variant is (key PK_USER_KEY_UX, lds 0), apart from every structured key (0 .. 11): the module carries the
+ * step loop of csrc/pk_ux.h and is registered with PK_USER_UX in flags; a launch refuses a module of the other kind. */
 #define PK_USER_RIDE 1
 #define PK_USER_SAMPLES_UV 2
 #define PK_USER_SAMPLES_UVW 4
+#define PK_USER_UX 8
+#define PK_USER_KEY_UX 12
 int32_t pk_generic_variant(pk_ctx* ctx, const pk_exec_params* prm, int32_t sample_flags, int32_t nsample, const int32_t* sample_fids, int32_t* key,
                            int32_t* lds, int32_t* typed, int32_t* fast);
 int32_t pk_set_user_program(pk_ctx* ctx, void* launcher, int32_t flags, int32_t nsample, const int32_t* sample_fids);
@@ -490,6 +494,12 @@ int32_t pk_execute_end(pk_ctx* ctx, pk_exec_stats* stats);
 #define PK_EVAL_MASKED 0x10000
 int32_t pk_eval(pk_ctx* ctx, const pk_exec_params* params, int32_t what, int64_t m, const double* t, const double* z,
                 const double* y, const double* x, double* out_u, double* out_v, double* out_w, int32_t* out_state);
+/* The same WITH the particles the points belong to (field[t, z, y, x, particles], field.py:394-405) on a UxGrid: ei (in / out, one per
+ * point) is the particles' `ei` on the sampled field's grid.  The face search starts from it when have_guess is set (the reference's
+ * np.any(ei) over the batch, uxgrid.py:113) -- a point found in its guessed face keeps the float64 barycentric coordinates, one found through
+ * the hash the float32-rounded ones -- and ei returns the cell of the sample point.  Fails when the sampled field is not on a UxGrid. */
+int32_t pk_eval_attached(pk_ctx* ctx, const pk_exec_params* params, int32_t what, int32_t have_guess, int64_t m, const double* t, const double* z,
+                         const double* y, const double* x, int32_t* ei, double* out_u, double* out_v, double* out_w, int32_t* out_state);
 
 /* XGrid.search + ravel_index with no guess: ei_out[i] = ravel(search(z, y, x)) on grid `grid_id`
  * (ParticleSet.populate_indices, particleset.py:252-262).  Host arrays of length m. */

@@ -14,6 +14,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PARCELS_HIP_LIB", os.path.join(_HERE, "libparcels_hip.so"))  # override: A/B builds
 
 PK_ABI_VERSION = 9
+# pk_set_user_program flags / the variant key of a UxGrid user module (include/parcels_hip.h)
+PK_USER_RIDE, PK_USER_SAMPLES_UV, PK_USER_SAMPLES_UVW, PK_USER_UX, PK_USER_KEY_UX = 1, 2, 4, 8, 12
 PK_F32, PK_F64 = 0, 1
 PK_MAX_GRIDS, PK_MAX_FIELDS, PK_MAX_KERNELS, PK_NUM_STATE_CODES = 4, 64, 8, 80
 PK_MAX_EXTRA = 8
@@ -267,6 +269,7 @@ ABI_SYMBOLS = [
     "pk_execute_rerun_keys",
     "pk_execute_twe_report",
     "pk_eval",
+    "pk_eval_attached",
     "pk_search",
     "pk_set_croco",
     "pk_sigma_croco",
@@ -365,6 +368,7 @@ def load():
     lib.pk_execute_rerun_keys.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(ExecStats)]
     lib.pk_execute_twe_report.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_int32]
     lib.pk_eval.argtypes = [C.c_void_p, C.POINTER(ExecParams), C.c_int32, C.c_int64] + [C.c_void_p] * 8
+    lib.pk_eval_attached.argtypes = [C.c_void_p, C.POINTER(ExecParams), C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 9
     lib.pk_search.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.pk_set_croco.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32]
     lib.pk_sigma_croco.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5

@@ -1913,6 +1913,7 @@ static bool ctx_has_ugrid(const pk_ctx* ctx) {
 
 // The kernel-list interpreter variant of a launch (include/parcels_hip.h: pk_generic_variant)
 static int32_t interp_key(const pk_ctx* ctx, const pk_exec_params* prm, const KArgs& a) {
+    if (ctx->grids[a.main_grid].d.kind == PK_UX_KIND) return PK_USER_KEY_UX;  // the step loop of pk_ux.h: no structured variant
     return (ctx->fields[prm->fU].d.dtype == PK_F32 ? 6 : 0) + (ctx->grids[a.main_grid].d.kind == 1 ? 3 : 0) + std::min<int>(prm->interp_uv, 2);
 }
 
@@ -2421,19 +2422,20 @@ static int32_t plan_launch(pk_ctx* ctx, const pk_exec_params* prm, const UserSha
     p = LaunchPlan{PROG_GENERIC, DEDICATED_NONE, false, lds_bytes, FAST_LP_OFF};
     if (ctx_has_ugrid(ctx)) {  // a fieldset on a UxGrid: the unstructured program (pk_ux.h) and nothing else
         if (ctx->grids[a.main_grid].d.kind != PK_UX_KIND) return ctx->fail("a launch on a context with a UxGrid needs its velocity on the UxGrid");
-        if (us.present) return ctx->fail("user kernels are not compiled for a UxGrid (they run in the host loop)");
+        if (us.present && !(us.flags & PK_USER_UX))
+            return ctx->fail("the registered user program was built for a structured grid: a launch on a UxGrid needs the UxGrid variant (PK_USER_UX)");
         if (prm->rk45_mode) return ctx->fail("AdvectionRK45 is not implemented on a UxGrid");
         if (prm->interp_uv != 4) return ctx->fail("the velocity on a UxGrid is interpolated with Ux_Velocity (interp_uv 4)");
         for (int k = 0; k < prm->nk; k++) {
             const int id = prm->kernels[k];
-            if (id == PK_KERNEL_ADVECTION_RK45 || id == PK_KERNEL_ADVECTIONDIFFUSION_M1 || id == PK_KERNEL_ADVECTIONDIFFUSION_EM ||
-                id == PK_KERNEL_DIFFUSION_UNIFORM_KH || id == PK_KERNEL_SUBMERGE_THROUGH_SURFACE)
+            if (id == PK_KERNEL_ADVECTION_RK45 || id == PK_KERNEL_SUBMERGE_THROUGH_SURFACE)
                 return ctx->fail("this built-in kernel is not implemented on a UxGrid");
         }
         p.prog = PROG_UX;
         p.lds = 0;
         return 0;
     }
+    if (us.present && (us.flags & PK_USER_UX)) return ctx->fail("the registered user program was built for a UxGrid: it cannot run a launch on a structured grid");
     bool croco = false;
     for (int k = 0; k < prm->nk; k++) croco = croco || prm->kernels[k] == PK_KERNEL_ADVECTION_RK2_3D_CROCO || prm->kernels[k] == PK_KERNEL_SAMPLE_SIGMA_CROCO;
     if (croco) {  // a list with a CROCO kernel: the sigma-grid program (pk_sigma.h), whatever built-in kernels stand beside it
@@ -2666,7 +2668,8 @@ int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
                 break;
             case DEDICATED_C3: launch_cgrid(field_f32, pf32, 1, a, n, p.lds, ctx->compute); break;
             case DEDICATED_NONE:
-                if (p.prog == PROG_UX) launch_ux(pf32, a, n, ctx->compute);
+                if (p.prog == PROG_UX && has_user) ctx->user_launch(&a, DEDICATED_NONE, PK_USER_KEY_UX, 0, 0, (void*)ctx->compute);
+                else if (p.prog == PROG_UX) launch_ux(pf32, a, n, ctx->compute);
                 else if (p.prog == PROG_SIGMA) launch_sigma(field_f32, curv, prm->interp_uv, a, n, p.lds, ctx->compute);
                 else if (has_user) ctx->user_launch(&a, DEDICATED_NONE, interp_key(ctx, prm, a), use_lds, (uint64_t)p.lds, (void*)ctx->compute);
                 else launch_general(p.prog, field_f32, curv, prm, use_lds, a, grid, p.lds, ctx->compute);
@@ -2799,12 +2802,13 @@ int32_t pk_generic_variant(pk_ctx* ctx, const pk_exec_params* prm, int32_t sampl
     int32_t rc = launch_args(ctx, prm, a, lds_bytes, use_lds);
     if (rc) return rc;
     // the module serves every launch of the list: it is asked about as a list with user kernels that may ride
-    const UserShape us{true, PK_USER_RIDE | (sample_flags & (PK_USER_SAMPLES_UV | PK_USER_SAMPLES_UVW)), nsample, sample_fids, true, true};
+    const bool ux = ctx->grids[a.main_grid].d.kind == PK_UX_KIND;  // (the module about to be built is the one this context needs)
+    const UserShape us{true, (ux ? PK_USER_UX : PK_USER_RIDE) | (sample_flags & (PK_USER_SAMPLES_UV | PK_USER_SAMPLES_UVW)), nsample, sample_fids, true, true};
     LaunchPlan p;
     rc = plan_launch(ctx, prm, us, a, lds_bytes, use_lds, p);
     if (rc) return rc;
     *key = interp_key(ctx, prm, a);
-    *lds = use_lds;
+    *lds = ux ? 0 : use_lds;
     *typed = ctx_is_typed(ctx) ? 1 : 0;
     *fast = p.ride ? p.kernel : DEDICATED_NONE;
     return 0;
@@ -2859,17 +2863,24 @@ int32_t pk_execute(pk_ctx* ctx, const pk_exec_params* prm, pk_exec_stats* stats)
 }
 
 // ---- sampling ------------------------------------------------------------------------------------------
-int32_t pk_eval(pk_ctx* ctx, const pk_exec_params* prm, int32_t what, int64_t m, const double* t, const double* z,
-                const double* y, const double* x, double* out_u, double* out_v, double* out_w, int32_t* out_state) {
+// pk_eval (ei == nullptr) and pk_eval_attached (ei: the particles' `ei` on the sampled field's grid, in / out; have_guess: np.any(ei))
+static int32_t eval_points(pk_ctx* ctx, const pk_exec_params* prm, int32_t what, int64_t m, const double* t, const double* z, const double* y,
+                           const double* x, int32_t* ei, int32_t have_guess, double* out_u, double* out_v, double* out_w, int32_t* out_state) {
     if (!ctx || !prm || !t || !z || !y || !x || !out_u) return -2;
     PK_HIP(ctx, hipSetDevice(ctx->device));
     if (m <= 0) return 0;
     pk_exec_params p2 = *prm;
     p2.twe_n = 0;
     p2.reset_state = ctx->eval_points_f32 ? 1 : 0;  // read by eval_kernel as "sample points are float32 columns"
+    if (ei) p2.have_guess0 = have_guess ? 1 : 0;
     if (what >= 0) {  // scalar sampling: the main grid is the sampled field's grid
         if (what >= (int)ctx->fields.size()) return ctx->fail("unknown field id");
         if (p2.fU < 0) { p2.fU = what; p2.fV = what; }
+    }
+    if (ei) {
+        const int fs_ = what >= 0 ? what : p2.fU;
+        if (what < -2 || fs_ < 0 || fs_ >= (int)ctx->fields.size() || ctx->grids[ctx->fields[fs_].d.grid].d.kind != PK_UX_KIND)
+            return ctx->fail("pk_eval_attached: the sampled field does not live on a UxGrid");
     }
     DParticles saved = ctx->dev;
     const bool was_bound = ctx->bound;
@@ -2887,7 +2898,12 @@ int32_t pk_eval(pk_ctx* ctx, const pk_exec_params* prm, int32_t what, int64_t m,
     double* d = nullptr;
     int32_t* ds = nullptr;
     PK_HIP(ctx, hipMalloc((void**)&d, sizeof(double) * m * 7));
-    PK_HIP(ctx, hipMalloc((void**)&ds, sizeof(int32_t) * m));
+    PK_HIP(ctx, hipMalloc((void**)&ds, sizeof(int32_t) * m * (ei ? 2 : 1)));
+    int32_t* de = nullptr;  // attached samples only: the second half of ds
+    if (ei) {
+        de = ds + m;
+        PK_HIP(ctx, hipMemcpyAsync(de, ei, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->compute));
+    }
     double *dt_ = d, *dz = d + m, *dy = d + 2 * m, *dx = d + 3 * m, *du = d + 4 * m, *dv = d + 5 * m, *dw = d + 6 * m;
     PK_HIP(ctx, hipMemcpyAsync(dt_, t, sizeof(double) * m, hipMemcpyHostToDevice, ctx->compute));
     PK_HIP(ctx, hipMemcpyAsync(dz, z, sizeof(double) * m, hipMemcpyHostToDevice, ctx->compute));
@@ -2911,7 +2927,8 @@ int32_t pk_eval(pk_ctx* ctx, const pk_exec_params* prm, int32_t what, int64_t m,
     if (ux) {
         const int eg = ctx->fields[what >= 0 ? what : p2.fU].d.grid;
         if (ctx->grids[eg].d.kind != PK_UX_KIND && what < 0) return ctx->fail("a vector field next to a UxGrid must live on the UxGrid");
-        launch_ux_eval(a, what, m, dt_, dz, dy, dx, du, dv, dw, ds, ctx->compute);
+        if (ei) launch_ux_eval_attached(a, what, m, dt_, dz, dy, dx, de, du, dv, dw, ds, ctx->compute);
+        else launch_ux_eval(a, what, m, dt_, dz, dy, dx, du, dv, dw, ds, ctx->compute);
     } else {
 #define PK_EVAL(FT, IN, TY) hipLaunchKernelGGL((eval_kernel<FT, IN, TY>), grid, dim3(256), 0, ctx->compute, a, what, m, dt_, dz, dy, dx, du, dv, dw, ds)
 #define PK_EVAL_T(FT, IN) do { if (typed) PK_EVAL(FT, IN, true); else PK_EVAL(FT, IN, false); } while (0)
@@ -2929,10 +2946,22 @@ int32_t pk_eval(pk_ctx* ctx, const pk_exec_params* prm, int32_t what, int64_t m,
     if (out_v) PK_HIP(ctx, hipMemcpyAsync(out_v, dv, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->compute));
     if (out_w) PK_HIP(ctx, hipMemcpyAsync(out_w, dw, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->compute));
     if (out_state) PK_HIP(ctx, hipMemcpyAsync(out_state, ds, sizeof(int32_t) * m, hipMemcpyDeviceToHost, ctx->compute));
+    if (ei) PK_HIP(ctx, hipMemcpyAsync(ei, de, sizeof(int32_t) * m, hipMemcpyDeviceToHost, ctx->compute));
     PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
     PK_HIP(ctx, hipFree(d));
     PK_HIP(ctx, hipFree(ds));
     return 0;
+}
+
+int32_t pk_eval(pk_ctx* ctx, const pk_exec_params* prm, int32_t what, int64_t m, const double* t, const double* z,
+                const double* y, const double* x, double* out_u, double* out_v, double* out_w, int32_t* out_state) {
+    return eval_points(ctx, prm, what, m, t, z, y, x, nullptr, 0, out_u, out_v, out_w, out_state);
+}
+
+int32_t pk_eval_attached(pk_ctx* ctx, const pk_exec_params* prm, int32_t what, int32_t have_guess, int64_t m, const double* t, const double* z,
+                         const double* y, const double* x, int32_t* ei, double* out_u, double* out_v, double* out_w, int32_t* out_state) {
+    if (!ei) return -2;
+    return eval_points(ctx, prm, what, m, t, z, y, x, ei, have_guess, out_u, out_v, out_w, out_state);
 }
 
 int32_t pk_search(pk_ctx* ctx, int32_t grid_id, int64_t m, const double* z, const double* y, const double* x, int32_t* ei_out) {

@@ -26,10 +26,13 @@ constexpr int UXF_SPH = 16;
 constexpr double UX_BC_TOL = -1e-6;               // coords >= -1e-6 (index_search.py:376)
 constexpr double UX_SUM_TOL = 1e-6 + 1e-3 * 1.0;  // np.isclose(sum, 1.0, rtol=1e-3, atol=1e-6): |sum - 1| <= atol + rtol * |1|
 
-// launchers (pk_prog_ux.hip, the only translation unit that defines PK_UX_KERNELS and so the kernels below)
+// launchers (pk_prog_ux.hip: the library's translation unit that defines PK_UX_KERNELS and so the kernels below; the only other one is the
+// module parcels_amd/jit.py generates for a kernel list with user kernels, which instantiates advect_ux_kernel with PK_USER_KERNELS)
 void launch_ux(int particles_f32, const KArgs& a, int64_t n, hipStream_t stream);
 void launch_ux_eval(const KArgs& a, int what, int64_t m, const double* t, const double* z, const double* y, const double* x, double* ou,
                     double* ov, double* ow, int32_t* ost, hipStream_t stream);
+void launch_ux_eval_attached(const KArgs& a, int what, int64_t m, const double* t, const double* z, const double* y, const double* x, int32_t* ei,
+                             double* ou, double* ov, double* ow, int32_t* ost, hipStream_t stream);
 void launch_ux_search(const DGrid& g, int64_t m, const double* z, const double* y, const double* x, int32_t* ei, hipStream_t stream);
 
 #ifdef PK_UX_KERNELS
@@ -425,6 +428,7 @@ __global__ void __launch_bounds__(256, 2) advect_ux_kernel(const KArgs a) {
     }
 }
 
+#ifndef PK_USER_KERNELS  // (a generated user module launches the step loop only)
 // Field.eval / VectorField.eval at explicit points on a UxGrid (pk_eval): what >= 0 scalar field, -1 UV, -2 UVW.  No guess (ei = None).
 __global__ void __launch_bounds__(256) eval_ux_kernel(const KArgs a, int what, int64_t m, const double* t, const double* z, const double* y,
                                                       const double* x, double* ou, double* ov, double* ow, int32_t* ost) {
@@ -455,6 +459,41 @@ __global__ void __launch_bounds__(256) eval_ux_kernel(const KArgs a, int what, i
     if (ost) ost[i] = c.state | (c.oob ? PK_EVAL_MASKED : 0);
 }
 
+// The same WITH the particles the points belong to (pk_eval_attached; field.py:394-405): the search starts from the particles' `ei` on the
+// sampled field's grid when the batch has a guess (a.prm.have_guess0: the reference's np.any(ei)), and `ei` returns the cell of the sample
+// point -- what one evaluation of the step loop above does for its particle.
+__global__ void __launch_bounds__(256) eval_ux_attached_kernel(const KArgs a, int what, int64_t m, const double* t, const double* z, const double* y,
+                                                               const double* x, int32_t* ei, double* ou, double* ov, double* ow, int32_t* ost) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    PCtx c;
+    c.state = PK_EVALUATE;
+    c.pf = false;
+    c.hz = c.hy = c.hx = c.ht = 0;
+    c.hyx_valid = false;
+    c.first_eval = 0xFu;
+    c.u32 = c.v32 = false;
+    c.oob = false;
+    c.ei0 = c.ei1 = c.ei2 = c.ei3 = 0;
+    c.it = 0u;
+    c.klo = 0;
+    const int grid = kfield(a, what < 0 ? a.prm.fU : what).grid;
+    ei_set(c, grid, ei[i]);
+    const bool pos_f32 = a.prm.reset_state != 0;  // option "eval_points_f32" (pk_eval)
+    c.zpos_f32 = pos_f32;
+    if (what < 0) {
+        double u, v, w;
+        ux_eval_uvw(a, c, what == -2, t[i], z[i], y[i], x[i], pos_f32, u, v, w);
+        ou[i] = u;
+        if (ov) ov[i] = v;
+        if (ow) ow[i] = w;
+    } else {
+        ou[i] = ux_eval_scalar(a, c, what, t[i], z[i], y[i], x[i], pos_f32);
+    }
+    ei[i] = ei_get(c, grid);
+    if (ost) ost[i] = c.state | (c.oob ? PK_EVAL_MASKED : 0);
+}
+
 // UxGrid.search + ravel_index with no guess (pk_search)
 __global__ void __launch_bounds__(256) search_ux_kernel(const DGrid g, int64_t m, const double* z, const double* y, const double* x, int32_t* ei) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -464,6 +503,7 @@ __global__ void __launch_bounds__(256) search_ux_kernel(const DGrid g, int64_t m
     ux_search(g, z[i], y[i], x[i], false, 0, p, nodes);
     ei[i] = (int32_t)((int64_t)p.zi * g.nx + p.fi);
 }
+#endif  // !PK_USER_KERNELS
 
 #endif  // PK_UX_KERNELS
 

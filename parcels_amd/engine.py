@@ -1113,12 +1113,19 @@ class DeviceEngine:
         return out
 
     # ---- sampling (Field.eval / VectorField.eval) ---------------------------------------------------------------
-    def sample(self, name, t, z, y, x):
+    def sample(self, name, t, z, y, x, ei=None):
+        """Field.eval / VectorField.eval at explicit points.  ``ei`` (a field on a UxGrid sampled WITH the particles, field.py:394-405): the
+        particles' `ei` on the field's grid, one per point -- the face search starts from it, and ``last_sample_ei`` is the cell of every
+        sample point afterwards (None when the sample was taken without a guess: no ``ei`` given, or field levels that stream through a
+        ring of slots -- ``_sample_streamed`` visits the points window by window and searches unguessed, as before)."""
         fs = self.fieldset
         f = fs.fields[name]
         t, z, y, x = np.broadcast_arrays(*(np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (t, z, y, x)))
         t, z, y, x = (np.ascontiguousarray(v) for v in (t, z, y, x))
         m = x.shape[0]
+        self.last_sample_ei = None
+        if ei is not None and (self.windowed or len(ei) != m or m == 0):
+            ei = None
         if self.windowed and m > 0:
             return self._sample_streamed(name, t, z, y, x)
         u, v, w = np.zeros(m), np.zeros(m), np.zeros(m)
@@ -1133,10 +1140,16 @@ class DeviceEngine:
             what = self.field_ids[name]
             prm.fU = prm.fV = what
             prm.fW = -1
-        self.ctx.check(
-            self.lib.pk_eval(self.ctx.handle, C.byref(prm), what, m, _ptr(t), _ptr(z), _ptr(y), _ptr(x), _ptr(u), _ptr(v), _ptr(w), _ptr(st)),
-            "pk_eval",
-        )
+        if ei is not None:
+            ei = np.ascontiguousarray(ei, dtype=np.int32).copy()
+            self.ctx.check(self.lib.pk_eval_attached(self.ctx.handle, C.byref(prm), what, int(np.any(ei)), m, _ptr(t), _ptr(z), _ptr(y), _ptr(x), _ptr(ei),
+                                                     _ptr(u), _ptr(v), _ptr(w), _ptr(st)), "pk_eval_attached")
+            self.last_sample_ei = ei
+        else:
+            self.ctx.check(
+                self.lib.pk_eval(self.ctx.handle, C.byref(prm), what, m, _ptr(t), _ptr(z), _ptr(y), _ptr(x), _ptr(u), _ptr(v), _ptr(w), _ptr(st)),
+                "pk_eval",
+            )
         self.last_sample_masked = (st & _hip.PK_EVAL_MASKED) != 0  # the rows whose value was zeroed for an out-of-bounds index
         self.last_sample_state = self._finish_sample_state(st)
         return u, v, w

@@ -236,9 +236,10 @@ class Field:
         if self._fieldset is None:
             raise RuntimeError("Field is not attached to a FieldSet")
         eng = self._fieldset._engine_or_create()
+        guess = _attached_guess(particles, eng, self)
         with _points_dtype(eng, y):
-            val = eng.sample(self.name, *_sample_points(t, z, y, x))[0]
-        _mark_particles(particles, eng, self, z, y, x)
+            val = eng.sample(self.name, *_sample_points(t, z, y, x), **({"ei": guess} if guess is not None else {}))[0]
+        _mark_particles(particles, eng, self, z, y, x, ei=getattr(eng, "last_sample_ei", None) if guess is not None else None)
         return val
 
     def __getitem__(self, key):
@@ -308,9 +309,23 @@ def _eval_key(field, key):
     return val
 
 
-def _mark_particles(particles, eng, field=None, z=None, y=None, x=None):
+def _attached_guess(particles, eng, field):
+    """A sample WITH the particles on a UxGrid starts its face search from their `ei` (field.py:173-176, uxgrid.py:113-118): a point found
+    in its guessed face keeps float64 barycentric coordinates, one found through the hash float32-rounded ones -- which a node-registered
+    field shows in its value.  -> the `ei` of the selected rows on the field's grid, or None (no particles; a structured grid, whose
+    search gives the same cell coordinates with and without a guess here)."""
+    from .hostkernels import HostParticles
+    from .uxgrid import UxGrid
+
+    if not isinstance(particles, HostParticles) or not isinstance(field.grid, UxGrid) or len(particles._rows) == 0:
+        return None
+    return np.ascontiguousarray(particles._data["ei"][particles._rows, eng.grids.index(field.grid)], dtype=np.int32)
+
+
+def _mark_particles(particles, eng, field=None, z=None, y=None, x=None, ei=None):
     """What sampling does to the particles a kernel passed along (field.py:394-405): their `ei` on the field's grid becomes the cell of
-    the sample point (_update_particles_ei, :307-317), the points it fails on get the error codes (:327-378)."""
+    the sample point (_update_particles_ei, :307-317; ``ei``: what a guessed search on a UxGrid found), the points it fails on get the
+    error codes (:327-378)."""
     from .hostkernels import HostParticles, _apply_sample_states
     from .statuscodes import OutsideTimeInterval
 
@@ -324,7 +339,7 @@ def _mark_particles(particles, eng, field=None, z=None, y=None, x=None):
         _, zz, yy, xx = _sample_points(0.0, z, y, x)
         n = len(particles._rows)
         zz, yy, xx = (np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)) for v in (zz, yy, xx))
-        particles._data["ei"][particles._rows, igrid] = eng.search(igrid, zz, yy, xx)
+        particles._data["ei"][particles._rows, igrid] = ei if ei is not None and len(ei) == n else eng.search(igrid, zz, yy, xx)
     _apply_sample_states(particles, getattr(eng, "last_sample_state", None))
 
 
@@ -366,9 +381,10 @@ class VectorField:
         if self._fieldset is None:
             raise RuntimeError("VectorField is not attached to a FieldSet")
         eng = self._fieldset._engine_or_create()
+        guess = _attached_guess(particles, eng, self.U)
         with _points_dtype(eng, y):
-            u, v, w = eng.sample(self.name, *_sample_points(t, z, y, x))
-        _mark_particles(particles, eng, self.U, z, y, x)
+            u, v, w = eng.sample(self.name, *_sample_points(t, z, y, x), **({"ei": guess} if guess is not None else {}))
+        _mark_particles(particles, eng, self.U, z, y, x, ei=getattr(eng, "last_sample_ei", None) if guess is not None else None)
         return (u, v, w) if self.vector_type == "3D" else (u, v)
 
     def __getitem__(self, key):

@@ -453,6 +453,11 @@ class _Translator(ast.NodeVisitor):
         if not attached:
             # field.py:173-176: no guess from `ei`, no state update, `ei` stays.  On a rectilinear grid the search does not depend on the
             # guess; a curvilinear search that starts from the hash returns float32-rounded cell coordinates (index_search.py:242-295)
+            if any(type(g).__name__ == "UxGrid" for g in getattr(self.fieldset, "gridset", ())):
+                # uxgrid.py:105-135: without the particles there is no guess, the face comes from the hash and its barycentric coordinates
+                # are float32-rounded (spatialhash.py:511) -- the attached form is the one the UxGrid step loop carries
+                raise NotTranslatable("sample without particles on a UxGrid (the face search starts from the hash, not from `ei`; pass the particles: "
+                                      "fieldset.F[t, z, y, x, particles])")
             ufld = getattr(fld, "U", None)
             curv = getattr(getattr(ufld if ufld is not None else fld, "grid", None), "is_curvilinear", None)
             if curv is None:
@@ -1120,6 +1125,40 @@ extern "C" void pk_user_launch(const void* kargs, int32_t prog, int32_t key, int
 """
 
 
+# The module of a FieldSet on a UxGrid: the step loop of csrc/pk_ux.h (advect_ux_kernel) instead of the structured interpreter.  Its variant is
+# (PK_USER_KEY_UX, 0) -- no structured key -- so a module of one kind can never be launched as the other.
+PK_USER_UX, PK_USER_KEY_UX = _hip.PK_USER_UX, _hip.PK_USER_KEY_UX
+_TEMPLATE_UX = """// generated by parcels_amd/jit.py -- user kernels on a UxGrid: {names}
+#define PK_USER_KERNELS 1
+#define PK_UX_KERNELS 1
+#include <stdint.h>
+namespace pk {{
+struct PkUserLocals {{
+{decl}
+}};
+}}
+#include "pk_ux.h"
+namespace pk {{
+PK_DEV bool user_prepare(const KArgs& a, int uk, int stage, int kslot, PCtx& c, PState& p, KLocal& L, Request& rq) {{
+    switch (uk) {{
+{cases}
+        default: c.state = PK_ERROR; return true;
+    }}
+}}
+}}  // namespace pk
+extern "C" void pk_user_launch(const void* kargs, int32_t prog, int32_t key, int32_t lds, uint64_t lds_bytes, void* stream) {{
+    using namespace pk;
+    const KArgs& a = *(const KArgs*)kargs;
+    if (prog != 0 || key != {key} || lds != 0 || lds_bytes != 0 || a.p.spatial_f32 != {pfm}) {{
+        fprintf(stderr, "parcels_amd user program built for the UxGrid variant (0, %d, 0) with float%d particles, launched as (%d, %d, %d) with float%d particles\\n",
+                {key}, {pfm} ? 32 : 64, prog, key, lds, a.p.spatial_f32 ? 32 : 64);
+        abort();
+    }}
+    hipLaunchKernelGGL((advect_ux_kernel<{pfm}>), dim3((unsigned)((a.p.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+}}
+"""
+
+
 def _csrc_hash() -> str:
     h = hashlib.sha256()
     for f in sorted(os.listdir(_CSRC)):
@@ -1147,21 +1186,25 @@ class UserProgram:
     """One compiled module: the kernel-list interpreter of ONE variant with up to PK_MAX_USER_KERNELS user kernels in it."""
 
     def __init__(self, sources: list[UserKernelSource], key: int, lds: int, fast: int = 0, particles_f32: bool = False):
-        """key / lds: the interpreter variant (pk_generic_variant); fast: 1 / 2 = also carry the dedicated A-grid kernel (2-D / 3-D) with
-        the user kernels riding along -- only for modules whose kernels sample no field and leave next_dt alone."""
+        """key / lds: the interpreter variant (pk_generic_variant; key PK_USER_KEY_UX: the step loop of a UxGrid, csrc/pk_ux.h).
+        fast: 1 / 2 = also carry the dedicated A-grid kernel (2-D / 3-D) with the user kernels riding along -- only for modules whose
+        kernels sample no field and leave next_dt alone."""
         if not (1 <= len(sources) <= PK_MAX_USER_KERNELS):
             raise NotTranslatable(f"1 .. {PK_MAX_USER_KERNELS} user kernels per kernel list")
         self.sources = list(sources)
         decl = "\n".join("    " + d for s in sources for d in s.decl) or "    char unused;"
         # the locals of different kernels never live at the same time, but they are few: one struct, distinct names
         cases = "\n".join(f"        case {k}: {{\n" + textwrap.indent(s.case_body(), "            ") + "\n        }" for k, s in enumerate(sources))
-        ft = "float" if key >= 6 else "double"
+        self.ux = key == PK_USER_KEY_UX
+        if not (0 <= key < 12 or self.ux):
+            raise NotTranslatable(f"unknown program variant {key}")
+        ft = "float" if 6 <= key < 12 else "double"
         kind, interp = (key % 6) // 3, key % 3
         # what the kernels sample decides whether the list may ride in a dedicated kernel (pk_generic_variant was asked with the same lists)
         sampled = [x for src in sources for x in src.sampled]
         self.sample_fids = sorted({x for x in sampled if isinstance(x, int)})
         self.sample_flags = (2 if "UV" in sampled else 0) | (4 if "UVW" in sampled else 0)  # PK_USER_SAMPLES_UV / _UVW
-        rides = fast and all("next_dt" not in src.touched and not src.detached for src in sources) and len(self.sample_fids) <= 4
+        rides = fast and not self.ux and all("next_dt" not in src.touched and not src.detached for src in sources) and len(self.sample_fids) <= 4
         self.flags = (1 | self.sample_flags) if rides else self.sample_flags  # PK_USER_RIDE: the module carries the dedicated kernel
         fast_launch = ""
         if self.flags & 1:
@@ -1177,8 +1220,15 @@ class UserProgram:
                 launch = (f"if (a.fastc.near_edges) hipLaunchKernelGGL((advect_cgrid_kernel<{ft}, {pfm}, {d3}, true>), {grid_}); "
                           f"else hipLaunchKernelGGL((advect_cgrid_kernel<{ft}, {pfm}, {d3}, false>), {grid_});")
             fast_launch = f"        if (prog == {int(fast)} && key == {fkey}) {{\n            {launch}\n            return;\n        }}"
-        self.source = _TEMPLATE.format(names=", ".join(s.name for s in sources), decl=decl, cases=cases, key=key, lds=lds, ft=ft, kind=kind,
-                                       interp=interp, ldsb="true" if lds else "false", fast_launch=fast_launch)
+        names = ", ".join(s.name for s in sources)
+        if self.ux:
+            if lds:
+                raise NotTranslatable("the UxGrid program stages nothing in LDS")
+            self.flags = PK_USER_UX | self.sample_flags
+            self.source = _TEMPLATE_UX.format(names=names, decl=decl, cases=cases, key=key, pfm=1 if particles_f32 else 0)
+        else:
+            self.source = _TEMPLATE.format(names=names, decl=decl, cases=cases, key=key, lds=lds, ft=ft, kind=kind, interp=interp,
+                                           ldsb="true" if lds else "false", fast_launch=fast_launch)
         # (measured on C2 with a sampling kernel riding in the dedicated A-grid kernel, tools/bench_user_kernels.py: 4 waves per SIMD 12.6 ms,
         # 3 waves 13.8 ms, 2 waves 12.5 ms -- the library's own occupancy target stays; PARCELS_AMD_JIT_FAST_WAVES overrides for A/B runs)
         # A dedicated kernel that carries user kernels keeps the correctly rounded quotients and full-range sines / cosines of the general

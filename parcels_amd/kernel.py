@@ -27,7 +27,7 @@ _RESERVED_COLUMNS = {"t", "z", "y", "x", "dz", "dy", "dx", "dt", "next_dt", "sta
 
 
 # built-in kernels the UxGrid program does not carry (csrc/pk_ux.h): each needs fixtures of its own first
-_NOT_ON_UXGRID = (_k.AdvectionRK45, _k.AdvectionDiffusionM1, _k.AdvectionDiffusionEM, _k.DiffusionUniformKh, _k.SubmergeParticle)
+_NOT_ON_UXGRID = (_k.AdvectionRK45, _k.SubmergeParticle)
 
 
 def _on_uxgrid(fieldset) -> bool:
@@ -398,10 +398,7 @@ class Kernel:
         engine = pset._engine()
         pset._t_live = None
         if self.host_functions and not self._jit_tried:
-            if _on_uxgrid(self._fieldset):  # no compiled user kernels on a UxGrid: they run in the host loop
-                self._jit_tried = True
-                self.jit_report = "user kernels are not compiled for a UxGrid"
-            elif any(_is_croco(f) for f in self._kernels):  # nor next to a CROCO kernel (csrc/pk_sigma.h)
+            if any(_is_croco(f) for f in self._kernels):  # no compiled user kernels next to a CROCO kernel (csrc/pk_sigma.h)
                 self._jit_tried = True
                 self.jit_report = "user kernels are not compiled next to a CROCO kernel"
             else:
