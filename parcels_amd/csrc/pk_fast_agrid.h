@@ -201,8 +201,14 @@ PK_DEV void fast_search(const pk_tab2* tab, int n, double first, double last, do
 // crossed an edge on either axis (which happens in nearly every wave-evaluation: round 5's kernel walked through up to six dependent
 // ~100-cycle LDS round trips per evaluation here; the PMC pass showed 0.36 of its wave cycles in s_waitcnt and no gain from fewer VALU
 // instructions alone, profiles/r06a_c2_flags_pmc.md).
+// `kept` (a compile-time NULL for the callers that do not ask): the table entries of the cells found, for a caller that holds them (FCtx::ya).
+struct CellEntries {
+    pk_tab2 ea, eb;   // {a[i], 1 / width} of lat, lon
+    double a1a, a1b;  // a[i + 1]
+};
 PK_DEV void fast_search2(const pk_tab2* taba, int na, double firsta, double lasta, double xa, int& cella, int& idxa, double& bca,
-                         const pk_tab2* tabb, int nb, double firstb, double lastb, double xb, int& cellb, int& idxb, double& bcb) {
+                         const pk_tab2* tabb, int nb, double firstb, double lastb, double xb, int& cellb, int& idxb, double& bcb,
+                         CellEntries* kept = nullptr) {
     int ia = cella, ib = cellb;
     pk_tab2 ea = taba[ia], eb = tabb[ib];
     double a1a = taba[ia + 1].x, a1b = tabb[ib + 1].x;
@@ -239,6 +245,10 @@ PK_DEV void fast_search2(const pk_tab2* taba, int na, double firsta, double last
     }
     idxa = ia;
     idxb = ib;
+    if (kept) {
+        kept->ea = ea; kept->a1a = a1a;
+        kept->eb = eb; kept->a1b = a1b;
+    }
 }
 
 // The two x-corners of one (level, z, y) row at byte offset `off` from a wave-uniform base: one wide load in saddr form.
@@ -429,6 +439,37 @@ PK_DEV double lp_sum(const LpField& f, double tau, double eta, double xsi) {
 
 PK_DEV int uniform_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// ---- cell record in registers (FAST_LP_CACHE only) ---------------------------------------------------------------------------------
+// A lane's cell changes in under 1 % of its evaluations (tests/test_gpu_level_pair_cache.py: the premise), yet every evaluation read the
+// two table entries per axis of that cell from LDS, compared, handled the edge cells and ravelled the index again -- one dependent LDS round
+// trip and ~27 VALU instructions in front of the block read.  PK_FAST_CELL_REGS keeps the entries in registers (FCtx::ya ..):
+//   * a lane with ya < y <= yb and xa < x <= xb is in the cell of its previous evaluation: indices, `ei` and the block test stay as they
+//     are and eta, xsi are the same (x - a) * RN(1 / width) on the same operands.  The strict test accepts a subset of what the table test
+//     accepts for that cell and the search is a pure function of the coordinate, so every other lane -- first evaluation, new cell,
+//     exactly on a node, outside an edge cell, NaN -- runs fast_search2 as before and renews the record from the entries it fetched;
+//   * a search that answered an out-of-bounds code (or a depth outside the grid) leaves no record: such a lane takes the table path and
+//     its status rules in every evaluation;
+//   * depth is searched when the particle's z is new, not in every evaluation: the 2-D stages never move z, so FCtx::mz and its compare leave
+//     the stage loop and the search is keyed on FAST_Z_UNSEARCHED.  z does move where the step loop adds a dz the particle brought into the
+//     launch (ParticleSet(..., dz=...), a dz an earlier kernel left): the position update re-arms the search there (fctx_depth_moved), one
+//     compare per step.  It drops the record as well -- a same-cell lane tests no index, and the new depth may lie outside the grid.
+// 0 = the table search in every evaluation (the code before the record; A/B builds).  FAST_LP_REGS, FAST_LP_OFF and modules with user
+// kernels are not affected.  (Measured step by step -- the record alone, then without ravel and tests on a same-cell lane, then with the early
+// block read: profiles/c2_cell_registers_ab.txt.)
+#ifndef PK_FAST_CELL_REGS
+#define PK_FAST_CELL_REGS 1
+#endif
+constexpr bool fast_cell_regs(int lp) { return PK_FAST_CELL_REGS != 0 && lp == FAST_LP_CACHE; }
+
+// The status rules of eval_uvw_fast for an evaluation some index of which carries an out-of-bounds code (field.py:307-378; the record's cold path)
+PK_DEV int fast_oob_state(int s, int xi, int yi, int zi, double xsi, double eta, double zeta, double tau) {
+    if ((xi == RIGHT_OUT_OF_BOUNDS || yi == RIGHT_OUT_OF_BOUNDS || zi == RIGHT_OUT_OF_BOUNDS) && s < PK_ERROROUTOFBOUNDS) s = PK_ERROROUTOFBOUNDS;
+    if (zi == LEFT_OUT_OF_BOUNDS && s < PK_ERRORTHROUGHSURFACE) s = PK_ERRORTHROUGHSURFACE;
+    const bool bad = !(isfinite(xsi) && isfinite(eta) && isfinite(zeta) && isfinite(tau));
+    if (bad && s < PK_ERRORINTERPOLATION) s = PK_ERRORINTERPOLATION;
+    return s;
+}
+
 // Per-particle evaluation context of the fast kernels.  Besides the status code and the `ei` entry of the velocity grid it holds
 // the cells of the previous evaluation (always valid cell indices: the search hints) and a memo of the last time and depth
 // searched: the search is a pure function of the coordinate, and the Runge-Kutta stages revisit t (stages 2 and 3 share
@@ -450,13 +491,25 @@ struct FCtx {
     // Level-pair cache (FAST_LP_CACHE): the slot holds Z0 / D of cell `bei` at depth mz for the wave-uniform key `bkey` of eval_uvw_fast
     // (ti << 2 | lenT << 1 | lenZ); a new depth drops the block, a new time alone does not.
     int32_t bkey;
+    // Cell record (PK_FAST_CELL_REGS, FAST_LP_CACHE): the table entries of the lane's cell (hy, hx) -- first node, second node, 1 / width of lat and
+    // of lon -- held in registers for as long as the lane stays inside it.  ya = +inf: no record (the test of eval_uvw_fast fails).
+    double ya, yb, yr, xa, xb, xr;
 };
 constexpr int32_t FAST_NO_BLOCK = -0x7fffffff - 1;
-PK_DEV void fctx_init(FCtx& c, int state, int32_t ei) {
+constexpr int FAST_Z_UNSEARCHED = -3;  // FCtx::zi before the launch's one depth search (PK_FAST_CELL_REGS; no index, no out-of-bounds code)
+// PK_FAST_CELL_REGS: the step loop moved z by a non-zero dz -- search depth again in the next evaluation (which drops the block of the old
+// depth and forms `zez`, `ei` anew), on the table path
+PK_DEV void fctx_depth_moved(FCtx& c) {
+    c.zi = FAST_Z_UNSEARCHED;
+    c.ya = __builtin_inf();
+}
+PK_DEV void fctx_init(FCtx& c, int state, int32_t ei, bool cell_regs = false) {
     c.state = state;
     c.ei = ei;
     c.ht = c.hz = c.hy = c.hx = 0;
-    c.zi = 0;
+    c.zi = cell_regs ? FAST_Z_UNSEARCHED : 0;
+    c.ya = c.xa = __builtin_inf();
+    c.yb = c.xb = c.yr = c.xr = 0.0;
     c.zez = 0u;
     c.mt = c.mz = __builtin_nan("");  // equal to nothing
     c.mtau = c.mzeta = 0.0;
@@ -475,6 +528,17 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
     uint32_t fl = T.fl;
     asm volatile("" : "+s"(fl));  // opaque: every FA_* test below is a scalar bit test HERE, not a loop-invariant lane mask (FastTabs::fl)
     u = v = w = 0.0;
+    // With the cell record the lane's block is requested HERE, in front of the time search and the cell test, which run under its latency (the slot
+    // address is a lane constant).  A lane whose block turns out stale throws the values away: the miss branch re-reads behind its write.  Before
+    // the slot's first fill the values are whatever LDS holds -- nothing but the final sums is formed from them, and a lane without a block misses.
+    // (Not in the instantiations for float32 particle storage: they start 6 VGPRs higher, and with the 16 of the early block
+    // advect_fast_kernel<double, 1, false, FAST_LP_CACHE> spilled 4 VGPRs inside the stage loop.)
+    constexpr bool SPEC = fast_cell_regs(LP) && !PF;
+    LpField fu, fv;
+    if constexpr (SPEC) {
+        fu.p0 = T.blk[0]; fu.p1 = T.blk[FAST_WG_LP]; fu.d0 = T.blk[2 * FAST_WG_LP]; fu.d1 = T.blk[3 * FAST_WG_LP];
+        fv.p0 = T.blk[4 * FAST_WG_LP]; fv.p1 = T.blk[5 * FAST_WG_LP]; fv.d0 = T.blk[6 * FAST_WG_LP]; fv.d1 = T.blk[7 * FAST_WG_LP];
+    }
     int ti = 0;
     double tau = 0.0;
     if (fl & FA_TI) {  // _search_time_index (index_search.py:65-91); (it, klo): the key of this sample (pk_device.h: twe_note -- a launch with LISTED
@@ -495,11 +559,12 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
     }
     int zi = 0, yi = 0, xi = 0;
     double zeta = 0.0, eta = 0.0, xsi = 0.0;
+    constexpr bool CR = fast_cell_regs(LP);
     if (fl & FA_Z) {
-        if (!(z == c.mz)) {
+        if (CR ? c.zi == FAST_Z_UNSEARCHED : !(z == c.mz)) {
             fast_search<true>(T.depth, F.gnz, F.z0, F.z1, z, c.hz, c.zi, c.mzeta, (fl & FA_NZ2) != 0);
             c.zez = (uint32_t)c.zi * F.ez;
-            c.mz = z;
+            if (!CR) c.mz = z;
             c.bei = FAST_NO_BLOCK;
         }
         zi = c.zi;
@@ -509,41 +574,71 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
 #define PK_FAST_SEARCH2 1
 #endif
     constexpr uint32_t YX2 = FA_Y | FA_X | FA_NY2 | FA_NX2;
-    if (PK_FAST_SEARCH2 && (fl & YX2) == YX2) {
-        fast_search2(T.lat, T.gny, F.y0, F.y1, y, c.hy, yi, eta, T.lon, T.gnx, F.x0, F.x1, x, c.hx, xi, xsi);
+    if constexpr (CR) {
+        const bool yx2 = (fl & YX2) == YX2;
+        // (bitwise: four compares and three s_and, no short-circuit exec-mask blocks; a NaN fails)
+        const bool same = yx2 & (c.ya < y) & (y <= c.yb) & (c.xa < x) & (x <= c.xb);
+        if (__builtin_expect(same, 1)) {
+            eta = fast_bary(y, c.ya, c.yb, c.yr);
+            xsi = fast_bary(x, c.xa, c.xb, c.xr);
+        } else {
+            CellEntries e;
+            if (yx2) {
+                fast_search2(T.lat, T.gny, F.y0, F.y1, y, c.hy, yi, eta, T.lon, T.gnx, F.x0, F.x1, x, c.hx, xi, xsi, &e);
+            } else {
+                if (fl & FA_Y) fast_search<true>(T.lat, T.gny, F.y0, F.y1, y, c.hy, yi, eta, (fl & FA_NY2) != 0);
+                if (fl & FA_X) fast_search<true>(T.lon, T.gnx, F.x0, F.x1, x, c.hx, xi, xsi, (fl & FA_NX2) != 0);
+            }
+            c.ei = (int32_t)((uint32_t)xi + (uint32_t)yi * F.ey + c.zez);  // (cold: the wrapped 32-bit product serves indices and codes alike)
+            if (__builtin_expect((xi | yi | zi) < 0, 0)) {
+                c.state = fast_oob_state(c.state, xi, yi, zi, xsi, eta, zeta, tau);
+                c.ya = __builtin_inf();
+                return;
+            }
+            if (yx2) {
+                c.ya = e.ea.x; c.yb = e.a1a; c.yr = e.ea.y;
+                c.xa = e.eb.x; c.xb = e.a1b; c.xr = e.eb.y;
+            }
+        }
     } else {
-        if (fl & FA_Y) fast_search<true>(T.lat, T.gny, F.y0, F.y1, y, c.hy, yi, eta, (fl & FA_NY2) != 0);
-        if (fl & FA_X) fast_search<true>(T.lon, T.gnx, F.x0, F.x1, x, c.hx, xi, xsi, (fl & FA_NX2) != 0);
-    }
-    // ravel_index (basegrid.py:83-152): the low 32 bits of the int64 sum are the wrapped 32-bit sum.  Of its three 32-bit products (v_mul_lo_u32
-    // each) one is left, and that one at full rate: ex == 1 (the fast path needs an x axis: pk_api.hip fill_fast, ravel_strides), zi * ez changes
-    // only with the depth memo (FCtx::zez), and for an in-bounds yi both yi and ey are below the 3840 nodes a 60 KB coordinate table holds, far
-    // inside the 24 bits of v_mad_u32_u24.  An out-of-bounds code (negative) takes the wrapped 32-bit product.
-    c.ei = (int32_t)((uint32_t)xi + __umul24((uint32_t)yi, F.ey) + c.zez);
-    if (__builtin_expect((xi | yi | zi) < 0, 0)) {  // some index carries an out-of-bounds code (-1 right, -2 left)
-        c.ei = (int32_t)((uint32_t)xi + (uint32_t)yi * F.ey + c.zez);
-        int s = c.state;  // field.py:307-356
-        if ((xi == RIGHT_OUT_OF_BOUNDS || yi == RIGHT_OUT_OF_BOUNDS || zi == RIGHT_OUT_OF_BOUNDS) && s < PK_ERROROUTOFBOUNDS) s = PK_ERROROUTOFBOUNDS;
-        if (zi == LEFT_OUT_OF_BOUNDS && s < PK_ERRORTHROUGHSURFACE) s = PK_ERRORTHROUGHSURFACE;
-        // field.py:359-378: a non-finite barycentric coordinate makes the (wrapped-around) gather NaN, then everything is zeroed
-        const bool bad = !(isfinite(xsi) && isfinite(eta) && isfinite(zeta) && isfinite(tau));
-        if (bad && s < PK_ERRORINTERPOLATION) s = PK_ERRORINTERPOLATION;
-        c.state = s;
-        return;
+        if (PK_FAST_SEARCH2 && (fl & YX2) == YX2) {
+            fast_search2(T.lat, T.gny, F.y0, F.y1, y, c.hy, yi, eta, T.lon, T.gnx, F.x0, F.x1, x, c.hx, xi, xsi);
+        } else {
+            if (fl & FA_Y) fast_search<true>(T.lat, T.gny, F.y0, F.y1, y, c.hy, yi, eta, (fl & FA_NY2) != 0);
+            if (fl & FA_X) fast_search<true>(T.lon, T.gnx, F.x0, F.x1, x, c.hx, xi, xsi, (fl & FA_NX2) != 0);
+        }
+        // ravel_index (basegrid.py:83-152): the low 32 bits of the int64 sum are the wrapped 32-bit sum.  Of its three 32-bit products (v_mul_lo_u32
+        // each) one is left, and that one at full rate: ex == 1 (the fast path needs an x axis: pk_api.hip fill_fast, ravel_strides), zi * ez changes
+        // only with the depth memo (FCtx::zez), and for an in-bounds yi both yi and ey are below the 3840 nodes a 60 KB coordinate table holds, far
+        // inside the 24 bits of v_mad_u32_u24.  An out-of-bounds code (negative) takes the wrapped 32-bit product.
+        c.ei = (int32_t)((uint32_t)xi + __umul24((uint32_t)yi, F.ey) + c.zez);
+        if (__builtin_expect((xi | yi | zi) < 0, 0)) {  // some index carries an out-of-bounds code (-1 right, -2 left)
+            c.ei = (int32_t)((uint32_t)xi + (uint32_t)yi * F.ey + c.zez);
+            int s = c.state;  // field.py:307-356
+            if ((xi == RIGHT_OUT_OF_BOUNDS || yi == RIGHT_OUT_OF_BOUNDS || zi == RIGHT_OUT_OF_BOUNDS) && s < PK_ERROROUTOFBOUNDS) s = PK_ERROROUTOFBOUNDS;
+            if (zi == LEFT_OUT_OF_BOUNDS && s < PK_ERRORTHROUGHSURFACE) s = PK_ERRORTHROUGHSURFACE;
+            // field.py:359-378: a non-finite barycentric coordinate makes the (wrapped-around) gather NaN, then everything is zeroed
+            const bool bad = !(isfinite(xsi) && isfinite(eta) && isfinite(zeta) && isfinite(tau));
+            if (bad && s < PK_ERRORINTERPOLATION) s = PK_ERRORINTERPOLATION;
+            c.state = s;
+            return;
+        }
     }
     const bool lenT = tau > 0, lenZ = !(zeta <= 0);
     const int key = (ti << 2) | (lenT ? 2 : 0) | (lenZ ? 1 : 0);
+    // (a same-cell lane of the cell record formed no indices: past the out-of-bounds return they are the hints)
+    if (CR) { yi = c.hy; xi = c.hx; }
     const uint32_t b00 = ((uint32_t)zi * F.st_z + (uint32_t)yi * F.st_y + (uint32_t)xi) * (uint32_t)sizeof(FT);
     const double omt = 1 - tau, omz = 1 - zeta, omx = 1 - xsi, ome = 1 - eta;
     const double w00 = omx * ome, w01 = xsi * ome, w10 = omx * eta, w11 = xsi * eta;
     double uu = 0.0, vv = 0.0, ww = 0.0;
     if constexpr (LP != FAST_LP_OFF) {
         static_assert(!D3, "the level-pair arithmetic is the 2-D kernel's (z must not move)");
-        LpField fu, fv;
         // FAST_LP_CACHE: only the lanes whose cell, depth or level pair changed since their block was formed fetch (a divergent branch most
         // wave-evaluations of the odd stages skip and ~1.3 lanes take in the even ones); FAST_LP_REGS: every lane, every evaluation
         const bool miss = LP == FAST_LP_REGS || c.ei != c.bei || key != c.bkey;
-        if (LP == FAST_LP_REGS || __builtin_amdgcn_ballot_w64(miss) != 0) {
+        const bool some_miss = LP == FAST_LP_REGS || __builtin_amdgcn_ballot_w64(miss) != 0;
+        if (some_miss) {
             // the waterfall over the key, as below (level bases stay in SGPRs); a lane that hit starts as done
             for (bool done = !miss; !done;) {
                 const int uk = uniform_i32(key);
@@ -574,7 +669,7 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
                 c.bkey = key;
             }
         }
-        if (LP == FAST_LP_CACHE) {
+        if (LP == FAST_LP_CACHE && (!SPEC || some_miss)) {
             fu.p0 = T.blk[0]; fu.p1 = T.blk[FAST_WG_LP]; fu.d0 = T.blk[2 * FAST_WG_LP]; fu.d1 = T.blk[3 * FAST_WG_LP];
             fv.p0 = T.blk[4 * FAST_WG_LP]; fv.p1 = T.blk[5 * FAST_WG_LP]; fv.d0 = T.blk[6 * FAST_WG_LP]; fv.d1 = T.blk[7 * FAST_WG_LP];
         }
