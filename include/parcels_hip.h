@@ -613,6 +613,38 @@ int32_t pk_interact_merge(pk_ctx* ctx, double radius, double sphere_radius_m, in
 int32_t pk_interact_epilogue(pk_ctx* ctx, double endtime, double dt0, int64_t* steps, int64_t* state_counts, int64_t* next_evaluated,
                              int64_t* next_active);
 
+/* ---- particles per grid cell on the device-resident particle columns (csrc/pk_density.hip) ----------------------------------------------
+ * Parcels had ParticleSet.density(field_name, particle_val, relative, area_scale) through v3; v4 and the reference dropped it.  What this
+ * call replaces is what a script does instead: read `pset.x` / `pset.y` (two columns down, marked dirty, up again before the next
+ * execute), `grid.search(z, y, x)` with no guess on them (ParticleSet.populate_indices, particleset.py:252-262 -- or pk_search, which uploads
+ * the points once more) and `np.bincount(cell, weights=w, minlength=ncells)`.  Here the bound rows are read where they are, in whichever
+ * row order the cell sort left them; nothing is written to them.
+ *   cell of a row: the X / Y (FACE) indices the unguessed search of grid `grid_id` answers for its x, y -- and, with levels != 0, its Z index
+ *     for z -- ravelled over (max(zdim, 1) with levels,) max(ydim, 1), max(xdim, 1).  Without levels z is not read.
+ *   outside (counted in *n_outside, part of no cell): an index that is an error code (-1, -2, -3), or a non-finite x, y (z with levels) --
+ *     tested before the search; the reference's searchsorted would put a NaN into the last cell.
+ *   out, no weights: ncells int64 counts.  With weights: ncells float64 sums, per cell the weights of its rows added in ascending HOST row
+ *     order in float64 from 0.0 -- np.bincount's bits (the rows are sorted by (cell, host row), no float atomics).
+ *   weights: PK_DENSITY_W_EXTRA = the device Variable extra[weight_extra], whose elements are weight_dtype (the library moves those columns
+ *     as opaque 4- / 8-byte elements, so the caller says what they are); PK_DENSITY_W_HOST = weights_host, n float64 in host row order.
+ * ncells must be the product above (checked).  Needs bound particles, n < 2^32, no launch in flight. */
+#define PK_DENSITY_W_NONE 0
+#define PK_DENSITY_W_EXTRA 1
+#define PK_DENSITY_W_HOST 2
+#define PK_DENSITY_F32 0
+#define PK_DENSITY_F64 1
+#define PK_DENSITY_I32 2
+#define PK_DENSITY_I64 3
+typedef struct {
+    int64_t n_inside;   /* rows that fell into a cell */
+    int64_t n_atomics;  /* 64-bit atomic adds the count kernel issued (one per run of equal cells in a wavefront); 0 for weighted sums */
+    double bin_ms;      /* HIP events: key (+ count) kernel | radix sort of the (cell, host row) keys | per-cell sums */
+    double sort_ms;
+    double sum_ms;
+} pk_density_info_t;
+int32_t pk_particles_density(pk_ctx* ctx, int32_t grid_id, int32_t levels, int32_t weight_kind, int32_t weight_extra, int32_t weight_dtype,
+                             const double* weights_host, int64_t ncells, void* out, int64_t* n_outside, pk_density_info_t* info);
+
 /* achieved copy bandwidth probe (device-to-device float4 copy), GB/s; used as a measured roofline denominator */
 int32_t pk_measure_copy_bandwidth(pk_ctx* ctx, int64_t bytes, int32_t iters, double* gbps);
 

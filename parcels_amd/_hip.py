@@ -230,6 +230,14 @@ class NeighborsSphInfo(C.Structure):  # pk_neighbors_info_spherical_t
 
 PK_NEIGHBORS_NO_COINCIDENT = 1
 
+
+class DensityInfo(C.Structure):  # pk_density_info_t
+    _fields_ = [("n_inside", C.c_int64), ("n_atomics", C.c_int64), ("bin_ms", C.c_double), ("sort_ms", C.c_double), ("sum_ms", C.c_double)]
+
+
+PK_DENSITY_W_NONE, PK_DENSITY_W_EXTRA, PK_DENSITY_W_HOST = 0, 1, 2
+PK_DENSITY_F32, PK_DENSITY_F64, PK_DENSITY_I32, PK_DENSITY_I64 = 0, 1, 2, 3
+
 ABI_SYMBOLS = [
     "pk_abi_version",
     "pk_init",
@@ -287,6 +295,7 @@ ABI_SYMBOLS = [
     "pk_interact_attract",
     "pk_interact_merge",
     "pk_interact_epilogue",
+    "pk_particles_density",
     "pk_measure_copy_bandwidth",
     "pk_set_option",
     "pk_upload_stats",
@@ -409,6 +418,8 @@ def load():
     lib.pk_interact_merge.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_double)]
     lib.pk_interact_epilogue.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                          C.POINTER(C.c_int64)]
+    lib.pk_particles_density.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.POINTER(C.c_int64), C.POINTER(DensityInfo)]
     if lib.pk_abi_version() != PK_ABI_VERSION:
         raise HipLibraryError(f"ABI version mismatch: library {lib.pk_abi_version()}, binding {PK_ABI_VERSION}")
     _lib = lib

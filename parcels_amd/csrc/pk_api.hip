@@ -20,6 +20,7 @@
 #include "pk_hashbuild.h"
 #include "pk_neighbors.h"
 #include "pk_interact.h"
+#include "pk_density.h"
 #include "pk_host_stage.h"
 #include "pk_kernels.h"
 #include "pk_ux.h"
@@ -3264,6 +3265,44 @@ int32_t pk_interact_merge(pk_ctx* ctx, double radius, double sphere_radius_m, in
     if (interact_merge(ctx->nbr, ctx->compute, interact_columns(ctx), ctx->dev.extra[mass_extra], ctx->dev.extra_f32[mass_extra], radius, sphere_radius_m,
                        use_z, phase_ms, &msg))
         return ctx->fail(msg);
+    return 0;
+}
+
+// ---- particles per grid cell on the device-resident columns (pk_density.hip) ------------------------------
+int32_t pk_particles_density(pk_ctx* ctx, int32_t grid_id, int32_t levels, int32_t weight_kind, int32_t weight_extra, int32_t weight_dtype,
+                             const double* weights_host, int64_t ncells, void* out, int64_t* n_outside, pk_density_info_t* info) {
+    if (!ctx || !out || !n_outside) return -2;
+    if (!ctx->bound) return ctx->fail("pk_particles_density: no particles bound");
+    if (ctx->in_flight) return ctx->fail("pk_particles_density: a launch is in flight (call pk_execute_end)");
+    if (grid_id < 0 || grid_id >= (int)ctx->grids.size()) return ctx->fail("pk_particles_density: unknown grid id");
+    if (ncells <= 0) return ctx->fail("pk_particles_density: ncells must be positive");
+    DensityWeights w;
+    w.kind = weight_kind;
+    w.dtype = weight_dtype;
+    if (weight_kind == PK_DENSITY_W_EXTRA) {
+        if (weight_extra < 0 || weight_extra >= PK_MAX_EXTRA || !ctx->dev.extra[weight_extra])
+            return ctx->fail("pk_particles_density: weight_extra must name a device Variable of the bound particles (pk_particles_desc.extra)");
+        if (weight_dtype < PK_DENSITY_F32 || weight_dtype > PK_DENSITY_I64)
+            return ctx->fail("pk_particles_density: weight_dtype must be PK_DENSITY_F32, _F64, _I32 or _I64");
+        const bool four = weight_dtype == PK_DENSITY_F32 || weight_dtype == PK_DENSITY_I32;
+        if (four != (ctx->dev.extra_f32[weight_extra] != 0))
+            return ctx->fail("pk_particles_density: weight_dtype does not have the element size of the device Variable");
+        w.dev = ctx->dev.extra[weight_extra];
+    } else if (weight_kind == PK_DENSITY_W_HOST) {
+        if (!weights_host && ctx->dev.n > 0) return ctx->fail("pk_particles_density: PK_DENSITY_W_HOST needs weights_host");
+        w.host = weights_host;
+    } else if (weight_kind != PK_DENSITY_W_NONE) {
+        return ctx->fail("pk_particles_density: weight_kind must be PK_DENSITY_W_NONE, _EXTRA or _HOST");
+    }
+    PK_HIP(ctx, hipSetDevice(ctx->device));
+    const DParticles& d = ctx->dev;  // the column set that is current (a launch leaves what it wrote there)
+    DensityColumns c;
+    c.n = d.n;
+    c.f32 = d.spatial_f32;
+    c.x = d.x; c.y = d.y; c.z = d.z;
+    c.perm = ctx->has_perm ? ctx->d_perm : nullptr;
+    std::string msg;
+    if (density_run(ctx->compute, ctx->grids[grid_id].d, c, levels, w, ncells, out, n_outside, info, &msg)) return ctx->fail(msg);
     return 0;
 }
 

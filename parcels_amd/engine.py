@@ -1218,6 +1218,60 @@ def _engine_search(self, igrid, z, y, x):
 
 DeviceEngine.search = _engine_search
 
+_DENSITY_DTYPES = {np.dtype(np.float32): _hip.PK_DENSITY_F32, np.dtype(np.float64): _hip.PK_DENSITY_F64,
+                   np.dtype(np.int32): _hip.PK_DENSITY_I32, np.dtype(np.int64): _hip.PK_DENSITY_I64}
+
+
+def density_shape(grid, levels: bool) -> tuple:
+    """Shape of a density map over the cells of `grid`: the ravel dims of `ei` (get_axis_dim), Z only with `levels`; an axis the grid does
+    not have -- or one of length 1, whose only index is 0 -- contributes 1."""
+    dim = lambda a: max(int(grid.get_axis_dim(a)), 1) if a in grid.axes else 1  # noqa: E731
+    lateral = (dim("FACE"),) if isinstance(grid, UxGrid) else (dim("Y"), dim("X"))
+    return ((dim("Z"),) if levels else ()) + lateral
+
+
+def _engine_density(self, data, igrid, levels=False, weight_var=None, weight_host=None):
+    """Particles (or the sum of a weight) per cell of grid `igrid`, binned on the device-resident columns of `data` (pk_particles_density).
+    The rows are made current the way execute does it -- columns the host touched are uploaded, a set that is not resident is bound and
+    uploaded -- and then only read: nothing is marked stale or dirty, no particle column is downloaded, the row order of the cell sort
+    stays.  weight_var: a particle Variable (a device-resident one is read in place, any other is current on the host); weight_host: float64
+    weights in host row order.  Returns (flat map, n_outside, info dict)."""
+    grid = self.grids[igrid]
+    shape = density_shape(grid, levels)
+    ncells = int(np.prod(shape))
+    n = len(data.raw("particle_id") if isinstance(data, LazyColumns) else data["particle_id"])
+    weighted = weight_var is not None or weight_host is not None
+    out = np.zeros(ncells, np.float64 if weighted else np.int64)
+    info = _hip.DensityInfo()
+    n_out = C.c_int64(0)
+    if n == 0:
+        return out, 0, {"n_inside": 0, "n_atomics": 0, "bin_ms": 0.0, "sort_ms": 0.0, "sum_ms": 0.0}
+    if not (isinstance(data, LazyColumns) and data.resident() and data._engine is self):
+        # about to be bound: the device Variables of the last kernel list may belong to another ParticleSet's class (execute sets them
+        # from its kernels before it binds; there is no kernel here)
+        self.device_variables = [v for v in self.device_variables if v in data]
+    if isinstance(data, LazyColumns) and hasattr(self, "attach"):
+        self.attach(data)
+    else:
+        self.bind_particles(data)
+        self.h2d()
+    kind, extra, code, host = _hip.PK_DENSITY_W_NONE, 0, 0, None
+    if weight_var is not None:
+        raw = data.raw(weight_var) if isinstance(data, LazyColumns) else data[weight_var]
+        if weight_var in getattr(self, "_bound_devvars", ()):
+            kind, extra, code = _hip.PK_DENSITY_W_EXTRA, self._bound_devvars.index(weight_var), _DENSITY_DTYPES[raw.dtype]
+        else:  # a host-only Variable: no launch writes it, its host array is current
+            weight_host = raw
+    if weight_host is not None:
+        kind = _hip.PK_DENSITY_W_HOST
+        host = np.ascontiguousarray(weight_host, dtype=np.float64)  # (np.bincount casts its weights to double the same way)
+    self.ctx.check(self.lib.pk_particles_density(self.ctx.handle, int(self.grid_ids[igrid]), int(bool(levels)), kind, int(extra), int(code), _ptr(host),
+                                                 ncells, _ptr(out), C.byref(n_out), C.byref(info)), "pk_particles_density")
+    return out, int(n_out.value), {k: getattr(info, k) for k, _ in _hip.DensityInfo._fields_}
+
+
+DeviceEngine.density = _engine_density
+
 
 def raise_particle_errors(data: dict, first_code=None):
     """kernel.py:236-245: raise for the first error code present, in ErrorsToThrow order.  ``first_code`` (a sharded ParticleSet): the

@@ -8,7 +8,8 @@ import warnings
 
 import numpy as np
 
-from .columns import LazyColumns
+from ._hip import COLUMN_BITS as COLUMN_BITS_NAMES
+from .columns import LazyColumns, readonly
 from .field import to_seconds
 from .kernel import Kernel
 from .particle import Particle, create_particle_data
@@ -265,6 +266,80 @@ class ParticleSet:
         eng = self._engine()
         for i in range(len(self.fieldset.gridset)):
             self._data["ei"][:, i] = eng.search(i, self._data["z"], self._data["y"], self._data["x"])
+
+    def density(self, field=None, particle_val=None, relative=False, area_scale=False, *, levels=False, return_outside=False):
+        """Particles per cell of a field's grid, binned on the GPU from the device-resident columns (Parcels v3's ParticleSet.density; v4
+        and the reference have no such method).
+
+        ``field``: a Field, a VectorField, a field name or None (``fieldset.U``); the map covers the cells of its grid: shape
+        ``(ydim, xdim)`` on an XGrid, ``(n_face,)`` on a UxGrid, with the vertical dimension in front when ``levels=True``.  A particle
+        counts in the cell that ``grid.search(z, y, x)`` without a guess answers for its position (what ``populate_indices`` stores); without
+        ``levels`` only the horizontal indices matter.  A particle whose search answers an error code, or -- a deliberate difference from
+        the reference, whose ``searchsorted`` puts a NaN into the last cell -- whose ``x``, ``y`` (``z`` with ``levels``) is not finite, is
+        *outside* and in no cell.
+
+        ``particle_val``: None for counts (int64), else the name of a float32 / float64 / int32 / int64 particle Variable or an array of
+        ``len(pset)`` weights in row order; the map is then float64 and equals ``np.bincount(cell, weights=w, minlength=ncells)`` bit for bit
+        (per cell the weights are added in ascending row order).  ``relative``: divide by the sum of the map (zeros when it is 0);
+        ``area_scale``: divide by ``grid.cell_areas()``; ``return_outside``: return ``(map, n_outside)``.
+
+        The call only reads the particles: columns the host changed are uploaded as ``execute`` would, nothing is downloaded or marked,
+        and ``execute -> density -> execute`` gives the bits of ``execute -> execute``."""
+        from .engine import density_shape
+        from .field import Field, VectorField
+
+        if self._shard is not None:
+            raise NotImplementedError("ParticleSet.density on a sharded (multi-process) ParticleSet: the per-rank maps are not summed over the ranks yet")
+        fs = self.fieldset
+        if field is None:
+            field = "U"
+        if isinstance(field, str):
+            if field not in fs.fields:
+                raise ValueError(f"density: the FieldSet has no field {field!r}")
+            field = fs.fields[field]
+        elif not isinstance(field, (Field, VectorField)):
+            raise TypeError(f"density: field must be a Field, a VectorField, a field name or None. Got {type(field).__name__}")
+        grids = fs.gridset
+        if fs.fields.get(field.name) is not field or not any(g is field.grid for g in grids):
+            raise ValueError(f"density: field {field.name!r} is not a field of this ParticleSet's FieldSet")
+        igrid = next(i for i, g in enumerate(grids) if g is field.grid)
+        n = len(self)
+        weight_var = weight_host = None
+        if isinstance(particle_val, str):
+            var = next((v for v in self._pclass.variables if v.name == particle_val), None)
+            if var is None:
+                raise ValueError(f"density: the particle class has no Variable {particle_val!r}")
+            d = self._data
+            dt = (d.raw(particle_val) if isinstance(d, LazyColumns) else d[particle_val]).dtype
+            if dt not in (np.float32, np.float64, np.int32, np.int64) or particle_val == "ei":
+                raise TypeError(f"density: Variable {particle_val!r} is {dt}; weights must be float32, float64, int32 or int64")
+            weight_var = particle_val
+        elif particle_val is not None:
+            w = np.asarray(particle_val)
+            if w.ndim != 1 or w.shape[0] != n:
+                raise ValueError(f"density: particle_val has shape {w.shape}, expected ({n},) -- one weight per particle in row order")
+            if w.dtype not in (np.float32, np.float64, np.int32, np.int64):
+                raise TypeError(f"density: particle_val is {w.dtype}; weights must be float32, float64, int32 or int64")
+            weight_host = w
+        shape = density_shape(field.grid, bool(levels))
+        areas = None
+        if area_scale:
+            areas = np.asarray(field.grid.cell_areas(), dtype=np.float64)
+        eng = self._engine()
+        if getattr(eng, "comm", None) is not None:
+            raise NotImplementedError("ParticleSet.density in a multi-process run: the per-rank maps are not summed over the ranks yet")
+        if weight_var in COLUMN_BITS_NAMES:  # a built-in column (t, dt, x ...): lives on the device as a column of its own, read through the mirror
+            weight_host, weight_var = readonly(self._data)[weight_var], None
+        flat, n_outside, info = eng.density(self._data, igrid, levels=bool(levels), weight_var=weight_var, weight_host=weight_host)
+        self._last_density_info = info
+        out = flat.reshape(shape)
+        if relative:
+            out = out.astype(np.float64)
+            total = out.sum()
+            out = out / total if total != 0 else np.zeros_like(out)
+        if areas is not None:
+            out = out / (areas if not levels else areas[None])
+        return (out, n_outside) if return_outside else out
 
     # -- the outer time loop (particleset.py:355-470) ------------------------------------------------------------
     def execute(self, kernels, dt, endtime=None, runtime=None, output_file=None, verbose_progress=False):

@@ -109,6 +109,20 @@ class UxGrid:
         ei = np.asarray(ei)
         return {"Z": ei // dims[1], "FACE": ei % dims[1]}
 
+    def cell_areas(self) -> np.ndarray:
+        """Area of every triangle, shape ``(n_face,)``.  Flat mesh: the planar area in mesh units squared.  Spherical mesh: the nodes are
+        put on the sphere of radius ``deg2m * 180 / pi`` and the area of the planar triangle through them is taken, in m**2 -- the *chordal*
+        approximation of the spherical triangle (low by about (edge angle)**2 / 12 relative)."""
+        from .xgrid import _chordal_area, _sphere_xyz
+
+        m = self.uxgrid
+        f = m.face_node_connectivity
+        if self._mesh.is_spherical():
+            xyz = _sphere_xyz(m.node_lon, m.node_lat, self.deg2m * 180.0 / np.pi)
+            return _chordal_area([xyz[f[:, k]] for k in range(3)])
+        x, y = m.node_lon[f], m.node_lat[f]
+        return np.abs(0.5 * ((x[:, 1] - x[:, 0]) * (y[:, 2] - y[:, 0]) - (y[:, 1] - y[:, 0]) * (x[:, 2] - x[:, 0])))
+
     def get_spatial_hash(self) -> SpatialHash:
         if self._spatialhash is None:
             self._spatialhash = SpatialHash.from_triangles(self.uxgrid.node_lon, self.uxgrid.node_lat, self.uxgrid.face_node_connectivity,
