@@ -24,12 +24,28 @@ PK_KERNEL_SAMPLE_FIELD = 10
 PK_KERNEL_ADVECTION_RK2_3D_CROCO = 11
 PK_KERNEL_SAMPLE_SIGMA_CROCO = 12
 PK_EVAL_MASKED = 0x10000  # pk_eval: or'ed into out_state where the value was zeroed for an out-of-bounds index
-PK_COL_EXTRA0 = 0x1000
-PK_COL_T, PK_COL_Z, PK_COL_Y, PK_COL_X, PK_COL_DT, PK_COL_STATE, PK_COL_PARTICLE_ID = 0x001, 0x002, 0x004, 0x008, 0x080, 0x200, 0x800
 PK_COMM_ID_BYTES = 128
 PK_OP_MIN, PK_OP_MAX, PK_OP_SUM = 0, 1, 2
-COLUMN_BITS = {n: 1 << i for i, n in enumerate(
-    ["t", "z", "y", "x", "dz", "dy", "dx", "dt", "next_dt", "state", "ei", "particle_id"])}
+# The named particle columns of pk_particles_desc, in the order of their PK_COL_* mask bits (include/parcels_hip.h):
+# (name, bit, dtype kind, one value per grid).  Kind "spatial" is float32 or float64 by pk_particles_desc.spatial_dtype; the optional
+# next_dt is float64 on the device whatever the host Variable is.  The user columns follow from bit PK_COL_EXTRA0 on.
+COLUMNS = (
+    ("t", 0x001, "f64", False),
+    ("z", 0x002, "spatial", False),
+    ("y", 0x004, "spatial", False),
+    ("x", 0x008, "spatial", False),
+    ("dz", 0x010, "spatial", False),
+    ("dy", 0x020, "spatial", False),
+    ("dx", 0x040, "spatial", False),
+    ("dt", 0x080, "f64", False),
+    ("next_dt", 0x100, "f64", False),
+    ("state", 0x200, "i32", False),
+    ("ei", 0x400, "i32", True),
+    ("particle_id", 0x800, "i64", False),
+)
+COLUMN_BITS = {name: bit for name, bit, _, _ in COLUMNS}
+globals().update({f"PK_COL_{name.upper()}": bit for name, bit in COLUMN_BITS.items()})  # PK_COL_T ... PK_COL_PARTICLE_ID
+PK_COL_EXTRA0 = 1 << len(COLUMNS)
 
 
 class HipLibraryError(RuntimeError):

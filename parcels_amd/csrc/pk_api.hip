@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -52,6 +53,45 @@ struct HostField {
     std::vector<int32_t> slot_pending;  // level being copied into the slot (async upload), -1 = none
     std::vector<uint64_t> slot_gen;     // stamp of the last upload into the slot (pk_ctx::upload_counter): tells a re-upload of the same level apart
 };
+
+// ---- the particle columns: ONE table -------------------------------------------------------------------
+// Every operation on the particle columns (allocate, free, copy, sort, compact, checkpoint, snapshot, exchange) walks this list, in this
+// order: it is the bit order of the PK_COL_* masks, the layout of the checkpoint buffer and the order of the exchange.
+//   X(member of pk_particles_desc and of DParticles, mask bit, element bytes, `ngrids` values per row, exists only where the host binds one)
+// COL_SPATIAL: 4 or 8 bytes by pk_particles_desc::spatial_dtype.  Behind these rows come the PK_MAX_EXTRA user columns (index
+// PK_COL_EXTRA_FIRST + k, bit PK_COL_EXTRA0 << k, 4 or 8 bytes by extra_dtype[k], optional, no launch writes them) and the device-only
+// `iter` (index PK_NCOLS of particle_columns: no bit, 4 bytes, written by a launch).
+constexpr int COL_SPATIAL = 0;
+// the columns an advection launch writes: with `iter`, the members of DPOut (pk_device.h)
+#define PK_LAUNCH_COLUMNS(X)                       \
+    X(t, PK_COL_T, 8, false, false)                \
+    X(z, PK_COL_Z, COL_SPATIAL, false, false)      \
+    X(y, PK_COL_Y, COL_SPATIAL, false, false)      \
+    X(x, PK_COL_X, COL_SPATIAL, false, false)      \
+    X(dz, PK_COL_DZ, COL_SPATIAL, false, false)    \
+    X(dy, PK_COL_DY, COL_SPATIAL, false, false)    \
+    X(dx, PK_COL_DX, COL_SPATIAL, false, false)    \
+    X(dt, PK_COL_DT, 8, false, false)              \
+    X(next_dt, PK_COL_NEXT_DT, 8, false, true)     \
+    X(state, PK_COL_STATE, 4, false, false)        \
+    X(ei, PK_COL_EI, 4, true, false)
+#define PK_COLUMNS(X) PK_LAUNCH_COLUMNS(X) X(particle_id, PK_COL_PARTICLE_ID, 8, false, false)
+
+struct ColInfo { uint32_t bit; int elem; bool per_grid, optional; };
+#define X(m, bit, elem, per_grid, optional) {bit, elem, per_grid, optional},
+constexpr ColInfo PK_COL_INFO[] = {PK_COLUMNS(X)};
+#undef X
+#define X(m, bit, elem, per_grid, optional) | bit
+constexpr uint32_t PK_LAUNCH_MASK = 0u PK_LAUNCH_COLUMNS(X);
+#undef X
+constexpr int PK_COL_EXTRA_FIRST = (int)(sizeof(PK_COL_INFO) / sizeof(PK_COL_INFO[0]));
+constexpr int PK_NCOLS = PK_COL_EXTRA_FIRST + PK_MAX_EXTRA;
+constexpr bool col_bits_in_table_order() {
+    for (int k = 0; k < PK_COL_EXTRA_FIRST; k++)
+        if (PK_COL_INFO[k].bit != 1u << k) return false;
+    return PK_COL_EXTRA0 == 1u << PK_COL_EXTRA_FIRST;
+}
+static_assert(col_bits_in_table_order(), "the table lists the columns in the bit order of the PK_COL_* masks (parcels_hip.h)");
 
 constexpr int PK_STAGE_BUFFERS = 3;  // pinned staging chunks of the level stream (see stage_acquire)
 
@@ -164,8 +204,8 @@ struct pk_ctx {
     // asynchronous write-out snapshots (pk_particles_snapshot_begin / _wait): two sets of device staging columns (host row order)
     // + pinned host columns, so that the D2H and the encode of interval k overlap the launch of interval k+1
     struct Snapshot {
-        void* dev[12 + PK_MAX_EXTRA] = {};
-        void* host[12 + PK_MAX_EXTRA] = {};
+        void* dev[PK_NCOLS] = {};
+        void* host[PK_NCOLS] = {};
         int64_t capacity = 0;  // rows the buffers were sized for
         int64_t n = 0;         // rows of the snapshot in flight
         uint32_t mask = 0;
@@ -646,6 +686,7 @@ static int32_t upload(pk_ctx* ctx, HostGrid& g, const T* host, size_t n, const T
     return 0;
 }
 
+static void free_particles(pk_ctx* ctx);  // the particles section
 
 // ---- context -------------------------------------------------------------------------------------------
 extern "C" {
@@ -736,7 +777,7 @@ int32_t pk_upload_stats(pk_ctx* ctx, double* out4) {
 static void free_snapshots(pk_ctx* ctx) {
     for (auto& sn : ctx->snap) {
         if (sn.in_flight && sn.done) (void)hipEventSynchronize(sn.done);
-        for (int k = 0; k < 12 + PK_MAX_EXTRA; k++) {
+        for (int k = 0; k < PK_NCOLS; k++) {
             if (sn.dev[k]) (void)hipFree(sn.dev[k]);
             if (sn.host[k]) (void)hipHostFree(sn.host[k]);
             sn.dev[k] = sn.host[k] = nullptr;
@@ -744,35 +785,6 @@ static void free_snapshots(pk_ctx* ctx) {
         sn.capacity = 0;
         sn.in_flight = false;
     }
-}
-
-static void free_particles(pk_ctx* ctx) {
-    if (ctx->d_chk) (void)hipFree(ctx->d_chk);
-    ctx->d_chk = nullptr;
-    ctx->chk_bytes = 0;
-    ctx->chk_valid = false;
-    void* cols[] = {ctx->dev.t,  ctx->dev.z,  ctx->dev.y,       ctx->dev.x,     ctx->dev.dz, ctx->dev.dy,
-                    ctx->dev.dx, ctx->dev.dt, ctx->dev.next_dt, ctx->dev.state, ctx->dev.ei, ctx->dev.particle_id, ctx->dev.iter, ctx->alt.iter};
-    ctx->rerun_valid = false;
-    for (void* p : cols)
-        if (p) (void)hipFree(p);
-    void* alts[] = {ctx->alt.t,  ctx->alt.z,  ctx->alt.y,       ctx->alt.x,     ctx->alt.dz, ctx->alt.dy,
-                    ctx->alt.dx, ctx->alt.dt, ctx->alt.next_dt, ctx->alt.state, ctx->alt.ei, ctx->alt.particle_id,
-                    ctx->d_perm, ctx->d_perm_alt, ctx->d_keys, ctx->d_keys_alt, ctx->d_idx, ctx->d_idx_alt, ctx->d_sort_tmp};
-    for (void* p : alts)
-        if (p) (void)hipFree(p);
-    for (int k = 0; k < PK_MAX_EXTRA; k++) {
-        if (ctx->dev.extra[k]) (void)hipFree(ctx->dev.extra[k]);
-        if (ctx->alt.extra[k]) (void)hipFree(ctx->alt.extra[k]);
-    }
-    ctx->d_perm = ctx->d_perm_alt = nullptr;
-    ctx->d_keys = ctx->d_keys_alt = nullptr;
-    ctx->d_idx = ctx->d_idx_alt = nullptr;
-    ctx->d_sort_tmp = nullptr;
-    ctx->sort_tmp_bytes = 0;
-    ctx->dev = DParticles{};
-    ctx->alt = DParticles{};
-    ctx->capacity = 0;
 }
 
 int32_t pk_destroy(pk_ctx* ctx) {
@@ -1324,131 +1336,104 @@ int32_t pk_field_slots(pk_ctx* ctx, int32_t field_id, int32_t* levels, int32_t* 
     return 0;
 }
 
-// ---- particles -----------------------------------------------------------------------------------------
-static size_t spatial_size(const pk_ctx* ctx) { return ctx->host.spatial_dtype == PK_F32 ? 4 : 8; }
-
-int32_t pk_particles_bind(pk_ctx* ctx, const pk_particles_desc* host) {
-    if (!ctx || !host) return -2;
-    if (host->n < 0 || host->ngrids < 1 || host->ngrids > PK_MAX_GRIDS) return ctx->fail("bad particle descriptor");
-    if (host->n > 0 && (!host->t || !host->z || !host->y || !host->x || !host->dz || !host->dy || !host->dx || !host->dt ||
-                        !host->state || !host->ei || !host->particle_id))
-        return ctx->fail("particle columns must not be NULL");
-    PK_HIP(ctx, hipSetDevice(ctx->device));
-    if (host->n_extra < 0 || host->n_extra > PK_MAX_EXTRA) return ctx->fail("bad number of extra particle columns");
-    bool extra_changed = host->n_extra != ctx->host.n_extra;
-    for (int k = 0; k < host->n_extra && !extra_changed; k++) extra_changed = host->extra_dtype[k] != ctx->host.extra_dtype[k];
-    for (int k = 0; k < host->n_extra; k++) {
-        if (host->extra_dtype[k] != PK_F32 && host->extra_dtype[k] != PK_F64) return ctx->fail("extra particle columns must be PK_F32 or PK_F64");
-        if (host->n > 0 && !host->extra[k]) return ctx->fail("particle columns must not be NULL");
-    }
-    const bool realloc_needed = !ctx->bound || host->n > ctx->capacity || host->ngrids != ctx->host.ngrids || extra_changed ||
-                                host->spatial_dtype != ctx->host.spatial_dtype || (host->next_dt != nullptr) != (ctx->dev.next_dt != nullptr);
-    ctx->host = *host;
-    if (realloc_needed) {
-        free_particles(ctx);
-        const int64_t cap = std::max<int64_t>(host->n, 1);
-        const size_t ss = spatial_size(ctx);
-        PK_HIP(ctx, hipMalloc((void**)&ctx->dev.t, cap * 8));
-        PK_HIP(ctx, hipMalloc(&ctx->dev.z, cap * ss));
-        PK_HIP(ctx, hipMalloc(&ctx->dev.y, cap * ss));
-        PK_HIP(ctx, hipMalloc(&ctx->dev.x, cap * ss));
-        PK_HIP(ctx, hipMalloc(&ctx->dev.dz, cap * ss));
-        PK_HIP(ctx, hipMalloc(&ctx->dev.dy, cap * ss));
-        PK_HIP(ctx, hipMalloc(&ctx->dev.dx, cap * ss));
-        PK_HIP(ctx, hipMalloc((void**)&ctx->dev.dt, cap * 8));
-        if (host->next_dt) PK_HIP(ctx, hipMalloc((void**)&ctx->dev.next_dt, cap * 8));
-        PK_HIP(ctx, hipMalloc((void**)&ctx->dev.state, cap * 4));
-        PK_HIP(ctx, hipMalloc((void**)&ctx->dev.ei, cap * 4 * host->ngrids));
-        PK_HIP(ctx, hipMalloc((void**)&ctx->dev.particle_id, cap * 8));
-        PK_HIP(ctx, hipMalloc((void**)&ctx->dev.iter, cap * 4));
-        for (int k = 0; k < host->n_extra; k++) PK_HIP(ctx, hipMalloc(&ctx->dev.extra[k], cap * (host->extra_dtype[k] == PK_F32 ? 4 : 8)));
-        ctx->capacity = cap;
-    }
-    for (int k = 0; k < PK_MAX_EXTRA; k++) ctx->dev.extra_f32[k] = ctx->alt.extra_f32[k] = (k < host->n_extra && host->extra_dtype[k] == PK_F32);
-    ctx->has_perm = false;
-    ctx->rerun_valid = false;
-    ctx->chk_valid = false;
-    ctx->dev.n = host->n;
-    ctx->dev.ngrids = host->ngrids;
-    ctx->dev.spatial_f32 = host->spatial_dtype == PK_F32;
-    ctx->bound = true;
-    return 0;
-}
-
 }  // extern "C" (helpers with C++ linkage follow)
 
-struct ColRef {
-    void* h;
-    void* d;
-    void* a;  // alt/staging device column
-    size_t elem;
-    int width;
-};
+// ---- particles -----------------------------------------------------------------------------------------
+static size_t spatial_size(const pk_ctx* ctx) { return ctx->host.spatial_dtype == PK_F32 ? 4 : 8; }
+// Every per-column operation below derives from the table at the top of this file (PK_COLUMNS).  The column pointers of a descriptor or of a device column set, in table order: named columns, then the extras
+template <class S>
+static std::array<void*, PK_NCOLS> column_pointers(const S& s) {
+    std::array<void*, PK_NCOLS> p{};
+    int k = 0;
+#define X(m, bit, elem, per_grid, optional) p[k++] = s.m;
+    PK_COLUMNS(X)
+#undef X
+    for (int e = 0; e < PK_MAX_EXTRA; e++) p[k++] = s.extra[e];
+    return p;
+}
+// ... and the way back: every column member of `s` <- p[0 .. n_cols), n_cols = PK_COL_EXTRA_FIRST (named columns only) or PK_NCOLS
+template <class S>
+static void set_column_pointers(S& s, void* const* p, int n_cols) {
+    int k = 0;
+#define X(m, bit, elem, per_grid, optional) s.m = static_cast<decltype(s.m)>(p[k++]);
+    PK_COLUMNS(X)
+#undef X
+    for (; k < n_cols; k++) s.extra[k - PK_COL_EXTRA_FIRST] = p[k];
+}
 
+// one column: host array, device column, alt/staging device column; launch_output: an advection launch writes it (pk_device.h: DPOut)
+struct ColRef { void *h, *d, *a; size_t elem; int width; bool launch_output; };
 static std::vector<ColRef> particle_columns(pk_ctx* ctx) {
-    const size_t ss = spatial_size(ctx);
-    const int ng = ctx->host.ngrids;
-    return {
-        {ctx->host.t, ctx->dev.t, ctx->alt.t, 8, 1},          {ctx->host.z, ctx->dev.z, ctx->alt.z, ss, 1},
-        {ctx->host.y, ctx->dev.y, ctx->alt.y, ss, 1},          {ctx->host.x, ctx->dev.x, ctx->alt.x, ss, 1},
-        {ctx->host.dz, ctx->dev.dz, ctx->alt.dz, ss, 1},       {ctx->host.dy, ctx->dev.dy, ctx->alt.dy, ss, 1},
-        {ctx->host.dx, ctx->dev.dx, ctx->alt.dx, ss, 1},       {ctx->host.dt, ctx->dev.dt, ctx->alt.dt, 8, 1},
-        {ctx->host.next_dt, ctx->dev.next_dt, ctx->alt.next_dt, 8, 1},
-        {ctx->host.state, ctx->dev.state, ctx->alt.state, 4, 1},
-        {ctx->host.ei, ctx->dev.ei, ctx->alt.ei, 4, ng},
-        {ctx->host.particle_id, ctx->dev.particle_id, ctx->alt.particle_id, 8, 1},
-        {ctx->host.extra[0], ctx->dev.extra[0], ctx->alt.extra[0], (size_t)(ctx->dev.extra_f32[0] ? 4 : 8), 1},
-        {ctx->host.extra[1], ctx->dev.extra[1], ctx->alt.extra[1], (size_t)(ctx->dev.extra_f32[1] ? 4 : 8), 1},
-        {ctx->host.extra[2], ctx->dev.extra[2], ctx->alt.extra[2], (size_t)(ctx->dev.extra_f32[2] ? 4 : 8), 1},
-        {ctx->host.extra[3], ctx->dev.extra[3], ctx->alt.extra[3], (size_t)(ctx->dev.extra_f32[3] ? 4 : 8), 1},
-        {ctx->host.extra[4], ctx->dev.extra[4], ctx->alt.extra[4], (size_t)(ctx->dev.extra_f32[4] ? 4 : 8), 1},
-        {ctx->host.extra[5], ctx->dev.extra[5], ctx->alt.extra[5], (size_t)(ctx->dev.extra_f32[5] ? 4 : 8), 1},
-        {ctx->host.extra[6], ctx->dev.extra[6], ctx->alt.extra[6], (size_t)(ctx->dev.extra_f32[6] ? 4 : 8), 1},
-        {ctx->host.extra[7], ctx->dev.extra[7], ctx->alt.extra[7], (size_t)(ctx->dev.extra_f32[7] ? 4 : 8), 1},
-        {nullptr, ctx->dev.iter, ctx->alt.iter, 4, 1},  // device only (index PK_NCOLS: beyond the column masks of the ABI)
-    };
+    const auto h = column_pointers(ctx->host), d = column_pointers(ctx->dev), a = column_pointers(ctx->alt);
+    std::vector<ColRef> cols;
+    for (int k = 0; k < PK_COL_EXTRA_FIRST; k++) {
+        const ColInfo& c = PK_COL_INFO[k];
+        cols.push_back({h[k], d[k], a[k], c.elem == COL_SPATIAL ? spatial_size(ctx) : (size_t)c.elem, c.per_grid ? ctx->host.ngrids : 1,
+                        (c.bit & PK_LAUNCH_MASK) != 0});
+    }
+    for (int k = PK_COL_EXTRA_FIRST; k < PK_NCOLS; k++)
+        cols.push_back({h[k], d[k], a[k], (size_t)(ctx->dev.extra_f32[k - PK_COL_EXTRA_FIRST] ? 4 : 8), 1, false});
+    cols.push_back({nullptr, ctx->dev.iter, ctx->alt.iter, 4, 1, true});  // device only (index PK_NCOLS: beyond the column masks of the ABI)
+    return cols;
 }
-constexpr int PK_NCOLS = 12 + PK_MAX_EXTRA;
-static_assert(PK_MAX_EXTRA == 8, "particle_columns lists eight extra columns");
 
-// exchange the two column sets (sizes / flags stay): after the cell sort and the compaction wrote the new order into `alt`
-static void swap_column_sets(pk_ctx* ctx) {
+// Allocate the columns of one set (`dev` or `alt`) for `cap` rows: the optional ones where the bound host descriptor has them (pk_particles_bind
+// and pk_particles_compact keep `dev` and the host descriptor alike in that).  What was allocated before a failure stays in `set` for free_particles.
+static int32_t alloc_column_set(pk_ctx* ctx, DParticles& set, int64_t cap) {
+    const std::vector<ColRef> cols = particle_columns(ctx);
+    void* p[PK_NCOLS + 1] = {};  // (the last one: `iter`)
+    hipError_t e = hipSuccess;
+    for (int k = 0; k <= PK_NCOLS && e == hipSuccess; k++) {
+        const bool present = k == PK_NCOLS || (k >= PK_COL_EXTRA_FIRST ? k - PK_COL_EXTRA_FIRST < ctx->host.n_extra : !PK_COL_INFO[k].optional || cols[k].h);
+        if (present) e = hipMalloc(&p[k], (size_t)cap * cols[k].elem * cols[k].width);
+    }
+    set_column_pointers(set, p, PK_NCOLS);
+    set.iter = static_cast<int32_t*>(p[PK_NCOLS]);
+    return e == hipSuccess ? 0 : ctx->fail("hipMalloc of a particle column", e);
+}
+
+static void free_particles(pk_ctx* ctx) {
+    if (ctx->d_chk) (void)hipFree(ctx->d_chk);
+    ctx->d_chk = nullptr;
+    ctx->chk_bytes = 0;
+    ctx->chk_valid = false;
+    ctx->rerun_valid = false;
+    for (const ColRef& c : particle_columns(ctx)) {
+        if (c.d) (void)hipFree(c.d);
+        if (c.a) (void)hipFree(c.a);
+    }
+    void* sort_buffers[] = {ctx->d_perm, ctx->d_perm_alt, ctx->d_keys, ctx->d_keys_alt, ctx->d_idx, ctx->d_idx_alt, ctx->d_sort_tmp};
+    for (void* p : sort_buffers)
+        if (p) (void)hipFree(p);
+    ctx->d_perm = ctx->d_perm_alt = nullptr;
+    ctx->d_keys = ctx->d_keys_alt = nullptr;
+    ctx->d_idx = ctx->d_idx_alt = nullptr;
+    ctx->d_sort_tmp = nullptr;
+    ctx->sort_tmp_bytes = 0;
+    ctx->dev = DParticles{};
+    ctx->alt = DParticles{};
+    ctx->capacity = 0;
+}
+
+// exchange the column pointers of `dev` and `alt` (sizes / flags stay): all of them, or only the columns a launch writes
+static void swap_columns(pk_ctx* ctx, bool launch_outputs_only) {
     DParticles &d = ctx->dev, &a = ctx->alt;
-    std::swap(d.t, a.t); std::swap(d.z, a.z); std::swap(d.y, a.y); std::swap(d.x, a.x);
-    std::swap(d.dz, a.dz); std::swap(d.dy, a.dy); std::swap(d.dx, a.dx); std::swap(d.dt, a.dt);
-    std::swap(d.next_dt, a.next_dt); std::swap(d.state, a.state); std::swap(d.ei, a.ei); std::swap(d.particle_id, a.particle_id);
-    for (int k = 0; k < PK_MAX_EXTRA; k++) std::swap(d.extra[k], a.extra[k]);
+#define X(m, bit, elem, per_grid, optional) if (!launch_outputs_only || ((bit) & PK_LAUNCH_MASK)) std::swap(d.m, a.m);
+    PK_COLUMNS(X)
+#undef X
+    for (int k = 0; k < PK_MAX_EXTRA && !launch_outputs_only; k++) std::swap(d.extra[k], a.extra[k]);
     std::swap(d.iter, a.iter);
-    ctx->rerun_valid = false;  // the second set no longer holds the state before the last launch
+    if (!launch_outputs_only) ctx->rerun_valid = false;  // the second set no longer holds the state before the last launch
 }
-// exchange the columns an advection launch writes (pk_device.h: DPOut): the launch read `dev` and wrote `alt`
-static void swap_launch_outputs(pk_ctx* ctx) {
-    DParticles &d = ctx->dev, &a = ctx->alt;
-    std::swap(d.t, a.t); std::swap(d.z, a.z); std::swap(d.y, a.y); std::swap(d.x, a.x);
-    std::swap(d.dz, a.dz); std::swap(d.dy, a.dy); std::swap(d.dx, a.dx); std::swap(d.dt, a.dt);
-    std::swap(d.next_dt, a.next_dt); std::swap(d.state, a.state); std::swap(d.ei, a.ei); std::swap(d.iter, a.iter);
-}
+static void swap_column_sets(pk_ctx* ctx) { swap_columns(ctx, false); }    // after the cell sort and the compaction wrote the new order into `alt`
+static void swap_launch_outputs(pk_ctx* ctx) { swap_columns(ctx, true); }  // the launch read `dev` and wrote `alt`
 
 // second column set + permutation buffers, allocated on first use (only when cell sorting is requested)
 static int32_t ensure_alt(pk_ctx* ctx) {
     if (ctx->alt.t) return 0;
     const int64_t cap = ctx->capacity;
-    const size_t ss = spatial_size(ctx);
-    PK_HIP(ctx, hipMalloc((void**)&ctx->alt.t, cap * 8));
-    PK_HIP(ctx, hipMalloc(&ctx->alt.z, cap * ss));
-    PK_HIP(ctx, hipMalloc(&ctx->alt.y, cap * ss));
-    PK_HIP(ctx, hipMalloc(&ctx->alt.x, cap * ss));
-    PK_HIP(ctx, hipMalloc(&ctx->alt.dz, cap * ss));
-    PK_HIP(ctx, hipMalloc(&ctx->alt.dy, cap * ss));
-    PK_HIP(ctx, hipMalloc(&ctx->alt.dx, cap * ss));
-    PK_HIP(ctx, hipMalloc((void**)&ctx->alt.dt, cap * 8));
-    if (ctx->dev.next_dt) PK_HIP(ctx, hipMalloc((void**)&ctx->alt.next_dt, cap * 8));
-    PK_HIP(ctx, hipMalloc((void**)&ctx->alt.state, cap * 4));
-    PK_HIP(ctx, hipMalloc((void**)&ctx->alt.ei, cap * 4 * ctx->host.ngrids));
-    PK_HIP(ctx, hipMalloc((void**)&ctx->alt.particle_id, cap * 8));
-    PK_HIP(ctx, hipMalloc((void**)&ctx->alt.iter, cap * 4));
-    for (int k = 0; k < PK_MAX_EXTRA; k++)
-        if (ctx->dev.extra[k]) PK_HIP(ctx, hipMalloc(&ctx->alt.extra[k], cap * (ctx->dev.extra_f32[k] ? 4 : 8)));
+    const int32_t rc = alloc_column_set(ctx, ctx->alt, cap);
+    if (rc) return rc;
     PK_HIP(ctx, hipMalloc((void**)&ctx->d_perm, cap * 8));
     PK_HIP(ctx, hipMalloc((void**)&ctx->d_perm_alt, cap * 8));
     PK_HIP(ctx, hipMalloc((void**)&ctx->d_keys, cap * 8));
@@ -1458,14 +1443,14 @@ static int32_t ensure_alt(pk_ctx* ctx) {
     return 0;
 }
 
-template <class T>
-static void launch_gather(pk_ctx* ctx, const void* in, void* out, const uint32_t* perm, int64_t n, int width) {
-    hipLaunchKernelGGL((gather_rows_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->compute, (const T*)in, (T*)out, perm, n, width);
-}
-template <class T>
-static void launch_scatter(pk_ctx* ctx, const void* in, void* out, const int64_t* perm, int64_t n, int width) {
-    hipLaunchKernelGGL((scatter_rows_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->compute, (const T*)in, (T*)out, perm, n, width);
-}
+// The row kernels (pk_kernels.h, pk_select.inc) are templates on the unsigned integer of the column's element size and take
+// (const T* src, T* dst, ...): launch the instantiation that fits `elem`, one lane per row, on the compute stream.
+#define PK_LAUNCH_ROWS(ctx, kernel, elem, n, src, dst, ...)                                                                                            \
+    do {                                                                                                                                               \
+        const dim3 grid_((unsigned)(((n) + 255) / 256));                                                                                               \
+        if ((elem) == 8) hipLaunchKernelGGL((kernel<unsigned long long>), grid_, dim3(256), 0, (ctx)->compute, (const unsigned long long*)(src), (unsigned long long*)(dst), __VA_ARGS__); \
+        else hipLaunchKernelGGL((kernel<uint32_t>), grid_, dim3(256), 0, (ctx)->compute, (const uint32_t*)(src), (uint32_t*)(dst), __VA_ARGS__);      \
+    } while (0)
 
 static int bits_for(unsigned long long v) {
     int b = 1;
@@ -1500,8 +1485,7 @@ static int32_t sort_particles(pk_ctx* ctx, int main_grid, int horizontal_major) 
     const uint32_t* perm = ctx->d_idx_alt;
     for (const ColRef& c : particle_columns(ctx)) {
         if (!c.d || !c.a) continue;
-        if (c.elem == 8) launch_gather<unsigned long long>(ctx, c.d, c.a, perm, n, c.width);
-        else launch_gather<uint32_t>(ctx, c.d, c.a, perm, n, c.width);
+        PK_LAUNCH_ROWS(ctx, gather_rows_kernel, c.elem, n, c.d, c.a, perm, n, c.width);
     }
     hipLaunchKernelGGL(compose_perm_kernel, grid, dim3(256), 0, ctx->compute, ctx->has_perm ? ctx->d_perm : nullptr, perm, ctx->d_perm_alt, n);
     PK_HIP(ctx, hipGetLastError());
@@ -1526,8 +1510,7 @@ static int32_t copy_particles(pk_ctx* ctx, bool to_device, uint32_t mask = 0xFFF
         if (to_device) {
             PK_HIP(ctx, hipMemcpyAsync(c.d, c.h, bytes, hipMemcpyHostToDevice, ctx->compute));
         } else if (ctx->has_perm) {  // undo the cell sort: host row perm[i] <- device row i
-            if (c.elem == 8) launch_scatter<unsigned long long>(ctx, c.d, c.a, ctx->d_perm, n, c.width);
-            else launch_scatter<uint32_t>(ctx, c.d, c.a, ctx->d_perm, n, c.width);
+            PK_LAUNCH_ROWS(ctx, scatter_rows_kernel, c.elem, n, c.d, c.a, ctx->d_perm, n, c.width);
             PK_HIP(ctx, hipMemcpyAsync(c.h, c.a, bytes, hipMemcpyDeviceToHost, ctx->compute));
         } else {
             PK_HIP(ctx, hipMemcpyAsync(c.h, c.d, bytes, hipMemcpyDeviceToHost, ctx->compute));
@@ -1540,6 +1523,41 @@ static int32_t copy_particles(pk_ctx* ctx, bool to_device, uint32_t mask = 0xFFF
 #include "pk_select.inc"
 
 extern "C" {
+
+int32_t pk_particles_bind(pk_ctx* ctx, const pk_particles_desc* host) {
+    if (!ctx || !host) return -2;
+    if (host->n < 0 || host->ngrids < 1 || host->ngrids > PK_MAX_GRIDS) return ctx->fail("bad particle descriptor");
+    const auto hp = column_pointers(*host);
+    for (int k = 0; k < PK_COL_EXTRA_FIRST; k++)
+        if (host->n > 0 && !PK_COL_INFO[k].optional && !hp[k]) return ctx->fail("particle columns must not be NULL");
+    PK_HIP(ctx, hipSetDevice(ctx->device));
+    if (host->n_extra < 0 || host->n_extra > PK_MAX_EXTRA) return ctx->fail("bad number of extra particle columns");
+    bool extra_changed = host->n_extra != ctx->host.n_extra;
+    for (int k = 0; k < host->n_extra && !extra_changed; k++) extra_changed = host->extra_dtype[k] != ctx->host.extra_dtype[k];
+    for (int k = 0; k < host->n_extra; k++) {
+        if (host->extra_dtype[k] != PK_F32 && host->extra_dtype[k] != PK_F64) return ctx->fail("extra particle columns must be PK_F32 or PK_F64");
+        if (host->n > 0 && !host->extra[k]) return ctx->fail("particle columns must not be NULL");
+    }
+    const bool realloc_needed = !ctx->bound || host->n > ctx->capacity || host->ngrids != ctx->host.ngrids || extra_changed ||
+                                host->spatial_dtype != ctx->host.spatial_dtype || (host->next_dt != nullptr) != (ctx->dev.next_dt != nullptr);
+    ctx->host = *host;
+    if (realloc_needed) free_particles(ctx);
+    for (int k = 0; k < PK_MAX_EXTRA; k++) ctx->dev.extra_f32[k] = ctx->alt.extra_f32[k] = (k < host->n_extra && host->extra_dtype[k] == PK_F32);
+    if (realloc_needed) {
+        const int64_t cap = std::max<int64_t>(host->n, 1);
+        const int32_t rc = alloc_column_set(ctx, ctx->dev, cap);
+        if (rc) return rc;
+        ctx->capacity = cap;
+    }
+    ctx->has_perm = false;
+    ctx->rerun_valid = false;
+    ctx->chk_valid = false;
+    ctx->dev.n = host->n;
+    ctx->dev.ngrids = host->ngrids;
+    ctx->dev.spatial_f32 = host->spatial_dtype == PK_F32;
+    ctx->bound = true;
+    return 0;
+}
 
 int32_t pk_particles_h2d(pk_ctx* ctx) {
     if (!ctx) return -2;
@@ -1649,9 +1667,7 @@ int32_t pk_particles_h2d_columns(pk_ctx* ctx, uint32_t mask) {
             PK_HIP(ctx, hipMemcpyAsync(c.d, c.h, bytes, hipMemcpyHostToDevice, ctx->compute));
         } else {  // device row i holds host row perm[i]
             PK_HIP(ctx, hipMemcpyAsync(c.a, c.h, bytes, hipMemcpyHostToDevice, ctx->compute));
-            const dim3 grid((unsigned)((n + 255) / 256));
-            if (c.elem == 8) hipLaunchKernelGGL((gather_rows64_kernel<unsigned long long>), grid, dim3(256), 0, ctx->compute, (const unsigned long long*)c.a, (unsigned long long*)c.d, ctx->d_perm, n, c.width);
-            else hipLaunchKernelGGL((gather_rows64_kernel<uint32_t>), grid, dim3(256), 0, ctx->compute, (const uint32_t*)c.a, (uint32_t*)c.d, ctx->d_perm, n, c.width);
+            PK_LAUNCH_ROWS(ctx, gather_rows64_kernel, c.elem, n, c.a, c.d, ctx->d_perm, n, c.width);
             PK_HIP(ctx, hipGetLastError());
         }
     }
@@ -1730,7 +1746,7 @@ static int32_t snapshot_begin(pk_ctx* ctx, uint32_t mask, int32_t slot, bool fil
     const std::vector<ColRef> cols = particle_columns(ctx);
     const size_t ss = spatial_size(ctx);
     bool fits = sn.capacity >= n && sn.ngrids == ctx->host.ngrids && sn.ss == ss;
-    for (int k = 0; k < PK_MAX_EXTRA; k++) fits = fits && sn.extra_elem[k] == (cols[12 + k].d ? cols[12 + k].elem : 0);
+    for (int k = 0; k < PK_MAX_EXTRA; k++) fits = fits && sn.extra_elem[k] == (cols[PK_COL_EXTRA_FIRST + k].d ? cols[PK_COL_EXTRA_FIRST + k].elem : 0);
     for (int k = 0; k < PK_NCOLS; k++)
         if (((mask >> k) & 1u) && cols[k].d && !sn.dev[k]) fits = false;  // a column the buffers were not sized for
     if (!fits) {  // (re)size the columns of this mask only: pinning costs ~0.3 s per GB
@@ -1749,7 +1765,7 @@ static int32_t snapshot_begin(pk_ctx* ctx, uint32_t mask, int32_t slot, bool fil
         sn.capacity = cap;
         sn.ngrids = ctx->host.ngrids;
         sn.ss = ss;
-        for (int k = 0; k < PK_MAX_EXTRA; k++) sn.extra_elem[k] = cols[12 + k].d ? cols[12 + k].elem : 0;
+        for (int k = 0; k < PK_MAX_EXTRA; k++) sn.extra_elem[k] = cols[PK_COL_EXTRA_FIRST + k].d ? cols[PK_COL_EXTRA_FIRST + k].elem : 0;
     }
     sn.n = n;
     sn.mask = mask;
@@ -1770,8 +1786,7 @@ static int32_t snapshot_begin(pk_ctx* ctx, uint32_t mask, int32_t slot, bool fil
             if (!((mask >> k) & 1u) || !c.d) continue;
             const size_t bytes = (size_t)n * c.elem * c.width;
             if (ctx->has_perm) {  // undo the cell sort: host row perm[i] <- device row i
-                if (c.elem == 8) launch_scatter<unsigned long long>(ctx, c.d, sn.dev[k], ctx->d_perm, n, c.width);
-                else launch_scatter<uint32_t>(ctx, c.d, sn.dev[k], ctx->d_perm, n, c.width);
+                PK_LAUNCH_ROWS(ctx, scatter_rows_kernel, c.elem, n, c.d, sn.dev[k], ctx->d_perm, n, c.width);
             } else {
                 PK_HIP(ctx, hipMemcpyAsync(sn.dev[k], c.d, bytes, hipMemcpyDeviceToDevice, ctx->compute));
             }
@@ -1805,11 +1820,10 @@ int32_t pk_particles_snapshot_wait(pk_ctx* ctx, int32_t slot, pk_particles_desc*
     out->n = sn.n;
     out->ngrids = sn.ngrids;
     out->spatial_dtype = sn.ss == 4 ? PK_F32 : PK_F64;
-    void** dst[12] = {(void**)&out->t, &out->z, &out->y, &out->x, &out->dz, &out->dy, &out->dx, (void**)&out->dt, (void**)&out->next_dt,
-                      (void**)&out->state, (void**)&out->ei, (void**)&out->particle_id};
-    for (int k = 0; k < 12; k++) *dst[k] = ((sn.mask >> k) & 1u) ? sn.host[k] : nullptr;
+    void* cols[PK_NCOLS];
+    for (int k = 0; k < PK_NCOLS; k++) cols[k] = ((sn.mask >> k) & 1u) ? sn.host[k] : nullptr;
+    set_column_pointers(*out, cols, PK_NCOLS);
     for (int k = 0; k < PK_MAX_EXTRA; k++) {
-        out->extra[k] = ((sn.mask >> (12 + k)) & 1u) ? sn.host[12 + k] : nullptr;
         out->extra_dtype[k] = sn.extra_elem[k] == 4 ? PK_F32 : PK_F64;
         if (sn.extra_elem[k]) out->n_extra = k + 1;
     }
@@ -1822,14 +1836,7 @@ int32_t pk_particles_device(pk_ctx* ctx, pk_particles_desc* dev, int64_t** perm)
     dev->n = ctx->dev.n;
     dev->ngrids = ctx->dev.ngrids;
     dev->spatial_dtype = ctx->host.spatial_dtype;
-    dev->t = ctx->dev.t;
-    dev->z = ctx->dev.z; dev->y = ctx->dev.y; dev->x = ctx->dev.x;
-    dev->dz = ctx->dev.dz; dev->dy = ctx->dev.dy; dev->dx = ctx->dev.dx;
-    dev->dt = ctx->dev.dt;
-    dev->next_dt = ctx->dev.next_dt;
-    dev->state = ctx->dev.state;
-    dev->ei = ctx->dev.ei;
-    dev->particle_id = ctx->dev.particle_id;
+    set_column_pointers(*dev, column_pointers(ctx->dev).data(), PK_COL_EXTRA_FIRST);  // (the extras are not handed out)
     if (perm) *perm = ctx->has_perm ? ctx->d_perm : nullptr;
     return 0;
 }
@@ -1872,8 +1879,7 @@ int32_t pk_particles_compact(pk_ctx* ctx, const pk_particles_desc* new_host, int
         PK_HIP(ctx, hipMemcpyAsync(&last_keep, keep + (n - 1), 8, hipMemcpyDeviceToHost, ctx->compute));
         for (const ColRef& c : particle_columns(ctx)) {
             if (!c.d || !c.a) continue;
-            if (c.elem == 8) hipLaunchKernelGGL((compact_rows_kernel<unsigned long long>), grid, dim3(256), 0, ctx->compute, (const unsigned long long*)c.d, (unsigned long long*)c.a, keep, pos, n, c.width);
-            else hipLaunchKernelGGL((compact_rows_kernel<uint32_t>), grid, dim3(256), 0, ctx->compute, (const uint32_t*)c.d, (uint32_t*)c.a, keep, pos, n, c.width);
+            PK_LAUNCH_ROWS(ctx, compact_rows_kernel, c.elem, n, c.d, c.a, keep, pos, n, c.width);
         }
         if (perm) hipLaunchKernelGGL(compact_perm_kernel, grid, dim3(256), 0, ctx->compute, perm, keep, pos, host_pos, n, ctx->d_perm_alt);
         PK_HIP(ctx, hipGetLastError());
@@ -2629,20 +2635,16 @@ int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
         rc = ensure_alt(ctx);
         if (rc) return rc;
         a.p = ctx->dev;
-        a.po = DPOut{ctx->alt.t, ctx->alt.z, ctx->alt.y, ctx->alt.x, ctx->alt.dz, ctx->alt.dy, ctx->alt.dx, ctx->alt.dt, ctx->alt.next_dt,
-                     ctx->alt.state, ctx->alt.ei, ctx->alt.iter};
+#define X(m, bit, elem, per_grid, optional) a.po.m = ctx->alt.m;
+        PK_LAUNCH_COLUMNS(X)
+#undef X
+        a.po.iter = ctx->alt.iter;
         if (!prm->reset_state || prm->body_only) {
             // a continued (paused) call or a masked body launch: some rows are not stepped -- they keep their values by this
             // device-to-device copy of the columns a launch writes (the kernels themselves carry no copy code: pk_kernels.h)
-            const size_t ss = spatial_size(ctx);
-            const size_t nn = (size_t)n;
-            const struct { void* dst; const void* src; size_t bytes; } cp[] = {
-                {ctx->alt.t, ctx->dev.t, nn * 8}, {ctx->alt.z, ctx->dev.z, nn * ss}, {ctx->alt.y, ctx->dev.y, nn * ss}, {ctx->alt.x, ctx->dev.x, nn * ss},
-                {ctx->alt.dz, ctx->dev.dz, nn * ss}, {ctx->alt.dy, ctx->dev.dy, nn * ss}, {ctx->alt.dx, ctx->dev.dx, nn * ss}, {ctx->alt.dt, ctx->dev.dt, nn * 8},
-                {ctx->alt.next_dt, ctx->dev.next_dt, nn * 8}, {ctx->alt.state, ctx->dev.state, nn * 4},
-                {ctx->alt.ei, ctx->dev.ei, nn * 4 * (size_t)ctx->host.ngrids}, {ctx->alt.iter, ctx->dev.iter, nn * 4}};
-            for (const auto& c : cp)
-                if (c.dst && c.src) PK_HIP(ctx, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, ctx->compute));
+            for (const ColRef& c : particle_columns(ctx))
+                if (c.launch_output && c.d && c.a)
+                    PK_HIP(ctx, hipMemcpyAsync(c.a, c.d, (size_t)n * c.elem * c.width, hipMemcpyDeviceToDevice, ctx->compute));
         }
         if (ctx->clock_probe) {  // the probe may start once everything queued before the advection kernel is done
             if (!ctx->probe) {
@@ -3200,8 +3202,7 @@ int32_t pk_interact_host_order(pk_ctx* ctx) {
         if (rc) return rc;
         for (const ColRef& c : particle_columns(ctx)) {  // host row perm[i] <- device row i, as pk_particles_d2h does on its way out
             if (!c.d || !c.a) continue;
-            if (c.elem == 8) launch_scatter<unsigned long long>(ctx, c.d, c.a, ctx->d_perm, n, c.width);
-            else launch_scatter<uint32_t>(ctx, c.d, c.a, ctx->d_perm, n, c.width);
+            PK_LAUNCH_ROWS(ctx, scatter_rows_kernel, c.elem, n, c.d, c.a, ctx->d_perm, n, c.width);
         }
         PK_HIP(ctx, hipGetLastError());
         PK_HIP(ctx, hipStreamSynchronize(ctx->compute));

@@ -83,18 +83,18 @@ struct PkComm {
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;
     // device staging: this rank's selected rows (pk_select.inc) and the gathered rows, per column
-    void* d_sel[12 + PK_MAX_EXTRA] = {};
-    size_t sel_bytes[12 + PK_MAX_EXTRA] = {};
-    void* d_all[12 + PK_MAX_EXTRA] = {};
-    size_t all_bytes[12 + PK_MAX_EXTRA] = {};
+    void* d_sel[PK_NCOLS] = {};
+    size_t sel_bytes[PK_NCOLS] = {};
+    void* d_all[PK_NCOLS] = {};
+    size_t all_bytes[PK_NCOLS] = {};
     long long* d_counts = nullptr;  // [world] (+ 1: this rank's count as the all-gather's send buffer)
     long long* d_red = nullptr;     // pk_comm_allreduce_i64
     int red_cap = 0;
     std::vector<int64_t> counts;    // of the last exchange
     int64_t total = 0;              // rows this rank holds gathered (0 on the ranks a gather-to-root skipped)
     uint32_t mask = 0;
-    size_t elem[12 + PK_MAX_EXTRA] = {};
-    int width[12 + PK_MAX_EXTRA] = {};
+    size_t elem[PK_NCOLS] = {};
+    int width[PK_NCOLS] = {};
 };
 
 #define PK_NCCL(ctx, call)                                                                            \
@@ -228,7 +228,7 @@ int32_t pk_comm_destroy(pk_ctx* ctx) {
     if (!cm) return 0;
     (void)hipSetDevice(ctx->device);
     if (cm->comm) (void)rccl().CommDestroy(cm->comm);
-    for (int k = 0; k < 12 + PK_MAX_EXTRA; k++) {
+    for (int k = 0; k < PK_NCOLS; k++) {
         if (cm->d_sel[k]) (void)hipFree(cm->d_sel[k]);
         if (cm->d_all[k]) (void)hipFree(cm->d_all[k]);
     }
@@ -322,9 +322,8 @@ int32_t pk_gathered_fetch(pk_ctx* ctx, const pk_particles_desc* out, int64_t cap
     if (!cm) return ctx->fail("no communicator (pk_comm_init)");
     if (capacity < cm->total) return ctx->fail("pk_gathered_fetch: the arrays are shorter than the gathered rows");
     PK_HIP(ctx, hipSetDevice(ctx->device));
-    void* dst[12 + PK_MAX_EXTRA] = {out->t, out->z, out->y, out->x, out->dz, out->dy, out->dx, out->dt, out->next_dt, out->state, out->ei, out->particle_id};
-    for (int k = 0; k < PK_MAX_EXTRA; k++) dst[12 + k] = out->extra[k];
-    for (int k = 0; k < 12 + PK_MAX_EXTRA; k++) {
+    const auto dst = column_pointers(*out);
+    for (int k = 0; k < PK_NCOLS; k++) {
         if (!((cm->mask >> k) & 1u)) continue;
         if (!dst[k]) return ctx->fail("pk_gathered_fetch: a gathered column has no destination array");
         if (cm->total > 0)

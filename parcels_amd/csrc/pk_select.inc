@@ -75,9 +75,5 @@ static void select_column(pk_ctx* ctx, const ColRef& c, void* dst) {
     using namespace pk;
     const int64_t n = ctx->dev.n;
     const int64_t* perm = ctx->has_perm ? ctx->d_perm : nullptr;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (c.elem == 8) hipLaunchKernelGGL((select_rows_kernel<unsigned long long>), grid, dim3(256), 0, ctx->compute, (const unsigned long long*)c.d,
-                                        (unsigned long long*)dst, perm, ctx->sel.d_flag, ctx->sel.d_offs, n, c.width);
-    else hipLaunchKernelGGL((select_rows_kernel<uint32_t>), grid, dim3(256), 0, ctx->compute, (const uint32_t*)c.d, (uint32_t*)dst, perm, ctx->sel.d_flag,
-                            ctx->sel.d_offs, n, c.width);
+    PK_LAUNCH_ROWS(ctx, select_rows_kernel, c.elem, n, c.d, dst, perm, ctx->sel.d_flag, ctx->sel.d_offs, n, c.width);
 }

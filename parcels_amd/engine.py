@@ -415,25 +415,26 @@ class DeviceEngine:
             src._extra_refs.pop("next_dt", None)
             data = _RawView(src)
         n = data["x"].shape[0]
-        for k in ("t", "z", "y", "x", "dz", "dy", "dx", "dt", "state", "ei", "particle_id"):
+        required = [(name, kind) for name, _, kind, _ in _hip.COLUMNS if name != "next_dt"]  # (next_dt: optional, handled below)
+        for k, _ in required:
             a = data[k]
             if not a.flags["C_CONTIGUOUS"]:
                 data[k] = np.ascontiguousarray(a)
         sdt = data["x"].dtype
-        if any(data[k].dtype != sdt for k in ("z", "y", "dz", "dy", "dx")) or sdt not in (np.float32, np.float64):
+        want = {"f64": np.float64, "spatial": sdt, "i32": np.int32, "i64": np.int64}
+        bad = {kind for k, kind in required if data[k].dtype != want[kind]}
+        if "spatial" in bad or sdt not in (np.float32, np.float64):
             raise TypeError("z, y, x, dz, dy, dx must share one dtype (float32 or float64)")
-        if data["t"].dtype != np.float64 or data["dt"].dtype != np.float64:
+        if "f64" in bad:
             raise TypeError("t and dt must be float64")
-        if data["state"].dtype != np.int32 or data["ei"].dtype != np.int32 or data["particle_id"].dtype != np.int64:
+        if bad:
             raise TypeError("state/ei must be int32 and particle_id int64")
         d = _hip.ParticlesDesc()
         d.n = n
         d.ngrids = data["ei"].shape[1]
         d.spatial_dtype = _hip.PK_F32 if sdt == np.float32 else _hip.PK_F64
-        d.t = _ptr(data["t"])
-        d.z, d.y, d.x = _ptr(data["z"]), _ptr(data["y"]), _ptr(data["x"])
-        d.dz, d.dy, d.dx = _ptr(data["dz"]), _ptr(data["dy"]), _ptr(data["dx"])
-        d.dt = _ptr(data["dt"])
+        for k, _ in required:
+            setattr(d, k, _ptr(data[k]))
         nd = data.get("next_dt")
         self._next_dt_f32 = None
         if nd is not None and nd.dtype == np.float32:
@@ -446,7 +447,6 @@ class DeviceEngine:
         elif nd is not None and nd.dtype != np.float64:
             raise TypeError("next_dt must be float32 or float64")
         d.next_dt = _ptr(nd) if nd is not None else None
-        d.state, d.ei, d.particle_id = _ptr(data["state"]), _ptr(data["ei"]), _ptr(data["particle_id"])
         d.n_extra = len(self.device_variables)
         for k, name in enumerate(self.device_variables):
             a = data[name]
@@ -549,7 +549,7 @@ class DeviceEngine:
         n_new = int(np.count_nonzero(keep))
         new = {}
         for name, arr in pairs:
-            if name != "state" and (name in _hip.COLUMN_BITS or name in self.device_variables):
+            if name != "state" and self._column_bit(name):
                 new[name] = np.empty((n_new,) + arr.shape[1:], dtype=arr.dtype)
             else:
                 new[name] = np.ascontiguousarray(arr[keep])
@@ -566,7 +566,7 @@ class DeviceEngine:
             data._stale.clear()
             data._dirty.clear()
             new._engine = self
-            new._stale = {k for k in new.raw_keys() if k != "state" and (k in _hip.COLUMN_BITS or k in self.device_variables)}
+            new._stale = {k for k in new.raw_keys() if k != "state" and self._column_bit(k)}
         return new
 
     def h2d(self):
@@ -676,7 +676,7 @@ class DeviceEngine:
         return out
 
     # ---- asynchronous write-out snapshots ------------------------------------------------------------------------
-    _SNAP_COLS = ("t", "z", "y", "x", "dz", "dy", "dx", "dt", "next_dt", "state", "ei", "particle_id")
+    _SNAP_COLS = tuple(_hip.COLUMN_BITS)  # (particlefile.py reads it)
 
     def snapshot_begin(self, columns, slot: int, filter_t=None):
         """Enqueue the copy of the named device columns (host row order) into the pinned host set ``slot``; returns at once.
@@ -692,7 +692,7 @@ class DeviceEngine:
             self.ctx.check(self.lib.pk_particles_snapshot_filtered(self.ctx.handle, mask, int(slot), float(filter_t)), "pk_particles_snapshot_filtered")
         b = self._bound
         raw = b.raw if isinstance(b, LazyColumns) else b.__getitem__  # (dtypes only: no download, no dirty mark)
-        self._snap_dtypes = {k: raw(k).dtype for k in b.keys() if k in _hip.COLUMN_BITS or k in self.device_variables}
+        self._snap_dtypes = {k: raw(k).dtype for k in b.keys() if self._column_bit(k)}
 
     def snapshot_wait(self, slot: int) -> dict:
         """Block until snapshot ``slot`` has landed; NumPy views of its pinned columns (valid until the slot is reused).  Callable
@@ -703,18 +703,17 @@ class DeviceEngine:
             raise _hip.HipLibraryError(f"pk_particles_snapshot_wait(slot={slot}) failed ({rc})")
         n = int(d.n)
         sp = np.float32 if d.spatial_dtype == _hip.PK_F32 else np.float64
-        spec = {"t": np.float64, "z": sp, "y": sp, "x": sp, "dz": sp, "dy": sp, "dx": sp, "dt": np.float64, "next_dt": np.float64,
-                "state": np.int32, "ei": np.int32, "particle_id": np.int64}
+        kinds = {"f64": np.float64, "spatial": sp, "i32": np.int32, "i64": np.int64}
         out = {}
-        for name in self._SNAP_COLS:
+        for name, _, kind, per_grid in _hip.COLUMNS:
             ptr = getattr(d, name)
             if not ptr:
                 continue
-            width = int(d.ngrids) if name == "ei" else 1
-            dt = np.dtype(spec[name])
+            width = int(d.ngrids) if per_grid else 1
+            dt = np.dtype(kinds[kind])
             buf = (C.c_char * (n * width * dt.itemsize)).from_address(ptr)
             a = np.frombuffer(buf, dtype=dt, count=n * width)
-            if name == "ei":
+            if per_grid:
                 a = a.reshape(n, width)
             want = self._snap_dtypes.get(name)
             if name == "next_dt" and want is not None and want != dt:  # float32 Variable shadowed by a float64 device column

@@ -16,13 +16,14 @@ import warnings
 
 import numpy as np
 
+from . import _hip
 from . import kernels as _k
 from .engine import raise_particle_errors
 from .statuscodes import StatusCode
 from .uxgrid import UxGrid
 
 
-_RESERVED_COLUMNS = {"t", "z", "y", "x", "dz", "dy", "dx", "dt", "next_dt", "state", "ei", "particle_id"}
+_RESERVED_COLUMNS = set(_hip.COLUMN_BITS)  # the built-in columns: no user Variable may take their names
 
 
 

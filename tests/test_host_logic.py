@@ -46,6 +46,22 @@ def test_ctypes_structs_match_header_layout(tmp_path):
     assert _hip.PK_MAX_EXTRA == 8 and _hip.PK_MAX_KERNELS == 8
 
 
+def test_column_table_matches_header_bits():
+    """The PK_COL_* defines of include/parcels_hip.h, in the order the header lists them == the bits of _hip.COLUMNS, in order;
+    PK_COL_EXTRA0 is the first bit behind the named columns."""
+    import re
+
+    from parcels_amd import _hip
+
+    with open(os.path.join(ROOT_DIR, "include", "parcels_hip.h")) as f:
+        defines = [(m.group(1), int(m.group(2), 16)) for m in re.finditer(r"^#define PK_COL_(\w+) (0x[0-9a-fA-F]+)u", f.read(), re.M)]
+    assert defines[-1] == ("EXTRA0", 1 << len(_hip.COLUMNS)) and _hip.PK_COL_EXTRA0 == 1 << len(_hip.COLUMNS)
+    assert defines[:-1] == [(name.upper(), bit) for name, bit, _, _ in _hip.COLUMNS]
+    assert [bit for _, bit, _, _ in _hip.COLUMNS] == [1 << k for k in range(len(_hip.COLUMNS))]
+    for name, bit in defines[:-1]:
+        assert getattr(_hip, "PK_COL_" + name) == bit == _hip.COLUMN_BITS[name.lower()]
+
+
 def test_no_gpu_fails_loudly():
     """The product path has no CPU fallback: without a device the engine must raise, not compute."""
     import torch
