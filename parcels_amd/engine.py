@@ -15,8 +15,11 @@ Replaces the body of the reference's ``Kernel.execute`` (src/parcels/_core/kerne
 from __future__ import annotations
 
 import ctypes as C
+import logging
 import os
+import time
 import warnings
+from collections import namedtuple
 
 import numpy as np
 
@@ -68,7 +71,33 @@ class _LazyLevels:
         return np.ascontiguousarray(a, dtype=self.dtype)
 
 
+def _timed(total, key, fn, *args):
+    """fn(*args), its wall time added to total[key]"""
+    t = time.perf_counter()
+    out = fn(*args)
+    total[key] += time.perf_counter() - t
+    return out
+
+
+# What the launches of one DeviceEngine.execute share: `params` are the make_params arguments that no launch changes, `have_guess0` and
+# `skip_first_sort` hold for the first launch of a pass only, `span0` is the re-sort horizon in seconds of model time (None: none)
+_Call = namedtuple("_Call", "kernel_ids params have_guess0 sort_by_cell skip_first_sort sign span0")
+# What one pass over a call reports to its settlement (DeviceEngine._settle_pass): the first erring iteration and the smallest sample key at
+# which a particle left a time interval (0: none), every unlisted failing sample (ascending), per listed key whether some particle justified
+# it, whether every launch reported real justification flags, and the state counts (code -> particles) after the last launch
+_PassResult = namedtuple("_PassResult", "err twk found hits validated counts")
+
+
 class DeviceEngine:
+    # what an engine built without __init__ (the scripted engines of the CPU suite) has as well
+    _sorted_t = None  # model time at which the device rows were last cell-sorted (None: host order / unknown)
+    _next_dt_f32 = None
+    _user_program = None
+    # a sharded ParticleSet is one batch: hooks of parcels_amd.distributed.batch_agreement (set by ParticleSet.execute for a collective run)
+    agree_min = None
+    agree_codes = None
+    exact_error_stop = True  # kernel.py:236-245: after an error every particle stops where the reference's batch loop did
+
     def __init__(self, fieldset, device: int = 0, nslots: int | None = None, memory_fraction: float = 0.6,
                  hash_build: str | None = None, neighbour_probe: int = 0):
         # hash_build: "device" (default) builds the Morton table of a curvilinear grid on the GPU (csrc/pk_hashbuild.hip);
@@ -98,17 +127,12 @@ class DeviceEngine:
         self._plan_and_create_fields(nslots, memory_fraction)
         self._bound_sig = None
         self._bound = None
-        self._sorted_t = None  # model time at which the device rows were last cell-sorted (None: host order / unknown)
         # what crossed PCIe for the particle columns: calls and column counts (tests and bench.py's `repeat_execute` leg read it)
         self.transfers = {"h2d_full": 0, "h2d_columns": 0, "d2h_full": 0, "d2h_columns": 0, "columns_up": 0, "columns_down": 0}
         self.comm = None  # (rank, world) once the context has joined an RCCL communicator (comm_init)
         self.comm_stats = {"gathers": 0, "allreduces": 0}
         self.comm_last_counts = None
-        self._next_dt_f32 = None
         self.device_variables: list[str] = []  # user Variables bound as extra device columns (set by Kernel: SampleField targets)
-        # a sharded ParticleSet is one batch: hooks of parcels_amd.distributed.batch_agreement (set by ParticleSet.execute for a collective run)
-        self.agree_min = None
-        self.agree_codes = None
         self.last_stats: dict | None = None
 
     # ---- grids -----------------------------------------------------------------------------------------------
@@ -322,7 +346,6 @@ class DeviceEngine:
                 for lv in range(self.field_host[f.name].shape[0]):
                     self._upload(f.name, lv, asynchronous=False)
         self.windowed = any(self.field_nslots[f.name] < self.field_host[f.name].shape[0] for f in self.scalar_fields)
-        self.exact_error_stop = True  # kernel.py:236-245: after an error every particle stops where the reference's batch loop did
 
     def _upload(self, name, level, asynchronous):
         leader = self.pack_leader_of.get(name)
@@ -757,7 +780,7 @@ class DeviceEngine:
         p.fKh_zonal = fid.get("Kh_zonal", -1)
         p.fKh_meridional = fid.get("Kh_meridional", -1)
         p.rk45_mode = int("RK45_tol" in context)
-        p.next_dt_f32 = int(getattr(self, "_next_dt_f32", None) is not None)
+        p.next_dt_f32 = int(self._next_dt_f32 is not None)
         p.reset_state = int(reset_state)
         p.have_guess0 = int(have_guess0)
         p.sort_by_cell = int(sort_by_cell)
@@ -849,8 +872,7 @@ class DeviceEngine:
 
     def set_user_program(self, program):
         """Register (or, with None, unregister) the run-time compiled module that carries a kernel list's user kernels (jit.py)."""
-        cur = getattr(self, "_user_program", None)
-        if program is cur:
+        if program is self._user_program:
             return
         fids = (C.c_int32 * 4)(*(list(program.sample_fids) + [0] * 4)[:4]) if program is not None else (C.c_int32 * 4)()
         self.ctx.check(self.lib.pk_set_user_program(self.ctx.handle, C.c_void_p(program.launcher() if program is not None else None),
@@ -881,159 +903,43 @@ class DeviceEngine:
         is intact); a call of several launches (streamed levels, re-sort horizons, user kernels that update Variables in place) from
         the device checkpoint taken before its first launch.  ``self.agree_min`` (set for a sharded ParticleSet, distributed.py):
         the batch is ALL shards, so the ranks agree on the smallest error iteration / sample key after every pass."""
-        sign = 1 if dt0 > 0 else -1
-        import time as _time
-
         # host-side split of a streamed run: commit = synchronous level uploads before a launch, prefetch = staging + enqueueing
         # the next level while the kernel runs, wait = pk_execute_end after the prefetch was enqueued
         total = {"steps": 0, "attempts": 0, "kernel_ms": 0.0, "sort_ms": 0.0, "launches": 0, "commit_s": 0.0, "prefetch_s": 0.0, "wait_s": 0.0,
                  "first_error_iter": 0, "reran": 0, "time_error_keys": [], "pack_ms": 0.0, "packs": 0}
         span0 = None
         if resort_every and sort_by_cell:
-            ctx_ = context or {}
-            span0 = max(float(resort_every), abs(float(dt0)), abs(float(ctx_.get("RK45_max_dt", 0.0))))
+            span0 = max(float(resort_every), abs(float(dt0)), abs(float((context or {}).get("RK45_max_dt", 0.0))))
         # A run that may take several launches keeps the state before the first one on the device: an error in a LATER launch stops the
         # whole batch at an iteration some particles passed launches ago (kernel.py:236-245), so the run starts over with that limit.
-        checkpointed = False
         # (a re-sort horizon only cuts runs longer than itself: the usual output interval is one launch and needs no checkpoint)
         several = self.windowed or (span0 is not None and not (t_start is not None and np.isfinite(t_start) and abs(float(endtime) - float(t_start)) <= span0))
         # user kernels update their Variables in place (they are not part of the column set a launch writes): repeating a launch from the
         # columns it read would apply them twice, so a repeat of such a list always restarts from the checkpoint
         several = several or in_place_variables
-        if several and self.exact_error_stop:
+        checkpointed = bool(several and self.exact_error_stop)
+        if checkpointed:
             self.ctx.check(self.lib.pk_particles_checkpoint(self.ctx.handle), "pk_particles_checkpoint")
-            checkpointed = True
         # Rows that are still in the cell order of an earlier call (device-resident columns, parcels_amd/columns.py) are not sorted again
         # before `resort_every` of model time has passed: the order of ONE sort holds for weeks of a smooth flow (DESIGN.md section 5), and a
         # sort costs a third of a 24-step launch.  Locality only -- trajectories do not depend on the row order.
-        sorted_t = getattr(self, "_sorted_t", None)
-        skip_first_sort = bool(sort_by_cell and sorted_t is not None and t_start is not None and np.isfinite(t_start)
-                               and abs(float(t_start) - sorted_t) < (float(resort_every) if resort_every else np.inf))
+        skip_first_sort = bool(sort_by_cell and self._sorted_t is not None and t_start is not None and np.isfinite(t_start)
+                               and abs(float(t_start) - self._sorted_t) < (float(resort_every) if resort_every else np.inf))
+        call = _Call(kernel_ids, dict(endtime=endtime, dt0=dt0, context=context, seed=seed, samples=samples), have_guess0, sort_by_cell,
+                     skip_first_sort, 1 if dt0 > 0 else -1, span0)
         cap = 0  # iteration limit of the batch loop (0: none)
         keys: list[int] = []  # samples that fail call-wide with OutsideTimeInterval (pk_exec_params.twe_key)
-        rerun = False  # the next pass is a single launch repeated from the second column set
-        agree = getattr(self, "agree_min", None)
+        rerun = False  # this pass is the single launch, repeated from the second column set
         while True:  # passes over the whole call
-            reset = 1
-            t_live = t_start
-            last_live = None
-            span = span0
-            pass_err, pass_twk = 0, 0
-            pass_found: set = set()          # unlisted failing samples of this pass (all launches)
-            pass_hits = [False] * len(keys)  # listed samples some particle justified in this pass
-            validated = True                 # every launch of the pass reported real justification flags
-            total["steps"] = total["attempts"] = 0
             try:
-                while True:  # launches of one pass
-                    st = _hip.ExecStats()
-                    prefetched = False
-                    if rerun:
-                        karr = (C.c_int64 * max(len(keys), 1))(*keys)
-                        self.ctx.check(self.lib.pk_execute_rerun_keys(self.ctx.handle, int(cap), len(keys), karr, C.byref(st)), "pk_execute_rerun_keys")
-                        rerun = False
-                    else:
-                        nxt = None
-                        if self.windowed:
-                            if t_live is None or not np.isfinite(t_live):
-                                t_live = 0.0 if sign > 0 else max(float(f.model.time_flt[-1]) for f in self._windowed_fields())
-                            _t = _time.perf_counter()
-                            nxt = self._commit_window(float(t_live), sign)
-                            total["commit_s"] += _time.perf_counter() - _t
-                        horizon = None
-                        if span is not None and t_live is not None and np.isfinite(t_live):
-                            horizon = (-np.inf, float(t_live) + span) if sign > 0 else (float(t_live) - span, np.inf)
-                        sort_now = 0 if (reset and skip_first_sort) else sort_by_cell
-                        prm = self.make_params(kernel_ids, endtime=endtime, dt0=dt0, context=context, seed=seed, reset_state=reset,
-                                               have_guess0=(have_guess0 if reset else 1), sort_by_cell=sort_now, samples=samples, horizon=horizon,
-                                               max_iters=cap, twe_keys=keys)
-
-                        if sort_now and t_live is not None and np.isfinite(t_live):
-                            self._sorted_t = float(t_live)
-                        elif sort_now:
-                            self._sorted_t = None
-                        self.ctx.check(self.lib.pk_execute_begin(self.ctx.handle, C.byref(prm)), "pk_execute_begin")
-                        try:
-                            _t = _time.perf_counter()
-                            prefetched = self._prefetch(nxt)  # overlaps the kernel that was just launched
-                            total["prefetch_s"] += _time.perf_counter() - _t
-                        finally:
-                            _t = _time.perf_counter()
-                            self.ctx.check(self.lib.pk_execute_end(self.ctx.handle, C.byref(st)), "pk_execute_end")
-                            total["wait_s"] += _time.perf_counter() - _t
-                    reset = 0
-                    total["steps"] += st.steps
-                    total["attempts"] += st.attempts
-                    total["kernel_ms"] += st.kernel_ms
-                    total["sort_ms"] += st.sort_ms
-                    total["pack_ms"] += getattr(st, "pack_ms", 0.0)
-                    total["packs"] += getattr(st, "packs", 0)
-                    total["launches"] += st.launches
-                    total["sclk_mhz"] = float(getattr(st, "sclk_mhz", 0.0))  # shader clock of the (last) launch's kernel
-                    total["program"] = int(st.program)  # which device program the (last) launch ran: include/parcels_hip.h, pk_exec_stats
-                    counts = {code: int(st.state_counts[code]) for code in range(_hip.PK_NUM_STATE_CODES) if st.state_counts[code]}
-                    if st.first_error_iter > 0:
-                        pass_err = int(st.first_error_iter) if pass_err == 0 else min(pass_err, int(st.first_error_iter))
-                    if st.first_time_error_key > 0:
-                        pass_twk = int(st.first_time_error_key) if pass_twk == 0 else min(pass_twk, int(st.first_time_error_key))
-                    if self.exact_error_stop and (st.first_time_error_key > 0 or keys):
-                        fl, hl, real = self._twe_report(keys, int(st.first_time_error_key))
-                        pass_found.update(fl)
-                        pass_hits = [a or b for a, b in zip(pass_hits, hl)]
-                        validated = validated and real
-                    if st.paused == 0:
-                        break
-                    if not self.windowed and span is None:
-                        raise _hip.HipLibraryError("particles paused although all time levels are resident (internal error)")
-                    # (what this launch found already decides that the pass will be repeated: stop it here.  The launches not made would have
-                    # reached listed samples too: a pass that was cut short says nothing against a listed key)
-                    if self.exact_error_stop and agree is None and (pass_found or self._repeat_decision(pass_err, pass_twk, cap) is not None):
-                        pass_hits = [True] * len(keys)
-                        break
-                    t_live = st.t_min_live if sign > 0 else st.t_max_live
-                    # no particle moved AND no new level is on its way (a small ring needs one launch per cycle just to bring in the
-                    # level behind the window; the next commit makes it resident): the step itself does not fit
-                    if last_live is not None and t_live == last_live and not prefetched:
-                        if span is not None:
-                            span *= 2.0  # the soft horizon, not the ring, stopped every particle: widen it
-                        else:
-                            raise RuntimeError(
-                                "field window too small: a single step does not fit into the resident time levels; "
-                                "increase nslots (FieldSet.to_device(nslots=...))"
-                            )
-                    last_live = t_live
+                res = self._run_pass(call, total, t_start, cap, keys, rerun)
             except Exception:
-                # a collective run: the other ranks are on their way to the agreement of this pass -- meet them there (they raise
-                # CollectiveAbort), then let this rank's own exception through
-                if agree is not None and self.exact_error_stop:
-                    try:
-                        agree(0, 0, failed=True)
-                    except Exception as e2:  # noqa: BLE001 -- the original exception matters; the swallowed one is logged (ADVICE r5)
-                        import logging
-
-                        logging.getLogger("parcels_amd").warning("the failure agreement of a collective run raised as well: %r", e2)
+                self._meet_the_ranks_after_a_failure()
                 raise
             if not self.exact_error_stop:
                 break
-            found = sorted(pass_found)
-            if agree is not None:  # the batch of the reference is every shard's particles
-                pass_err, pass_twk = agree(pass_err, pass_twk)
-                agree_keys = getattr(agree, "keys", None)
-                if not pass_twk and not keys:
-                    pass  # nobody found a failing sample and none is listed (both known to every rank): the common pass costs ONE all-reduce
-                else:
-                    got = agree_keys(found if validated else None, pass_hits) if agree_keys is not None else None
-                    if got is not None and got[0] is not None:
-                        found, pass_hits = got
-                    else:  # (an agreement of the round-4 form, or a rank without validation: the smallest key only, one key per pass)
-                        validated = False
-            if not validated:
-                found, pass_hits = ([pass_twk] if pass_twk else []), [True] * len(keys)
-            # kernel.py:236-245 / field.py:31-44: what the pass found decides whether the call is repeated -- with the failing samples listed
-            # (all that were found, validated by the next pass) or with the iteration limit of the first error
-            decision, keys, cap = self._twe_step(keys, cap, pass_err, found, pass_hits,
-                                                 speculative=validated and total["reran"] < self.TWE_SPECULATIVE_PASSES)
-            repeat = decision is not None
-            if not repeat:
+            decision, keys, cap = self._settle_pass(keys, cap, res, total["reran"])
+            if decision is None:
                 break
             total["reran"] += 1
             if checkpointed:
@@ -1042,13 +948,128 @@ class DeviceEngine:
                 raise _hip.HipLibraryError("a call of several launches has to be repeated but has no checkpoint (internal error)")
             else:
                 rerun = True  # the state before the (only) launch still sits in the second column set
-        total["first_error_iter"] = cap
-        total["time_error_keys"] = list(keys)
-        total["state_counts"] = counts
+        total.update(first_error_iter=cap, time_error_keys=list(keys), state_counts=res.counts)
         if self.agree_codes is not None and self.exact_error_stop:
-            total["codes_any_shard"] = self._agree_on_codes(counts)
+            total["codes_any_shard"] = self._agree_on_codes(res.counts)
         self.last_stats = total
         return total
+
+    def _launch(self, call, total, *, reset, t_live, span, cap, keys, rerun):
+        """One launch of a pass -> (its pk_exec_stats, whether a level was prefetched behind it): the repeat of the call's only launch from
+        the second column set, or commit the window, launch up to the horizon, prefetch while the kernel runs, wait."""
+        st = _hip.ExecStats()
+        if rerun:
+            karr = (C.c_int64 * max(len(keys), 1))(*keys)
+            self.ctx.check(self.lib.pk_execute_rerun_keys(self.ctx.handle, int(cap), len(keys), karr, C.byref(st)), "pk_execute_rerun_keys")
+            return st, False
+        nxt = None
+        if self.windowed:
+            if t_live is None or not np.isfinite(t_live):
+                t_live = 0.0 if call.sign > 0 else max(float(f.model.time_flt[-1]) for f in self._windowed_fields())
+            nxt = _timed(total, "commit_s", self._commit_window, float(t_live), call.sign)
+        known = t_live is not None and np.isfinite(t_live)
+        horizon = None
+        if span is not None and known:
+            horizon = (-np.inf, float(t_live) + span) if call.sign > 0 else (float(t_live) - span, np.inf)
+        sort_now = 0 if (reset and call.skip_first_sort) else call.sort_by_cell
+        prm = self.make_params(call.kernel_ids, reset_state=reset, have_guess0=(call.have_guess0 if reset else 1), sort_by_cell=sort_now,
+                               horizon=horizon, max_iters=cap, twe_keys=keys, **call.params)
+        if sort_now:
+            self._sorted_t = float(t_live) if known else None
+        self.ctx.check(self.lib.pk_execute_begin(self.ctx.handle, C.byref(prm)), "pk_execute_begin")
+        try:
+            prefetched = _timed(total, "prefetch_s", self._prefetch, nxt)  # overlaps the kernel that was just launched
+        finally:
+            self.ctx.check(_timed(total, "wait_s", self.lib.pk_execute_end, self.ctx.handle, C.byref(st)), "pk_execute_end")
+        return st, prefetched
+
+    @staticmethod
+    def _fold(total, st):
+        """The statistics of one launch into those of the call, which have three lifetimes -> the launch's state counts."""
+        total["steps"] += st.steps  # of the current pass: _run_pass zeroes these two
+        total["attempts"] += st.attempts
+        total["kernel_ms"] += st.kernel_ms  # summed over all passes, as are commit_s / prefetch_s / wait_s (_timed)
+        total["sort_ms"] += st.sort_ms
+        total["pack_ms"] += st.pack_ms
+        total["packs"] += st.packs
+        total["launches"] += st.launches
+        # of the last launch: the shader clock of its kernel, which device program it ran (include/parcels_hip.h, pk_exec_stats), and the
+        # state counts that execute returns
+        total["sclk_mhz"] = float(st.sclk_mhz)
+        total["program"] = int(st.program)
+        return {code: int(st.state_counts[code]) for code in range(_hip.PK_NUM_STATE_CODES) if st.state_counts[code]}
+
+    def _run_pass(self, call, total, t_start, cap, keys, rerun) -> _PassResult:
+        """The launches of one pass over the call: until no particle is left paused before a horizon or the end of the resident levels."""
+        reset, t_live, last_live, span = 1, t_start, None, call.span0
+        err = twk = 0
+        found: set = set()          # unlisted failing samples of this pass (all launches)
+        hits = [False] * len(keys)  # listed samples some particle justified in this pass
+        validated = True            # every launch of the pass reported real justification flags
+        total["steps"] = total["attempts"] = 0
+        while True:
+            st, prefetched = self._launch(call, total, reset=reset, t_live=t_live, span=span, cap=cap, keys=keys, rerun=rerun)
+            reset, rerun = 0, False
+            counts = self._fold(total, st)
+            if st.first_error_iter > 0:
+                err = int(st.first_error_iter) if err == 0 else min(err, int(st.first_error_iter))
+            if st.first_time_error_key > 0:
+                twk = int(st.first_time_error_key) if twk == 0 else min(twk, int(st.first_time_error_key))
+            if self.exact_error_stop and (st.first_time_error_key > 0 or keys):
+                fl, hl, real = self._twe_report(keys, int(st.first_time_error_key))
+                found.update(fl)
+                hits = [a or b for a, b in zip(hits, hl)]
+                validated = validated and real
+            if st.paused == 0:
+                break
+            if not self.windowed and span is None:
+                raise _hip.HipLibraryError("particles paused although all time levels are resident (internal error)")
+            # (what this launch found already decides that the pass will be repeated: stop it here.  The launches not made would have
+            # reached listed samples too: a pass that was cut short says nothing against a listed key.  Not in a collective run: every
+            # rank finishes its launches before the agreement)
+            if self.exact_error_stop and self.agree_min is None and (found or self._repeat_decision(err, twk, cap) is not None):
+                hits = [True] * len(keys)
+                break
+            t_live = st.t_min_live if call.sign > 0 else st.t_max_live
+            # no particle moved AND no new level is on its way (a small ring needs one launch per cycle just to bring in the
+            # level behind the window; the next commit makes it resident): the step itself does not fit
+            if last_live is not None and t_live == last_live and not prefetched:
+                if span is None:
+                    raise RuntimeError("field window too small: a single step does not fit into the resident time levels; "
+                                       "increase nslots (FieldSet.to_device(nslots=...))")
+                span *= 2.0  # the soft horizon, not the ring, stopped every particle: widen it
+            last_live = t_live
+        return _PassResult(err, twk, sorted(found), hits, validated, counts)
+
+    def _meet_the_ranks_after_a_failure(self):
+        """A pass of a collective run raised: the other ranks are on their way to the agreement of this pass -- meet them there (they raise
+        CollectiveAbort); the caller then lets this rank's own exception through."""
+        if self.agree_min is None or not self.exact_error_stop:
+            return
+        try:
+            self.agree_min(0, 0, failed=True)
+        except Exception as e2:  # noqa: BLE001 -- the original exception matters; the swallowed one is logged (ADVICE r5)
+            logging.getLogger("parcels_amd").warning("the failure agreement of a collective run raised as well: %r", e2)
+
+    def _settle_pass(self, keys, cap, res: _PassResult, reran: int):
+        """A pass is over -> (decision, keys, cap) of `_twe_step`, from what EVERY shard's pass found.  The one place where the ranks of a
+        collective run exchange what they found: `execute` and `execute_idle` must issue the same sequence of collectives."""
+        err, twk, found, hits, validated = res.err, res.twk, res.found, res.hits, res.validated
+        if self.agree_min is not None:  # the batch of the reference is every shard's particles
+            err, twk = self.agree_min(err, twk)
+            agree_keys = getattr(self.agree_min, "keys", None)
+            # (nobody found a failing sample and none is listed, both known to every rank: the common pass costs ONE all-reduce)
+            if twk or keys:
+                got = agree_keys(found if validated else None, hits) if agree_keys is not None else None
+                if got is not None and got[0] is not None:
+                    found, hits = got
+                else:  # (an agreement of the round-4 form, or a rank without validation: the smallest key only, one key per pass)
+                    validated = False
+        if not validated:
+            found, hits = ([twk] if twk else []), [True] * len(keys)
+        # kernel.py:236-245 / field.py:31-44: what the pass found decides whether the call is repeated -- with the failing samples listed
+        # (all that were found, validated by the next pass) or with the iteration limit of the first error; also its RuntimeError at PK_MAX_TWE
+        return self._twe_step(keys, cap, err, found, hits, speculative=validated and reran < self.TWE_SPECULATIVE_PASSES)
 
     _RAISING_CODES = (70, 60, 61, 51, 52, 50)  # statuscodes.ErrorsToThrow, in its order (kernel.py:31-38)
 
@@ -1064,17 +1085,9 @@ class DeviceEngine:
         if not self.exact_error_stop or self.agree_min is None:
             return total
         cap, keys = 0, []
-        while True:
-            pass_err, pass_twk = self.agree_min(0, 0)
-            agree_keys = getattr(self.agree_min, "keys", None)
-            if not pass_twk and not keys:  # (the same shortcut, from the same agreed values, as `execute`)
-                validated, found, hits = True, [], []
-            else:
-                got = agree_keys([], [False] * len(keys)) if agree_keys is not None else None
-                validated = got is not None and got[0] is not None
-                found, hits = got if validated else (([pass_twk] if pass_twk else []), [True] * len(keys))
-            # (the same decision, from the same agreed values, as the shards that hold particles -- also its RuntimeError at PK_MAX_TWE)
-            decision, keys, cap = self._twe_step(keys, cap, pass_err, found, hits, speculative=validated and total["reran"] < self.TWE_SPECULATIVE_PASSES)
+        while True:  # (the same decisions, from the same agreed values, as the shards that hold particles)
+            nothing = _PassResult(err=0, twk=0, found=[], hits=[False] * len(keys), validated=True, counts={})
+            decision, keys, cap = self._settle_pass(keys, cap, nothing, total["reran"])
             if decision is None:
                 break
             total["reran"] += 1
