@@ -158,7 +158,8 @@ PK_DEV int cell_index_tab(const pk_tab2* tab, int n, double x, int i) {
 // last cell (NumPy sorts NaN last), and cell_index_tab answers n-2.
 // FLAGGED: the caller answers "n >= 2" itself (`two`, a bit of FastTabs::fl tested where it is used).
 template <bool FLAGGED = false>
-PK_DEV void fast_search(const pk_tab2* tab, int n, double first, double last, double x, int& cell, int& idx, double& bc, bool two = true) {
+PK_DEV void fast_search(const pk_tab2* tab, int n, double first, double last, double x, int& cell, int& idx, double& bc, bool two = true,
+                        pk_tab2* kept = nullptr, double* kept1 = nullptr) {
     if (FLAGGED ? !two : n < 2) {  // :45-46
         idx = 0;
         bc = 0.0;
@@ -187,6 +188,10 @@ PK_DEV void fast_search(const pk_tab2* tab, int n, double first, double last, do
     }
     bc = fast_bary(x, e.x, a1, e.y);
     cell = i;
+    if (kept) {  // (a compile-time NULL for the callers that do not ask: the entries of the cell found, FCtx::ta)
+        *kept = e;
+        *kept1 = a1;
+    }
     // :55-58.  A point left of the first node is in cell 0, one right of the last node in cell n-2 (the clip of :47), so only lanes in
     // an edge cell pay the two fp64 compares (a divergent block most wavefronts skip: the particles live in the interior)
     if (__builtin_expect(i == 0 || i == n - 2, 0)) {
@@ -437,6 +442,19 @@ PK_DEV double lp_sum(const LpField& f, double tau, double eta, double xsi) {
     return fma(eta, fma(xsi, pxy, py), fma(xsi, px, p0));
 }
 
+// lp_sum on a block that stays in its registers (PK_FAST_BLOCK_REGS): the four fma(tau, D*, P*) as the three-address v_fma_f64.  The compiler
+// selects the two-address v_fmac_f64, which accumulates into P* -- dead behind the sum when the block came out of LDS, live here: it put a
+// v_mov_b64 in front of each of the eight.  The same fused operation on the same operands.
+PK_DEV double fma3(double a, double b, double c) {
+    double r;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+PK_DEV double lp_sum_held(const LpField& f, double tau, double eta, double xsi) {
+    const double p0 = fma3(tau, f.d0.x, f.p0.x), px = fma3(tau, f.d0.y, f.p0.y), py = fma3(tau, f.d1.x, f.p1.x), pxy = fma3(tau, f.d1.y, f.p1.y);
+    return fma(eta, fma(xsi, pxy, py), fma(xsi, px, p0));
+}
+
 PK_DEV int uniform_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // ---- cell record in registers (FAST_LP_CACHE only) ---------------------------------------------------------------------------------
@@ -460,6 +478,39 @@ PK_DEV int uniform_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
 #define PK_FAST_CELL_REGS 1
 #endif
 constexpr bool fast_cell_regs(int lp) { return PK_FAST_CELL_REGS != 0 && lp == FAST_LP_CACHE; }
+
+// ---- block and time cell in registers (FAST_LP_CACHE with the cell record, float64 particle storage) ------------------------------------------
+// With the cell record every evaluation still read the lane's 128-byte block from LDS -- the sixteen doubles the same lane had held in the
+// same registers one evaluation earlier: 0.79 of the wave-evaluations have no missing lane -- and every second one (stages 2 and 4 bring a
+// new t) searched the time table for the cell the wavefront has sat in since the launch began.
+// PK_FAST_BLOCK_REGS: Z0 / D of U and V (FCtx::fu, fv) are lane state that survives from one evaluation to the next and from one step to the
+// next; the LDS slot is their backing store.
+//   * Invariant: whenever ei == bei and the level pair is that of bkey, the registers hold what the slot holds.  A wave-evaluation without a
+//     missing lane touches LDS for nothing but a time-cell miss.
+//   * A wave-evaluation with a missing lane does what it did: the missing lanes fetch and write their slot behind the waterfall, then ALL
+//     lanes load the block from their slot -- so the hit lanes' registers are dead across the miss branch, whose corner rows need them.
+//   * The early returns (time error, out-of-bounds code) leave registers and slot as they are.
+//   * The final sums use the three-address v_fma_f64 (lp_sum_held): the compiler's v_fmac_f64 accumulates into P*, which now stays live, and
+//     cost a v_mov_b64 in front of each of the eight -- with them this build was 2 % SLOWER than the early read it replaces.
+//   * The 32 registers come out of the depth memo: of hz, zi, zez and mzeta one register stays, FCtx::zi = zi * 2 + lenZ.  The hit path needs
+//     neither index nor weight (a new depth drops the block: lenZ is no part of the hit test, FCtx::bkey holds the level pair only); the table
+//     path forms zi * ez for its ravel; the miss branch and the out-of-bounds rules read the depth cell's entry again and form zeta from the
+//     operands the search had (depth_zeta).  Without this the headline kernel spilled 4 VGPRs once per step (16 B of scratch).
+//   * Not in the instantiations for float32 particle storage, which start 6 VGPRs higher (as with the early block read): they keep their code.
+// PK_FAST_TIME_REC: the entries of the lane's time cell -- first node, second node, 1 / width (FCtx::ta, tb, tr), index FCtx::ht -- instead of the
+// memo (mt, mtau).  A lane with ta < t <= tb takes ti from the record and tau = (t - ta) * tr, the operands and the operation of fast_bary
+// inside fast_search: the same bits.  Every other lane -- first evaluation, new level pair, t exactly on a node, t == 0, NaN, a one-level
+// axis -- runs fast_search unchanged and renews the record from the entry the search holds; the range test stays in front.  One record per
+// lane: one per wavefront in scalar registers (renewed under a ballot from the first lane outside it) was built, measured and not kept.
+// 0 / 0 compiles to the code before (A/B builds).  Measured: profiles/c2_block_registers_ab.txt.
+#ifndef PK_FAST_BLOCK_REGS
+#define PK_FAST_BLOCK_REGS 1
+#endif
+constexpr bool fast_block_regs(int lp, bool pf) { return PK_FAST_BLOCK_REGS != 0 && fast_cell_regs(lp) && !pf; }
+#ifndef PK_FAST_TIME_REC
+#define PK_FAST_TIME_REC 1
+#endif
+constexpr bool fast_time_rec(int lp, bool pf) { return PK_FAST_TIME_REC != 0 && fast_block_regs(lp, pf); }
 
 // The status rules of eval_uvw_fast for an evaluation some index of which carries an out-of-bounds code (field.py:307-378; the record's cold path)
 PK_DEV int fast_oob_state(int s, int xi, int yi, int zi, double xsi, double eta, double zeta, double tau) {
@@ -494,27 +545,33 @@ struct FCtx {
     // Cell record (PK_FAST_CELL_REGS, FAST_LP_CACHE): the table entries of the lane's cell (hy, hx) -- first node, second node, 1 / width of lat and
     // of lon -- held in registers for as long as the lane stays inside it.  ya = +inf: no record (the test of eval_uvw_fast fails).
     double ya, yb, yr, xa, xb, xr;
+    // PK_FAST_BLOCK_REGS: the block itself -- what the slot holds whenever ei == bei and bkey names the level pair.  FCtx::zi is zi * 2 + lenZ then.
+    LpField fu, fv;
+    // PK_FAST_TIME_REC: the entries of the lane's time cell `ht` -- first node, second node, 1 / width.  ta = +inf: no record.
+    double ta, tb, tr;
 };
 constexpr int32_t FAST_NO_BLOCK = -0x7fffffff - 1;
 constexpr int FAST_Z_UNSEARCHED = -3;  // FCtx::zi before the launch's one depth search (PK_FAST_CELL_REGS; no index, no out-of-bounds code)
 // PK_FAST_CELL_REGS: the step loop moved z by a non-zero dz -- search depth again in the next evaluation (which drops the block of the old
 // depth and forms `zez`, `ei` anew), on the table path
-PK_DEV void fctx_depth_moved(FCtx& c) {
-    c.zi = FAST_Z_UNSEARCHED;
+constexpr int FAST_Z_UNSEARCHED_PACKED = -0x7fffffff - 1;  // the same for the packed depth cell of PK_FAST_BLOCK_REGS (zi * 2 + lenZ)
+PK_DEV void fctx_depth_moved(FCtx& c, bool packed = false) {
+    c.zi = packed ? FAST_Z_UNSEARCHED_PACKED : FAST_Z_UNSEARCHED;
     c.ya = __builtin_inf();
 }
-PK_DEV void fctx_init(FCtx& c, int state, int32_t ei, bool cell_regs = false) {
+PK_DEV void fctx_init(FCtx& c, int state, int32_t ei, bool cell_regs = false, bool packed = false) {
     c.state = state;
     c.ei = ei;
     c.ht = c.hz = c.hy = c.hx = 0;
-    c.zi = cell_regs ? FAST_Z_UNSEARCHED : 0;
-    c.ya = c.xa = __builtin_inf();
-    c.yb = c.xb = c.yr = c.xr = 0.0;
+    c.zi = packed ? FAST_Z_UNSEARCHED_PACKED : cell_regs ? FAST_Z_UNSEARCHED : 0;
+    c.ya = c.xa = c.ta = __builtin_inf();
+    c.yb = c.xb = c.yr = c.xr = c.tb = c.tr = 0.0;
     c.zez = 0u;
     c.mt = c.mz = __builtin_nan("");  // equal to nothing
     c.mtau = c.mzeta = 0.0;
     c.bei = FAST_NO_BLOCK;
     c.bkey = -1;
+    c.fu.p0 = c.fu.p1 = c.fu.d0 = c.fu.d1 = c.fv.p0 = c.fv.p1 = c.fv.d0 = c.fv.d1 = pk_tab2{0.0, 0.0};
 }
 
 // VectorField.eval (field.py:250-304) + XLinear_Velocity.interp (_xinterpolators.py:169-190).  PF: the sample point may come
@@ -528,12 +585,13 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
     uint32_t fl = T.fl;
     asm volatile("" : "+s"(fl));  // opaque: every FA_* test below is a scalar bit test HERE, not a loop-invariant lane mask (FastTabs::fl)
     u = v = w = 0.0;
-    // With the cell record the lane's block is requested HERE, in front of the time search and the cell test, which run under its latency (the slot
+    // With the cell record and without PK_FAST_BLOCK_REGS the lane's block is requested HERE, in front of the time search and the cell test, which run under its latency (the slot
     // address is a lane constant).  A lane whose block turns out stale throws the values away: the miss branch re-reads behind its write.  Before
     // the slot's first fill the values are whatever LDS holds -- nothing but the final sums is formed from them, and a lane without a block misses.
     // (Not in the instantiations for float32 particle storage: they start 6 VGPRs higher, and with the 16 of the early block
     // advect_fast_kernel<double, 1, false, FAST_LP_CACHE> spilled 4 VGPRs inside the stage loop.)
-    constexpr bool SPEC = fast_cell_regs(LP) && !PF;
+    constexpr bool BR = fast_block_regs(LP, PF);
+    constexpr bool SPEC = fast_cell_regs(LP) && !PF && !BR;
     LpField fu, fv;
     if constexpr (SPEC) {
         fu.p0 = T.blk[0]; fu.p1 = T.blk[FAST_WG_LP]; fu.d0 = T.blk[2 * FAST_WG_LP]; fu.d1 = T.blk[3 * FAST_WG_LP];
@@ -548,27 +606,61 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
             twe_note(a, it, klo);
             return;
         }
-        if (t != c.mt) {
-            int idx;
-            fast_search<true>(T.time, F.nt, F.t0, F.t1, t, c.ht, idx, c.mtau, (fl & FA_NT2) != 0);  // level times start at 0 (host check): idx == c.ht
-            c.mt = t;
-            if (LP == FAST_LP_OFF) c.bei = FAST_NO_BLOCK;  // (the level-pair block does not depend on t: its key holds ti and lenT)
+        if constexpr (fast_time_rec(LP, PF)) {
+            if (__builtin_expect((c.ta < t) & (t <= c.tb), 1)) {
+                tau = fast_bary(t, c.ta, c.tb, c.tr);
+            } else {
+                int idx;
+                pk_tab2 e;
+                double a1;
+                const bool two = (fl & FA_NT2) != 0;
+                fast_search<true>(T.time, F.nt, F.t0, F.t1, t, c.ht, idx, tau, two, &e, &a1);
+                c.ta = __builtin_inf();
+                if (two && idx >= 0) { c.ta = e.x; c.tb = a1; c.tr = e.y; }
+            }
+            ti = c.ht;
+        } else {
+            if (t != c.mt) {
+                int idx;
+                fast_search<true>(T.time, F.nt, F.t0, F.t1, t, c.ht, idx, c.mtau, (fl & FA_NT2) != 0);  // level times start at 0 (host check): idx == c.ht
+                c.mt = t;
+                if (LP == FAST_LP_OFF) c.bei = FAST_NO_BLOCK;  // (the level-pair block does not depend on t: its key holds ti and lenT)
+            }
+            ti = c.ht;
+            tau = c.mtau;
         }
-        ti = c.ht;
-        tau = c.mtau;
     }
     int zi = 0, yi = 0, xi = 0;
     double zeta = 0.0, eta = 0.0, xsi = 0.0;
     constexpr bool CR = fast_cell_regs(LP);
+    // PK_FAST_BLOCK_REGS: zeta of the packed depth cell FCtx::zi, from the operands the search had (the miss branch and the out-of-bounds rules)
+    auto depth_zeta = [&]() -> double {
+        if ((fl & (FA_Z | FA_NZ2)) != (FA_Z | FA_NZ2)) return 0.0;
+        const int q = c.zi >> 1;  // the cell an out-of-bounds code was found in: the first one (left) or the last one (right), fast_search
+        const int h = q >= 0 ? q : (q == LEFT_OUT_OF_BOUNDS ? 0 : F.gnz - 2);
+        const pk_tab2 e = T.depth[h];
+        return fast_bary(z, e.x, T.depth[h + 1].x, e.y);
+    };
     if (fl & FA_Z) {
-        if (CR ? c.zi == FAST_Z_UNSEARCHED : !(z == c.mz)) {
-            fast_search<true>(T.depth, F.gnz, F.z0, F.z1, z, c.hz, c.zi, c.mzeta, (fl & FA_NZ2) != 0);
-            c.zez = (uint32_t)c.zi * F.ez;
-            if (!CR) c.mz = z;
-            c.bei = FAST_NO_BLOCK;
+        if constexpr (BR) {
+            if (c.zi == FAST_Z_UNSEARCHED_PACKED) {
+                int hz = 0, idx;
+                double bz;
+                fast_search<true>(T.depth, F.gnz, F.z0, F.z1, z, hz, idx, bz, (fl & FA_NZ2) != 0);
+                c.zi = idx * 2 + (!(bz <= 0) ? 1 : 0);
+                c.bei = FAST_NO_BLOCK;
+            }
+            zi = c.zi >> 1;
+        } else {
+            if (CR ? c.zi == FAST_Z_UNSEARCHED : !(z == c.mz)) {
+                fast_search<true>(T.depth, F.gnz, F.z0, F.z1, z, c.hz, c.zi, c.mzeta, (fl & FA_NZ2) != 0);
+                c.zez = (uint32_t)c.zi * F.ez;
+                if (!CR) c.mz = z;
+                c.bei = FAST_NO_BLOCK;
+            }
+            zi = c.zi;
+            zeta = c.mzeta;
         }
-        zi = c.zi;
-        zeta = c.mzeta;
     }
 #ifndef PK_FAST_SEARCH2
 #define PK_FAST_SEARCH2 1
@@ -589,8 +681,10 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
                 if (fl & FA_Y) fast_search<true>(T.lat, T.gny, F.y0, F.y1, y, c.hy, yi, eta, (fl & FA_NY2) != 0);
                 if (fl & FA_X) fast_search<true>(T.lon, T.gnx, F.x0, F.x1, x, c.hx, xi, xsi, (fl & FA_NX2) != 0);
             }
-            c.ei = (int32_t)((uint32_t)xi + (uint32_t)yi * F.ey + c.zez);  // (cold: the wrapped 32-bit product serves indices and codes alike)
+            // (cold: the wrapped 32-bit product serves indices and codes alike)
+            c.ei = (int32_t)((uint32_t)xi + (uint32_t)yi * F.ey + (BR ? (uint32_t)zi * F.ez : c.zez));
             if (__builtin_expect((xi | yi | zi) < 0, 0)) {
+                if (BR) zeta = depth_zeta();
                 c.state = fast_oob_state(c.state, xi, yi, zi, xsi, eta, zeta, tau);
                 c.ya = __builtin_inf();
                 return;
@@ -624,8 +718,9 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
             return;
         }
     }
-    const bool lenT = tau > 0, lenZ = !(zeta <= 0);
-    const int key = (ti << 2) | (lenT ? 2 : 0) | (lenZ ? 1 : 0);
+    const bool lenT = tau > 0, lenZ = BR ? (c.zi & 1) != 0 : !(zeta <= 0);
+    // (PK_FAST_BLOCK_REGS: the hit test leaves lenZ out -- FCtx::bkey holds the level pair only, the waterfall's key has all three)
+    const int key = (ti << 2) | (lenT ? 2 : 0) | (!BR && lenZ ? 1 : 0);
     // (a same-cell lane of the cell record formed no indices: past the out-of-bounds return they are the hints)
     if (CR) { yi = c.hy; xi = c.hx; }
     const uint32_t b00 = ((uint32_t)zi * F.st_z + (uint32_t)yi * F.st_y + (uint32_t)xi) * (uint32_t)sizeof(FT);
@@ -639,9 +734,11 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
         const bool miss = LP == FAST_LP_REGS || c.ei != c.bei || key != c.bkey;
         const bool some_miss = LP == FAST_LP_REGS || __builtin_amdgcn_ballot_w64(miss) != 0;
         if (some_miss) {
+            if (BR) zeta = depth_zeta();  // (its two reads are under way while the corner rows are requested)
+            const int wkey = BR ? key | (lenZ ? 1 : 0) : key;
             // the waterfall over the key, as below (level bases stay in SGPRs); a lane that hit starts as done
             for (bool done = !miss; !done;) {
-                const int uk = uniform_i32(key);
+                const int uk = uniform_i32(wkey);
                 const int uti = uk >> 2;
                 int s0 = uti, s1 = uti + 1;
                 if (fl & FA_RING) {
@@ -651,7 +748,7 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
                 int64_t o0 = (int64_t)s0 * F.lvl_b, o1 = (int64_t)s1 * F.lvl_b;
                 int lens = uk & 3;
                 asm volatile("" : "+s"(o0), "+s"(o1), "+s"(lens));
-                if (key == uk) {
+                if (wkey == uk) {
                     if (lens == 3) lp_fetch<FT, true, true>(F, o0, o1, b00, zeta, fu, fv);
                     else if (lens == 2) lp_fetch<FT, true, false>(F, o0, o1, b00, zeta, fu, fv);
                     else if (lens == 1) lp_fetch<FT, false, true>(F, o0, o1, b00, zeta, fu, fv);
@@ -669,12 +766,21 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
                 c.bkey = key;
             }
         }
-        if (LP == FAST_LP_CACHE && (!SPEC || some_miss)) {
-            fu.p0 = T.blk[0]; fu.p1 = T.blk[FAST_WG_LP]; fu.d0 = T.blk[2 * FAST_WG_LP]; fu.d1 = T.blk[3 * FAST_WG_LP];
-            fv.p0 = T.blk[4 * FAST_WG_LP]; fv.p1 = T.blk[5 * FAST_WG_LP]; fv.d0 = T.blk[6 * FAST_WG_LP]; fv.d1 = T.blk[7 * FAST_WG_LP];
+        if constexpr (BR) {
+            if (some_miss) {
+                c.fu.p0 = T.blk[0]; c.fu.p1 = T.blk[FAST_WG_LP]; c.fu.d0 = T.blk[2 * FAST_WG_LP]; c.fu.d1 = T.blk[3 * FAST_WG_LP];
+                c.fv.p0 = T.blk[4 * FAST_WG_LP]; c.fv.p1 = T.blk[5 * FAST_WG_LP]; c.fv.d0 = T.blk[6 * FAST_WG_LP]; c.fv.d1 = T.blk[7 * FAST_WG_LP];
+            }
+            uu = lp_sum_held(c.fu, tau, eta, xsi);
+            vv = lp_sum_held(c.fv, tau, eta, xsi);
+        } else {
+            if (LP == FAST_LP_CACHE && (!SPEC || some_miss)) {
+                fu.p0 = T.blk[0]; fu.p1 = T.blk[FAST_WG_LP]; fu.d0 = T.blk[2 * FAST_WG_LP]; fu.d1 = T.blk[3 * FAST_WG_LP];
+                fv.p0 = T.blk[4 * FAST_WG_LP]; fv.p1 = T.blk[5 * FAST_WG_LP]; fv.d0 = T.blk[6 * FAST_WG_LP]; fv.d1 = T.blk[7 * FAST_WG_LP];
+            }
+            uu = lp_sum(fu, tau, eta, xsi);
+            vv = lp_sum(fv, tau, eta, xsi);
         }
-        uu = lp_sum(fu, tau, eta, xsi);
-        vv = lp_sum(fv, tau, eta, xsi);
     } else {
         const bool bc = !D3 && PK_FAST_BLOCK_CACHE && (fl & FA_BLK) != 0;
         // (in-bounds indices ravel to a non-negative `ei` that names the cell; the memo updates above already dropped a block of another (t, z))

@@ -736,7 +736,7 @@ __global__ void __launch_bounds__(fast_wg(LP), PK_MIN_WAVES_FAST) advect_fast_ke
         c.state = prm.reset_state ? PK_EVALUATE : P.state[i];  // kernel.py:188
         if (c.state == PK_EVALUATE) {
             unsigned it = prm.reset_state ? 0u : (unsigned)P.iter[i];
-            fctx_init(c, PK_EVALUATE, P.ei[i * P.ngrids + a.fast.grid], fast_cell_regs(LP));  // only the velocity grid's `ei` is touched
+            fctx_init(c, PK_EVALUATE, P.ei[i * P.ngrids + a.fast.grid], fast_cell_regs(LP), fast_block_regs(LP, pf));  // only the velocity grid's `ei` is touched
             double pt = P.t[i];
             double pz = ldp(P.z, i, pf), py = ldp(P.y, i, pf), px = ldp(P.x, i, pf);
             double pdz = ldp(P.dz, i, pf), pdy = ldp(P.dy, i, pf), pdx = ldp(P.dx, i, pf);
@@ -828,7 +828,7 @@ __global__ void __launch_bounds__(fast_wg(LP), PK_MIN_WAVES_FAST) advect_fast_ke
                     py = padd(pf, py, pdy);
                     // (the level-pair kernel with the cell record searches depth only when told that z moved: a dz brought into the launch)
                     if constexpr (fast_cell_regs(LP)) {
-                        if (__builtin_expect(!(pdz == 0), 0)) fctx_depth_moved(c);
+                        if (__builtin_expect(!(pdz == 0), 0)) fctx_depth_moved(c, fast_block_regs(LP, pf));
                     }
                     pz = padd(pf, pz, pdz);
                     pt += pdt;

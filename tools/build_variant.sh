@@ -1,6 +1,9 @@
 #!/bin/bash
 # A/B builds of the fast kernels: tools/build_variant.sh NAME -DPK_MIN_WAVES_FAST=5 ... -> parcels_amd/libparcels_hip_NAME.so
 # (select it at run time with PARCELS_HIP_LIB=...; the other objects are those of the last `make`)
+# Switches of the level-pair kernels (pk_fast_agrid.h), each 1 by default: -DPK_FAST_CELL_REGS=0 (table search in every evaluation),
+# -DPK_FAST_BLOCK_REGS=0 (the lane's block is read from LDS in every evaluation; also turns the time record off),
+# -DPK_FAST_TIME_REC=0 (the time memo instead of the time-cell record)
 set -e
 NAME=$1; shift
 cd "$(dirname "$0")/../parcels_amd/csrc"
@@ -11,7 +14,7 @@ for tu in ${PK_VARIANT_TUS:-pk_prog_rk4_fast pk_prog_rk4_fast_lp pk_prog_rk4_3d_
 done
 wait
 OBJS=""
-for o in pk_api pk_host_stage pk_hashbuild pk_neighbors pk_interact pk_prog_rk4 pk_prog_rk4_3d pk_prog_rk45 pk_prog_m1 pk_prog_generic pk_prog_typed pk_prog_rk4_fast pk_prog_rk4_fast_lp pk_prog_rk4_3d_fast pk_prog_cgrid_fast pk_prog_ux pk_prog_sigma; do
+for o in pk_api pk_host_stage pk_hashbuild pk_neighbors pk_interact pk_density pk_prog_rk4 pk_prog_rk4_3d pk_prog_rk45 pk_prog_m1 pk_prog_generic pk_prog_typed pk_prog_rk4_fast pk_prog_rk4_fast_lp pk_prog_rk4_3d_fast pk_prog_cgrid_fast pk_prog_ux pk_prog_sigma; do
   if [ -f /tmp/pkv_$NAME/$o.o ]; then OBJS="$OBJS /tmp/pkv_$NAME/$o.o"; else OBJS="$OBJS $o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o ../libparcels_hip_$NAME.so $OBJS
