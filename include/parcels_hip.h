@@ -645,6 +645,58 @@ typedef struct {
 int32_t pk_particles_density(pk_ctx* ctx, int32_t grid_id, int32_t levels, int32_t weight_kind, int32_t weight_extra, int32_t weight_dtype,
                              const double* weights_host, int64_t ncells, void* out, int64_t* n_outside, pk_density_info_t* info);
 
+/* ---- where the bound rows are, and where they came from (csrc/pk_connectivity.hip) ---------------------------------------------------------
+ * The label of every bound row, on the device-resident columns.  What this call replaces is what a script does to record where its
+ * particles are: read `pset.x` / `pset.y` (two columns down, marked dirty, up again before the next execute), `grid.search(z, y, x)` with
+ * no guess on them (ParticleSet.populate_indices, particleset.py:252-262), unravel the answer and index a region map with it.  Here the
+ * bound rows are read where they are, in whichever row order the cell sort left them; nothing is written to them.
+ *   cell of a row: as for pk_particles_density (the same device function): the unguessed search of grid `grid_id`, ravelled over
+ *     (max(zdim, 1) with levels,) max(ydim, 1), max(xdim, 1); an error code of the search, or a non-finite x, y (z with levels), is no cell.
+ *   label: the cell, or with regions_host != NULL the entry of that cell in the region table (ncells int32 / int64 values on the HOST,
+ *     regions_dtype = PK_DENSITY_I32 / PK_DENSITY_I64; copied to the device for the call).  A negative entry means "no region".
+ *   labels_out: n int64 on the host in HOST row order (written through the row permutation of the cell sort); -1 = no cell or no region.
+ * ncells must be the product above (checked).  Needs bound particles, n < 2^32, fewer than 2^31 cells, no launch in flight. */
+int32_t pk_particles_cells(pk_ctx* ctx, int32_t grid_id, int32_t levels, int32_t regions_dtype, const void* regions_host, int64_t ncells,
+                           int64_t* labels_out);
+
+/* Rows per (origin label, destination label) pair -- the connectivity (transition) matrix of the bound rows.  What this call replaces is the
+ * script above followed by `np.unique(origin * n_dest + dest, return_counts=True)` over one 64-bit key per particle (a host sort), or by
+ * `np.bincount` of the same keys.
+ *   destination label d of a row: what pk_particles_cells answers for it now; it must be below n_dest (a region table with a larger label
+ *     fails the call).  A row with no label is outside: d = n_dest.
+ *   origin label o of a row: origin_kind PK_DENSITY_W_EXTRA = the device Variable extra[origin_extra], read in DEVICE row order;
+ *     PK_DENSITY_W_HOST = origin_host, n labels in HOST row order (copied to the device, read through the row permutation); elements are
+ *     origin_dtype = PK_DENSITY_I32 / PK_DENSITY_I64.  o < 0: the row is not tracked and counted nowhere.  o >= n_origin: the row is
+ *     counted in info->n_above and nowhere else -- the caller refuses the result.
+ *   key of a tracked row: o * (n_dest + 1) + d, so the outside rows are one more column; needs n_origin * (n_dest + 1) < 2^62.
+ *   path PK_CONN_LDS (at most 8192 keys: a workgroup-private histogram, one global add per non-zero bin and workgroup) and PK_CONN_GLOBAL
+ *     (one 64-bit global add per run of equal keys inside a wavefront; fewer than 2^31 keys): dense_out = n_origin * (n_dest + 1) int64 on
+ *     the host, row-major, T[o][d].
+ *   path PK_CONN_SPARSE: the keys are stored, radix-sorted over the bits in use and run-length encoded.  keys_out / counts_out = room for
+ *     max_pairs int64 each on the host; info->n_pairs of them are written, ascending by key -- np.unique's order.  More pairs than room
+ *     fails the call (n is always enough room).
+ * The counts are integers added with integer adds: exact in every path.  Needs bound particles, n < 2^32, fewer than 2^31 cells, no launch
+ * in flight. */
+#define PK_CONN_LDS 0
+#define PK_CONN_GLOBAL 1
+#define PK_CONN_SPARSE 2
+typedef struct {
+    int64_t n_tracked;  /* rows with 0 <= origin < n_origin */
+    int64_t n_outside;  /* tracked rows in no destination */
+    int64_t n_pairs;    /* non-zero (origin, destination) pairs, the outside column counted as a destination */
+    int64_t n_atomics;  /* 64-bit global atomic adds issued (0 for PK_CONN_SPARSE) */
+    int64_t n_above;    /* rows with origin >= n_origin */
+    int32_t path;       /* the path taken */
+    int32_t reserved0;
+    double key_ms;      /* HIP events: key (+ count) kernel | radix sort of the keys | run-length encode */
+    double sort_ms;
+    double encode_ms;
+} pk_connectivity_info_t;
+int32_t pk_particles_connectivity(pk_ctx* ctx, int32_t grid_id, int32_t levels, int32_t regions_dtype, const void* regions_host, int64_t ncells,
+                                  int32_t origin_kind, int32_t origin_extra, int32_t origin_dtype, const void* origin_host, int64_t n_origin,
+                                  int64_t n_dest, int32_t path, int64_t* dense_out, int64_t* keys_out, int64_t* counts_out, int64_t max_pairs,
+                                  pk_connectivity_info_t* info);
+
 /* achieved copy bandwidth probe (device-to-device float4 copy), GB/s; used as a measured roofline denominator */
 int32_t pk_measure_copy_bandwidth(pk_ctx* ctx, int64_t bytes, int32_t iters, double* gbps);
 

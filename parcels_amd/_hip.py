@@ -254,6 +254,14 @@ class DensityInfo(C.Structure):  # pk_density_info_t
 PK_DENSITY_W_NONE, PK_DENSITY_W_EXTRA, PK_DENSITY_W_HOST = 0, 1, 2
 PK_DENSITY_F32, PK_DENSITY_F64, PK_DENSITY_I32, PK_DENSITY_I64 = 0, 1, 2, 3
 
+
+class ConnectivityInfo(C.Structure):  # pk_connectivity_info_t
+    _fields_ = [("n_tracked", C.c_int64), ("n_outside", C.c_int64), ("n_pairs", C.c_int64), ("n_atomics", C.c_int64), ("n_above", C.c_int64),
+                ("path", C.c_int32), ("reserved0", C.c_int32), ("key_ms", C.c_double), ("sort_ms", C.c_double), ("encode_ms", C.c_double)]
+
+
+PK_CONN_LDS, PK_CONN_GLOBAL, PK_CONN_SPARSE = 0, 1, 2
+
 ABI_SYMBOLS = [
     "pk_abi_version",
     "pk_init",
@@ -312,6 +320,8 @@ ABI_SYMBOLS = [
     "pk_interact_merge",
     "pk_interact_epilogue",
     "pk_particles_density",
+    "pk_particles_cells",
+    "pk_particles_connectivity",
     "pk_measure_copy_bandwidth",
     "pk_set_option",
     "pk_upload_stats",
@@ -436,6 +446,9 @@ def load():
                                          C.POINTER(C.c_int64)]
     lib.pk_particles_density.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                          C.POINTER(C.c_int64), C.POINTER(DensityInfo)]
+    lib.pk_particles_cells.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+    lib.pk_particles_connectivity.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                              C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ConnectivityInfo)]
     if lib.pk_abi_version() != PK_ABI_VERSION:
         raise HipLibraryError(f"ABI version mismatch: library {lib.pk_abi_version()}, binding {PK_ABI_VERSION}")
     _lib = lib

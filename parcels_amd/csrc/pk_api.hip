@@ -22,6 +22,7 @@
 #include "pk_neighbors.h"
 #include "pk_interact.h"
 #include "pk_density.h"
+#include "pk_connectivity.h"
 #include "pk_host_stage.h"
 #include "pk_kernels.h"
 #include "pk_ux.h"
@@ -3304,6 +3305,83 @@ int32_t pk_particles_density(pk_ctx* ctx, int32_t grid_id, int32_t levels, int32
     c.perm = ctx->has_perm ? ctx->d_perm : nullptr;
     std::string msg;
     if (density_run(ctx->compute, ctx->grids[grid_id].d, c, levels, w, ncells, out, n_outside, info, &msg)) return ctx->fail(msg);
+    return 0;
+}
+
+// ---- labels of the bound rows and origin-to-destination counts (pk_connectivity.hip) ------------------------
+static int32_t conn_ready(pk_ctx* ctx, const char* who, int32_t grid_id, int32_t regions_dtype, const void* regions_host, int64_t ncells) {
+    const std::string w(who);
+    if (!ctx->bound) return ctx->fail(w + ": no particles bound");
+    if (ctx->in_flight) return ctx->fail(w + ": a launch is in flight (call pk_execute_end)");
+    if (grid_id < 0 || grid_id >= (int)ctx->grids.size()) return ctx->fail(w + ": unknown grid id");
+    if (ncells <= 0) return ctx->fail(w + ": ncells must be positive");
+    if (regions_host && regions_dtype != PK_DENSITY_I32 && regions_dtype != PK_DENSITY_I64)
+        return ctx->fail(w + ": regions_dtype must be PK_DENSITY_I32 or PK_DENSITY_I64");
+    return 0;
+}
+
+static DensityColumns conn_columns(pk_ctx* ctx) {
+    const DParticles& d = ctx->dev;  // the column set that is current (a launch leaves what it wrote there)
+    DensityColumns c;
+    c.n = d.n;
+    c.f32 = d.spatial_f32;
+    c.x = d.x; c.y = d.y; c.z = d.z;
+    c.perm = ctx->has_perm ? ctx->d_perm : nullptr;
+    return c;
+}
+
+int32_t pk_particles_cells(pk_ctx* ctx, int32_t grid_id, int32_t levels, int32_t regions_dtype, const void* regions_host, int64_t ncells,
+                           int64_t* labels_out) {
+    if (!ctx) return -2;
+    if (int32_t rc = conn_ready(ctx, "pk_particles_cells", grid_id, regions_dtype, regions_host, ncells)) return rc;
+    if (!labels_out && ctx->dev.n > 0) return ctx->fail("pk_particles_cells: labels_out is NULL");
+    ConnLabels l;
+    l.regions = regions_host;
+    l.regions_dtype = regions_dtype;
+    PK_HIP(ctx, hipSetDevice(ctx->device));
+    std::string msg;
+    if (cells_run(ctx->compute, ctx->grids[grid_id].d, conn_columns(ctx), levels, l, ncells, labels_out, &msg)) return ctx->fail(msg);
+    return 0;
+}
+
+int32_t pk_particles_connectivity(pk_ctx* ctx, int32_t grid_id, int32_t levels, int32_t regions_dtype, const void* regions_host, int64_t ncells,
+                                  int32_t origin_kind, int32_t origin_extra, int32_t origin_dtype, const void* origin_host, int64_t n_origin,
+                                  int64_t n_dest, int32_t path, int64_t* dense_out, int64_t* keys_out, int64_t* counts_out, int64_t max_pairs,
+                                  pk_connectivity_info_t* info) {
+    if (!ctx || !info) return -2;
+    if (int32_t rc = conn_ready(ctx, "pk_particles_connectivity", grid_id, regions_dtype, regions_host, ncells)) return rc;
+    if (origin_dtype != PK_DENSITY_I32 && origin_dtype != PK_DENSITY_I64)
+        return ctx->fail("pk_particles_connectivity: origin_dtype must be PK_DENSITY_I32 or PK_DENSITY_I64");
+    ConnLabels l;
+    l.regions = regions_host;
+    l.regions_dtype = regions_dtype;
+    l.origin_dtype = origin_dtype;
+    l.n_origin = n_origin;
+    l.n_dest = n_dest;
+    if (origin_kind == PK_DENSITY_W_EXTRA) {
+        if (origin_extra < 0 || origin_extra >= PK_MAX_EXTRA || !ctx->dev.extra[origin_extra])
+            return ctx->fail("pk_particles_connectivity: origin_extra must name a device Variable of the bound particles (pk_particles_desc.extra)");
+        if ((origin_dtype == PK_DENSITY_I32) != (ctx->dev.extra_f32[origin_extra] != 0))
+            return ctx->fail("pk_particles_connectivity: origin_dtype does not have the element size of the device Variable");
+        l.origin_dev = ctx->dev.extra[origin_extra];
+    } else if (origin_kind == PK_DENSITY_W_HOST) {
+        if (!origin_host && ctx->dev.n > 0) return ctx->fail("pk_particles_connectivity: PK_DENSITY_W_HOST needs origin_host");
+        l.origin_host = origin_host;
+    } else {
+        return ctx->fail("pk_particles_connectivity: origin_kind must be PK_DENSITY_W_EXTRA or PK_DENSITY_W_HOST");
+    }
+    if (path == PK_CONN_SPARSE) {
+        if (max_pairs < 0 || (max_pairs > 0 && (!keys_out || !counts_out))) return ctx->fail("pk_particles_connectivity: PK_CONN_SPARSE needs keys_out and counts_out with room for max_pairs");
+    } else if (path == PK_CONN_LDS || path == PK_CONN_GLOBAL) {
+        if (!dense_out && n_origin > 0) return ctx->fail("pk_particles_connectivity: PK_CONN_LDS / PK_CONN_GLOBAL need dense_out");
+    } else {
+        return ctx->fail("pk_particles_connectivity: path must be PK_CONN_LDS, PK_CONN_GLOBAL or PK_CONN_SPARSE");
+    }
+    PK_HIP(ctx, hipSetDevice(ctx->device));
+    std::string msg;
+    if (connectivity_run(ctx->compute, ctx->grids[grid_id].d, conn_columns(ctx), levels, l, ncells, path, dense_out, keys_out, counts_out, max_pairs, info,
+                         &msg))
+        return ctx->fail(msg);
     return 0;
 }
 

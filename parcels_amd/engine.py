@@ -1242,6 +1242,22 @@ def density_shape(grid, levels: bool) -> tuple:
     return ((dim("Z"),) if levels else ()) + lateral
 
 
+def _engine_make_current_for_reading(self, data):
+    """The device rows of `data` made current the way execute does it, for a call that only reads them (density, cells, connectivity)."""
+    if not (isinstance(data, LazyColumns) and data.resident() and data._engine is self):
+        # about to be bound: the device Variables of the last kernel list may belong to another ParticleSet's class (execute sets them
+        # from its kernels before it binds; there is no kernel here)
+        self.device_variables = [v for v in self.device_variables if v in data]
+    if isinstance(data, LazyColumns) and hasattr(self, "attach"):
+        self.attach(data)
+    else:
+        self.bind_particles(data)
+        self.h2d()
+
+
+DeviceEngine.make_current_for_reading = _engine_make_current_for_reading
+
+
 def _engine_density(self, data, igrid, levels=False, weight_var=None, weight_host=None):
     """Particles (or the sum of a weight) per cell of grid `igrid`, binned on the device-resident columns of `data` (pk_particles_density).
     The rows are made current the way execute does it -- columns the host touched are uploaded, a set that is not resident is bound and
@@ -1258,15 +1274,7 @@ def _engine_density(self, data, igrid, levels=False, weight_var=None, weight_hos
     n_out = C.c_int64(0)
     if n == 0:
         return out, 0, {"n_inside": 0, "n_atomics": 0, "bin_ms": 0.0, "sort_ms": 0.0, "sum_ms": 0.0}
-    if not (isinstance(data, LazyColumns) and data.resident() and data._engine is self):
-        # about to be bound: the device Variables of the last kernel list may belong to another ParticleSet's class (execute sets them
-        # from its kernels before it binds; there is no kernel here)
-        self.device_variables = [v for v in self.device_variables if v in data]
-    if isinstance(data, LazyColumns) and hasattr(self, "attach"):
-        self.attach(data)
-    else:
-        self.bind_particles(data)
-        self.h2d()
+    self.make_current_for_reading(data)
     kind, extra, code, host = _hip.PK_DENSITY_W_NONE, 0, 0, None
     if weight_var is not None:
         raw = data.raw(weight_var) if isinstance(data, LazyColumns) else data[weight_var]
@@ -1283,6 +1291,99 @@ def _engine_density(self, data, igrid, levels=False, weight_var=None, weight_hos
 
 
 DeviceEngine.density = _engine_density
+
+
+_LABEL_DTYPES = {np.dtype(np.int32): _hip.PK_DENSITY_I32, np.dtype(np.int64): _hip.PK_DENSITY_I64}
+CONNECTIVITY_LDS_BINS = 8192  # DENS_LDS_BINS of csrc/pk_density_cell.h: the keys a workgroup-private histogram holds
+_CONNECTIVITY_PATHS = {"lds": _hip.PK_CONN_LDS, "global": _hip.PK_CONN_GLOBAL, "sparse": _hip.PK_CONN_SPARSE}
+
+
+def connectivity_path(n_origin: int, n_dest: int, sparse: bool) -> int:
+    """Which way pk_particles_connectivity counts: the LDS histogram while the n_origin * (n_dest + 1) keys fit it, global adds for a larger
+    dense matrix, sort + run-length encode for a sparse result.  PK_CONNECTIVITY_PATH=lds|global|sparse forces one (tests, A/B runs)."""
+    forced = os.environ.get("PK_CONNECTIVITY_PATH")
+    if forced:
+        if forced not in _CONNECTIVITY_PATHS:
+            raise ValueError(f"PK_CONNECTIVITY_PATH must be one of {sorted(_CONNECTIVITY_PATHS)}. Got {forced!r}")
+        return _CONNECTIVITY_PATHS[forced]
+    if sparse:
+        return _hip.PK_CONN_SPARSE
+    return _hip.PK_CONN_LDS if n_origin * (n_dest + 1) <= CONNECTIVITY_LDS_BINS else _hip.PK_CONN_GLOBAL
+
+
+def _region_table(regions):
+    """(dtype code, contiguous int32 / int64 table) of a region map, or (0, None)"""
+    if regions is None:
+        return 0, None
+    table = np.ascontiguousarray(regions.ravel(), dtype=np.int32 if regions.dtype == np.int32 else np.int64)
+    return _LABEL_DTYPES[table.dtype], table
+
+
+def _engine_cells(self, data, igrid, levels=False, regions=None):
+    """The label of every row of `data` in host row order (pk_particles_cells): its cell of grid `igrid` by density's rule, or the entry of
+    that cell in `regions`; -1 = outside.  The rows are made current and read as density does: only the labels come back."""
+    ncells = int(np.prod(density_shape(self.grids[igrid], levels)))
+    n = len(data.raw("particle_id") if isinstance(data, LazyColumns) else data["particle_id"])
+    out = np.full(n, -1, np.int64)
+    if n == 0:
+        return out
+    self.make_current_for_reading(data)
+    code, table = _region_table(regions)
+    self.ctx.check(self.lib.pk_particles_cells(self.ctx.handle, int(self.grid_ids[igrid]), int(bool(levels)), code, _ptr(table), ncells, _ptr(out)),
+                   "pk_particles_cells")
+    return out
+
+
+DeviceEngine.cells = _engine_cells
+
+
+def _engine_connectivity(self, data, igrid, n_origin, n_dest, levels=False, regions=None, origin_var=None, origin_host=None, sparse=False):
+    """Rows per (origin, destination) pair (pk_particles_connectivity).  origin_var: an int32 / int64 particle Variable (a device-resident
+    one is read in place, any other is current on the host); origin_host: int32 / int64 labels in host row order.  Returns (keys, counts,
+    info): the non-zero keys origin * (n_dest + 1) + d in ascending order (d = n_dest: outside) with their counts -- or, not sparse,
+    (matrix of shape (n_origin, n_dest + 1), None, info)."""
+    ncells = int(np.prod(density_shape(self.grids[igrid], levels)))
+    n = len(data.raw("particle_id") if isinstance(data, LazyColumns) else data["particle_id"])
+    path = connectivity_path(n_origin, n_dest, sparse)
+    info = _hip.ConnectivityInfo()
+    info.path = path
+    dense = keys = counts = None
+    if path == _hip.PK_CONN_SPARSE:
+        keys, counts = np.empty(n, np.int64), np.empty(n, np.int64)  # (n is always enough room; only the pairs found are written)
+    else:
+        dense = np.zeros(n_origin * (n_dest + 1), np.int64)
+    if n:
+        self.make_current_for_reading(data)
+        kind, extra, host = _hip.PK_DENSITY_W_HOST, 0, origin_host
+        if origin_var is not None:
+            raw = data.raw(origin_var) if isinstance(data, LazyColumns) else data[origin_var]
+            if origin_var in getattr(self, "_bound_devvars", ()):
+                kind, extra, host = _hip.PK_DENSITY_W_EXTRA, self._bound_devvars.index(origin_var), None
+                odt = raw.dtype
+            else:  # a host-only Variable: no launch writes it, its host array is current
+                host = raw
+        if host is not None:
+            host = np.ascontiguousarray(host)
+            odt = host.dtype
+        code, table = _region_table(regions)
+        self.ctx.check(self.lib.pk_particles_connectivity(self.ctx.handle, int(self.grid_ids[igrid]), int(bool(levels)), code, _ptr(table), ncells, kind, int(extra),
+                                                          _LABEL_DTYPES[odt], _ptr(host), int(n_origin), int(n_dest), path, _ptr(dense), _ptr(keys),
+                                                          _ptr(counts), n, C.byref(info)), "pk_particles_connectivity")
+    out = {k: getattr(info, k) for k, _ in _hip.ConnectivityInfo._fields_ if k != "reserved0"}
+    out["path"] = {v: k for k, v in _CONNECTIVITY_PATHS.items()}[path]
+    if path == _hip.PK_CONN_SPARSE:
+        keys, counts = keys[: info.n_pairs], counts[: info.n_pairs]
+        if sparse:
+            return keys, counts, out
+        dense = np.zeros(n_origin * (n_dest + 1), np.int64)  # (a forced path: the pairs scattered into the dense matrix)
+        dense[keys] = counts
+    elif sparse:  # (a forced path: the non-zero entries of the dense matrix are the pairs)
+        keys = np.flatnonzero(dense)
+        return keys, dense[keys], out
+    return dense.reshape(n_origin, n_dest + 1), None, out
+
+
+DeviceEngine.connectivity = _engine_connectivity
 
 
 def raise_particle_errors(data: dict, first_code=None):

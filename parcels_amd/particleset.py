@@ -341,6 +341,143 @@ class ParticleSet:
             out = out / (areas if not levels else areas[None])
         return (out, n_outside) if return_outside else out
 
+    def _label_query(self, what, field, levels, regions):
+        """The checks cells and connectivity share, raised before the device is touched -> (index of the grid, regions as an array or None)."""
+        from .engine import density_shape
+        from .field import Field, VectorField
+
+        if self._shard is not None:
+            raise NotImplementedError(f"ParticleSet.{what} on a sharded (multi-process) ParticleSet: the per-rank results are not combined over the ranks yet")
+        fs = self.fieldset
+        if field is None:
+            field = "U"
+        if isinstance(field, str):
+            if field not in fs.fields:
+                raise ValueError(f"{what}: the FieldSet has no field {field!r}")
+            field = fs.fields[field]
+        elif not isinstance(field, (Field, VectorField)):
+            raise TypeError(f"{what}: field must be a Field, a VectorField, a field name or None. Got {type(field).__name__}")
+        grids = fs.gridset
+        if fs.fields.get(field.name) is not field or not any(g is field.grid for g in grids):
+            raise ValueError(f"{what}: field {field.name!r} is not a field of this ParticleSet's FieldSet")
+        igrid = next(i for i, g in enumerate(grids) if g is field.grid)
+        if regions is not None:
+            regions = np.asarray(regions)
+            shape = density_shape(field.grid, bool(levels))
+            if regions.dtype.kind not in "iu":
+                raise TypeError(f"{what}: regions is {regions.dtype}; region labels must be integers")
+            if regions.shape != shape:
+                raise ValueError(f"{what}: regions has shape {regions.shape}, expected {shape} -- one label per cell of the grid")
+            if regions.dtype == np.uint64 and regions.size and int(regions.max()) >= 2**63:
+                raise ValueError(f"{what}: regions holds a label of 2**63 or more")
+        return igrid, regions
+
+    def _label_engine(self, what):
+        eng = self._engine()
+        if getattr(eng, "comm", None) is not None:
+            raise NotImplementedError(f"ParticleSet.{what} in a multi-process run: the per-rank results are not combined over the ranks yet")
+        return eng
+
+    def cells(self, field=None, *, levels=False, regions=None):
+        """Where every particle is now: an int64 array of ``len(pset)`` labels in row order, found on the GPU from the device-resident columns.
+
+        Without ``regions`` the label is the ravelled cell of the field's grid by the rule of ``density`` (``field`` and ``levels`` as there:
+        the cell ``grid.search(z, y, x)`` without a guess answers, over ``density_shape(grid, levels)``).  A particle whose search answers an
+        error code, or one of whose coordinates the search reads is not finite, is outside and gets -1.  ``regions``: an integer array of
+        exactly that shape that labels every cell (basins, reefs, protected areas); the label of a particle is then the label of its cell,
+        and a negative label means "no region" and gives -1.
+
+        Assign the result to an int32 or int64 particle Variable at release time to record origins for ``connectivity``: the Variable is a
+        particle column, so it follows deletions, additions and the cell sort.  Like ``density`` the call only reads the particles:
+        columns the host changed are uploaded as ``execute`` would, only the labels come back, nothing is downloaded or marked, and
+        ``execute -> cells -> execute`` gives the bits of ``execute -> execute``."""
+        igrid, regions = self._label_query("cells", field, levels, regions)
+        return self._label_engine("cells").cells(self._data, igrid, levels=bool(levels), regions=regions)
+
+    def connectivity(self, origin, field=None, *, regions=None, levels=False, n_origin=None, sparse=False, normalize=None, return_outside=False,
+                     max_dense=2**26):
+        """Of the particles that started in region i, how many are in region j now: the connectivity (transition) matrix, counted on the GPU.
+
+        ``origin``: the name of an int32 / int64 particle Variable (a device-resident one is read in place) or an integer array of
+        ``len(pset)`` labels in row order -- for example what ``cells`` answered at release time.  A negative origin means "not tracked":
+        the row is counted nowhere.  A label ``>= n_origin`` is a ValueError.  The destination of a row is what
+        ``cells(field, levels=levels, regions=regions)`` answers for it now; ``n_dest = regions.max() + 1`` with ``regions``, else the number
+        of cells, and ``n_origin`` defaults to ``n_dest``.
+
+        Dense (default): an int64 array ``T`` of shape ``(n_origin, n_dest)``, ``T[i, j]`` = rows with origin i and destination j; refused
+        when ``n_origin * n_dest > max_dense``.  ``sparse=True``: ``(i, j, count)``, three int64 arrays with the non-zero pairs sorted by
+        ``(i, j)`` -- ``np.unique(origin * n_dest + dest, return_counts=True)`` split with ``divmod``.  ``return_outside=True`` also returns
+        the tracked rows of each origin that are in no destination, as a second result: an int64 array of shape ``(n_origin,)``, or
+        ``(i_out, count_out)`` with ``sparse``.  ``normalize="origin"`` divides every row by its sum over the inside columns (float64; rows that sum to 0 stay 0).
+
+        Like ``density`` the call only reads the particles; ``pset._last_connectivity_info`` keeps what the library reports."""
+        n = len(self)
+        igrid, regions = self._label_query("connectivity", field, levels, regions)
+        if normalize not in (None, "origin"):
+            raise ValueError(f"connectivity: normalize must be None or 'origin'. Got {normalize!r}")
+        origin_var = origin_host = None
+        if isinstance(origin, str):
+            if not any(v.name == origin for v in self._pclass.variables):
+                raise ValueError(f"connectivity: the particle class has no Variable {origin!r}")
+            d = self._data
+            dt = (d.raw(origin) if isinstance(d, LazyColumns) else d[origin]).dtype
+            if dt not in (np.int32, np.int64) or origin == "ei":
+                raise TypeError(f"connectivity: Variable {origin!r} is {dt}; origin labels must be int32 or int64")
+            origin_var = origin
+        else:
+            o = np.asarray(origin)
+            if o.ndim != 1 or o.shape[0] != n:
+                raise ValueError(f"connectivity: origin has shape {o.shape}, expected ({n},) -- one label per particle in row order")
+            if o.dtype.kind not in "iu":
+                raise TypeError(f"connectivity: origin is {o.dtype}; origin labels must be integers")
+            if o.dtype == np.uint64 and o.size and int(o.max()) >= 2**63:
+                raise ValueError("connectivity: origin holds a label of 2**63 or more")
+            origin_host = o if o.dtype == np.int32 else o.astype(np.int64, copy=False)
+        from .engine import density_shape
+
+        grid = self.fieldset.gridset[igrid]
+        n_dest = int(np.prod(density_shape(grid, bool(levels)))) if regions is None else (int(regions.max()) + 1 if regions.size else 0)
+        n_dest = max(n_dest, 0)
+        n_origin = n_dest if n_origin is None else int(n_origin)
+        if n_origin < 0:
+            raise ValueError(f"connectivity: n_origin must not be negative. Got {n_origin}")
+        if sparse:
+            if n_origin * (n_dest + 1) >= 2**62:
+                raise ValueError(f"connectivity: n_origin = {n_origin} times n_dest + 1 = {n_dest + 1} does not fit the 62-bit pair key")
+        elif n_origin * n_dest > max_dense:
+            raise ValueError(f"connectivity: a dense matrix of n_origin = {n_origin} by n_dest = {n_dest} has more than max_dense = {max_dense} entries; "
+                             "use sparse=True")
+        eng = self._label_engine("connectivity")
+        if origin_var in COLUMN_BITS_NAMES:  # a built-in column (particle_id ...): lives on the device as a column of its own, read through the mirror
+            origin_host, origin_var = readonly(self._data)[origin_var], None
+        keys, counts, info = eng.connectivity(self._data, igrid, n_origin, n_dest, levels=bool(levels), regions=regions, origin_var=origin_var,
+                                              origin_host=origin_host, sparse=bool(sparse))
+        self._last_connectivity_info = info
+        if info["n_above"]:
+            raise ValueError(f"connectivity: {info['n_above']} rows have an origin label >= n_origin = {n_origin}")
+        if not sparse:
+            t, outside = keys[:, :n_dest], keys[:, n_dest].copy()
+            if normalize:
+                total = t.sum(axis=1, keepdims=True)
+                t = np.divide(t, total, out=np.zeros(t.shape, np.float64), where=total != 0)
+            else:
+                t = np.ascontiguousarray(t)
+            return (t, outside) if return_outside else t
+        i = keys // (n_dest + 1)  # (divmod, in the form NumPy runs fastest: the pairs may be millions)
+        j = keys - i * (n_dest + 1)
+        outside = np.flatnonzero(j == n_dest)
+        io, co = i[outside], counts[outside]
+        if outside.size:
+            inside = np.ones(keys.size, bool)
+            inside[outside] = False
+            i, j, counts = i[inside], j[inside], counts[inside]
+        elif counts.base is not None:
+            counts = counts.copy()  # (not a view of the engine's n-sized buffer)
+        if normalize:
+            _, row = np.unique(i, return_inverse=True)  # (the rows that occur: n_origin may be far larger than the number of pairs)
+            counts = counts / np.bincount(row, weights=counts)[row] if i.size else counts.astype(np.float64)
+        return ((i, j, counts), (io, co)) if return_outside else (i, j, counts)
+
     # -- the outer time loop (particleset.py:355-470) ------------------------------------------------------------
     def execute(self, kernels, dt, endtime=None, runtime=None, output_file=None, verbose_progress=False):
         # A multi-rank ParticleFile makes write() a collective: every rank must then make the SAME sequence of write() calls at the
