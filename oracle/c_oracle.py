@@ -28,6 +28,8 @@ KERNEL_IDS = {
     "AdvectionDiffusionEM": 8,
     "DiffusionUniformKh": 9,
     "SampleField": 10,
+    "AdvectionRK2_3D_CROCO": 11,
+    "SampleSigmaCroco": 12,
     "DoNothing": 23,
     "MoveEast": 24,
     "MoveNorth": 25,
@@ -39,6 +41,21 @@ KERNEL_IDS = {
 SCALAR_INTERP = {"XLinear": 0, "XConstantField": 1, "XNearest": 2, "CGrid_Tracer": 3, "XLinearInvdistLandTracer": 4}
 
 EARTH_RADIUS = 6366707.019493707  # mesh.py:6
+
+# po_params.sig_variant: ONE deliberately wrong restatement of the CROCO kernels each (tests/test_croco_oracle.py: sensitivity)
+CROCO_VARIANTS = {None: 0, "wrap_as_level_0": 1, "fallback_n_minus_1": 2, "zvec_without_zeta": 3, "w2_times_sigma": 4, "stage2_at_t": 5,
+                  "detached_h_with_guess": 6, "float64_arithmetic": 7}
+
+
+def croco_sample(kernel_name):
+    """(field, Variable) of a sigma-level sampling kernel of a CROCO case (tools/make_croco_golden.py: `SampleOmegaCroco`,
+    `SampleFieldCroco:<field>:<var>`, and the host recipe `HostRecipe:<field>:<var>`, the same text as a Python kernel), else None"""
+    if kernel_name == "SampleOmegaCroco":
+        return "omega", "omega"
+    if kernel_name.startswith(("SampleFieldCroco:", "HostRecipe:")):
+        _, field, var = kernel_name.split(":")
+        return field, var
+    return None
 
 
 class PoGrid(C.Structure):
@@ -146,6 +163,15 @@ class PoParams(C.Structure):
         ("dres", C.c_double),
         ("seed", C.c_uint64),
         ("twe_key", C.c_int64 * PO_MAX_TWE),
+        ("fh", C.c_int32),
+        ("fzeta", C.c_int32),
+        ("sig_n", C.c_int32),
+        ("sig_cs_f32", C.c_int32),
+        ("sig_variant", C.c_int32),
+        ("pad2", C.c_int32),
+        ("hc", C.c_double),
+        ("sig_s", C.c_void_p),
+        ("sig_cs", C.c_void_p),
     ]
 
 
@@ -173,6 +199,31 @@ def lib():
         assert _LIB.po_sizeof(2) == C.sizeof(PoParticles)
         assert _LIB.po_sizeof(3) == C.sizeof(PoParams)
     return _LIB
+
+
+_COS64 = C.CFUNCTYPE(C.c_double, C.c_double)(lambda a: float(np.cos(np.array([a, a]))[0]))  # (an array: the vectorised loop, not the scalar path)
+_COS32 = C.CFUNCTYPE(C.c_float, C.c_float)(lambda a: float(np.cos(np.array([a, a], dtype=np.float32))[0]))
+
+
+def _sincos(lat, lon, out):
+    a = np.array([lon, lat, lon, lat])
+    out[0], out[1] = np.cos(a[:2])
+    out[2], out[3] = np.sin(a[2:])
+
+
+_SINCOS64 = C.CFUNCTYPE(None, C.c_double, C.c_double, C.POINTER(C.c_double))(_sincos)
+
+
+class numpy_trig:
+    """with numpy_trig(): the oracle takes the cosine of a velocity's unit conversion and the sines / cosines of the curvilinear search's
+    unit-sphere points from NumPy, as the reference does -- for the
+    comparisons made bit for bit with the live reference on spherical meshes (single-threaded calls only).  Elsewhere: the C library's."""
+
+    def __enter__(self):
+        lib().po_set_cos(_COS64, _COS32, _SINCOS64)
+
+    def __exit__(self, *exc):
+        lib().po_set_cos(None, None, None)
 
 
 def _ptr(a):
@@ -378,7 +429,14 @@ class MarshalledCase:
         self.sample_vars = []
         for i, k in enumerate(kernels):
             p.sample_field[i] = p.sample_var[i] = -1
-            if k in samples:  # the user kernel `particles.<var> = fieldset.<F>[particles]`
+            cs = croco_sample(k)
+            if cs is not None:  # SampleOmegaCroco and its per-field form (kernels/_sigmagrids.py:28-35)
+                if cs[1] not in self.sample_vars:
+                    self.sample_vars.append(cs[1])
+                p.kernels[i] = KERNEL_IDS["SampleSigmaCroco"]
+                p.sample_field[i] = self.field_index[cs[0]]
+                p.sample_var[i] = self.sample_vars.index(cs[1])
+            elif k in samples:  # the user kernel `particles.<var> = fieldset.<F>[particles]`
                 fname, vname, _ = samples[k]
                 cols = []
                 for vn in sample_names(vname):
@@ -407,6 +465,18 @@ class MarshalledCase:
         p.rk45_max_dt = float(context.get("RK45_max_dt", 0.0))
         p.dres = float(context.get("dres", 0.0))
         p.seed = int(seed)
+        p.fh = p.fzeta = -1
+        if "hc" in context and "Cs_w" in fi:  # a CROCO fieldset (kernels/_sigmagrids.py reads h, zeta, Cs_w, hc and U.grid.depth)
+            p.fh, p.fzeta = fi.get("h", -1), fi.get("zeta", -1)
+            cs = np.asarray(case["fields"]["Cs_w"])
+            self.sig_s = np.ascontiguousarray(case["depth"], dtype=np.float64)
+            self.sig_cs = np.ascontiguousarray(cs.reshape(-1), dtype=np.float64)  # (exact: float32 values are float64 values)
+            assert self.sig_s.shape == self.sig_cs.shape
+            p.sig_n = len(self.sig_s)
+            p.sig_cs_f32 = int(cs.dtype == np.float32)
+            p.sig_variant = CROCO_VARIANTS[case.get("variant")]
+            p.hc = float(context["hc"])
+            p.sig_s, p.sig_cs = _ptr(self.sig_s), _ptr(self.sig_cs)
         return p
 
 
@@ -460,6 +530,9 @@ def initial_particles(case: dict, ngrids: int) -> dict:
         for vn in sample_names(vname):
             if vn is not None:
                 d[vn] = np.zeros(n, np.dtype(vdt))
+    for k in case["kernels"]:
+        if croco_sample(k) is not None:
+            d[croco_sample(k)[1]] = np.zeros(n, np.float64)
     return d
 
 
@@ -592,6 +665,19 @@ def sample_case(case: dict):
                        None, None, _ptr(st))
     assert rc == 0
     return {"value": out, "state": st}
+
+
+def sigma_points(case: dict, t, z, y, x, variant=None):
+    """convert_z_to_sigma_croco(fieldset, t, z, y, x, None) (kernels/_sigmagrids.py:6-25) at explicit points through po_sigma_points.
+    The reference raises for the whole call when a t lies outside zeta's time interval; such points get NaN here."""
+    mc = MarshalledCase(dict(case, variant=variant))
+    t, z, y, x = (np.ascontiguousarray(a, dtype=np.float64) for a in (t, z, y, x))
+    m = x.shape[0]
+    out = np.zeros(m)
+    prm = mc.params(kernels=[], endtime=0.0, dt0=1.0, context=case.get("context"))
+    rc = lib().po_sigma_points(mc.grids, mc.fields, C.byref(prm), C.c_int64(m), _ptr(t), _ptr(z), _ptr(y), _ptr(x), _ptr(out))
+    assert rc == 0
+    return out
 
 
 ERRORS_TO_THROW = [  # kernel.py:31-38 (order matters)

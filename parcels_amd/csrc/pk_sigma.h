@@ -62,8 +62,9 @@ PK_DEV double croco_sigma(const pk_tab2* tab, const SigmaA& S, double h, bool h3
 
 // Field.eval of a scalar field, attached or detached (see the head of this file).  v32: the value is a float32 array in the reference.
 // The attached form is eval_scalar (pk_device.h) without the search memo.
+// left_time (optional): set when THIS attached sample lies outside the field's time interval.
 PK_DEV double sig_eval(const KArgs& a, const Coords& mc, PCtx& c, int fidx, double t, double z, double y, double x, bool pos_f32, bool detached,
-                       bool& v32) {
+                       bool& v32, bool* left_time = nullptr) {
     const DField& f = kfield(a, fidx);
     const DGrid& g = kgrid(a, f.grid);
     v32 = false;
@@ -86,12 +87,14 @@ PK_DEV double sig_eval(const KArgs& a, const Coords& mc, PCtx& c, int fidx, doub
             if (li >= 0) {  // (see eval_uvw)
                 twe_justify(a, li, t, f.tlen);
                 c.state = PK_ERROROUTSIDETIMEINTERVAL;
+                if (left_time) *left_time = true;
                 return 0.0;
             }
         }
         if (!time_search(f, time, t, on_main ? c.ht : 0, p)) {
             c.state = PK_ERROROUTSIDETIMEINTERVAL;
             twe_note_all(a, c.it, klo);
+            if (left_time) *left_time = true;
             return 0.0;
         }
         const bool use_guess = take_first_eval(c, f.grid) ? (a.prm.have_guess0 != 0) : true;
@@ -130,6 +133,13 @@ struct SigLocal {
 };
 
 PK_DEV bool is_croco_id(int kid) { return kid == PK_KERNEL_ADVECTION_RK2_3D_CROCO || kid == PK_KERNEL_SAMPLE_SIGMA_CROCO; }
+// the stages whose sample is one of convert_z_to_sigma_croco's `fieldset.h.eval(...)` / `fieldset.zeta.eval(...)` (_sigmagrids.py:12-13): called
+// directly, not through Field.__getitem__, so an OutsideTimeInterval there is not turned into a status code (field.py:187-195) but leaves the
+// kernel and ParticleSet.execute -- no kernel later in the list (DeleteParticle, say) gets to see the particle
+PK_DEV bool is_conversion_stage(int kid, int stage) {
+    if (kid == PK_KERNEL_SAMPLE_SIGMA_CROCO) return stage <= 1;
+    return stage == 1 || stage == 2 || stage == 7 || stage == 8;
+}
 
 // prepare() of the two CROCO kernels: true when the kernel is finished
 PK_DEV bool croco_prepare(const KArgs& a, int kid, int stage, int kslot, PCtx& c, PState& p, KLocal& L, Request& rq, SigRq& sq) {
@@ -305,7 +315,8 @@ __global__ void __launch_bounds__(256, PK_SIGMA_MIN_WAVES) advect_sigma_kernel(c
                 it++;
                 c.it = body ? 0u : it;
                 p.dt = dtc;
-                for (int k = 0; k < prm.nk; k++) {  // kernel.py:206-216
+                bool raised = false;  // (see is_conversion_stage)
+                for (int k = 0; k < prm.nk && !raised; k++) {  // kernel.py:206-216
                     const int kid = prm.kernels[k];
                     const bool croco = is_croco_id(kid);
                     c.klo = k * 1000;
@@ -323,12 +334,14 @@ __global__ void __launch_bounds__(256, PK_SIGMA_MIN_WAVES) advect_sigma_kernel(c
                             double u, v = 0.0, w = 0.0;
                             bool v32 = false;
                             c.zpos_f32 = rq.zf32;
-                            if (rq.kind == RQ_SCALAR) u = sig_eval(a, mc, c, rq.fidx, rq.t, rq.z, rq.y, rq.x, rq.f32, croco && sq.detached, v32);
+                            if (rq.kind == RQ_SCALAR) u = sig_eval(a, mc, c, rq.fidx, rq.t, rq.z, rq.y, rq.x, rq.f32, croco && sq.detached, v32, &raised);
                             else eval_uvw<FT, KIND, INTERP, false>(a, mc, c, rq.kind == RQ_UVW, rq.t, rq.z, rq.y, rq.x, rq.f32, u, v, w);
+                            if (raised && !(croco && is_conversion_stage(kid, stage))) raised = false;
+                            if (raised) break;  // the exception of the reference: the state stays ErrorOutsideTimeInterval
                             if (croco) croco_consume(a, tab, kid, stage, c, p, L, sl, u, v, v32);
                             else consume(kid, stage, c, L, u, v, w);
                         }
-                    } while (c.state == PK_REPEAT);
+                    } while (c.state == PK_REPEAT && !raised);
                 }
                 if (body) break;
                 if (c.state == PK_EVALUATE || c.state == PK_SUCCESS) {  // :219-222

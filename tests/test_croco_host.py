@@ -17,7 +17,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURES = sorted(glob.glob(os.path.join(mg.GOLDEN, "croco_*.npz")))
 REQUIRED = ["croco_rect_flat_f64data_f64part", "croco_rect_flat_f64data_f32part", "croco_rect_flat_f32data_f64part", "croco_rect_flat_f32data_f32part",
             "croco_curv_flat_f32data_f64part", "croco_curv_flat_f32data_f32part", "croco_rect_sph_f64", "croco_edges", "croco_edges_delete",
-            "croco_backward", "croco_outputdt", "croco_rk2_2d", "croco_sample_tracer", "croco_sigma_points", "croco_host_recipe"]
+            "croco_backward", "croco_outputdt", "croco_rk2_2d", "croco_sample_tracer", "croco_sigma_points", "croco_host_recipe",
+            "croco_curv_flat_f64data_f64part", "croco_curv_sph_f32data_f64part", "croco_agrid_rect_f64", "croco_agrid_curv_f32", "croco_two_levels",
+            "croco_many_levels", "croco_three_waves"]
 
 
 def croco_dataset(coords, fields):
