@@ -129,6 +129,9 @@ const char* pk_last_error(const pk_ctx* ctx); /* ctx may be NULL: error of the l
  *                      cache or the launch fails (3-D advection, a list with compiled user kernels, tables too large).  In the library's
  *                      2-D kernel 0 and 2 run one arithmetic and agree in every bit; PK_NO_BLOCK_CACHE (environment) = no cache at all,
  *                      with the lerps in the reference's order
+ *   "fast_grid"        workgroups of the persistent launch of the level-pair-cache kernel, whose wavefronts claim chunks of 64 rows until none is
+ *                      left (csrc/pk_kernels.h: fast_persistent): 0 (default) as many as are resident at once, v > 0 at most v (tests and
+ *                      sweeps: results do not depend on it)
  * Environment variables PK_NO_FAST, PK_NO_FAST_CGRID, PK_NO_VELOCITY_PAIRS, PK_NO_SPECIAL, PK_NO_CELL_CACHE, PK_NO_HASH_DIR, PK_NO_CELL_TABLE, PK_SORT_HORIZONTAL give the initial
  * values. */
 int32_t pk_set_option(pk_ctx* ctx, const char* name, int32_t value);

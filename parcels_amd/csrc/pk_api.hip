@@ -202,6 +202,7 @@ struct pk_ctx {
     int no_fast_cgrid = 0;
     bool no_block_cache = false;  // PK_NO_BLOCK_CACHE: the 2-D A-grid kernel without its per-lane corner-block cache
     int block_cache = -1;         // option "block_cache": -1 plan_launch's rule, 0 none, 1 stage-pair block, 2 level-pair cache or fail
+    int fast_grid = 0;            // option "fast_grid": workgroups of the persistent A-grid launch -- 0 what is resident at once (pk_kernels.h), v > 0 at most v
     // asynchronous write-out snapshots (pk_particles_snapshot_begin / _wait): two sets of device staging columns (host row order)
     // + pinned host columns, so that the D2H and the encode of interval k overlap the launch of interval k+1
     struct Snapshot {
@@ -761,6 +762,10 @@ int32_t pk_set_option(pk_ctx* ctx, const char* name, int32_t value) {
     else if (n == "block_cache") {
         if (value < -1 || value > 2) return ctx->fail("pk_set_option: block_cache is -1 (planned), 0 (none), 1 (stage-pair block) or 2 (level-pair cache)");
         ctx->block_cache = value;
+    }
+    else if (n == "fast_grid") {
+        if (value < 0) return ctx->fail("pk_set_option: fast_grid is 0 (planned) or the largest number of workgroups of the persistent A-grid launch");
+        ctx->fast_grid = value;
     }
     else return ctx->fail("pk_set_option: unknown option '" + n + "'");
     return 0;
@@ -2598,7 +2603,7 @@ int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
     for (int k = 1; k < prm->twe_n; k++)
         if (!(prm->twe_key[k - 1] < prm->twe_key[k])) return ctx->fail("params.twe_key must be ascending");
     DCounters& counters0 = ctx->h_counters0;
-    counters0 = DCounters{0ull, 0ull, 0ull, 0xFFFFFFFFu, 0u, ~0ull, 0u, 0u};
+    counters0 = DCounters{0ull, 0ull, 0ull, 0xFFFFFFFFu, 0u, ~0ull, 0u, 0u, {}, {}};  // (cursor: the persistent launch claims from chunk 0 of every share)
     PK_HIP(ctx, hipMemcpyAsync(ctx->d_counters, &counters0, sizeof(DCounters), hipMemcpyHostToDevice, ctx->compute));
     PK_HIP(ctx, hipMemsetAsync(ctx->d_twe_found, 0, sizeof(unsigned long long) * TWE_FOUND_SLOTS, ctx->compute));
     if (prm->twe_n > 0) PK_HIP(ctx, hipMemsetAsync(ctx->d_twe_hit, 0, sizeof(unsigned int) * prm->twe_n, ctx->compute));
@@ -2661,7 +2666,7 @@ int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
         if (p.ride) ctx->user_launch(&a, p.kernel, field_f32 * 2 + pf32, 1, (uint64_t)p.lds, (void*)ctx->compute);
         else switch (p.kernel) {
             case DEDICATED_A2:
-                if (p.lp != FAST_LP_OFF) PK_HIP(ctx, launch_fast_lp(p.lp, field_f32, pf32, a, p.lds, ctx->compute));
+                if (p.lp != FAST_LP_OFF) PK_HIP(ctx, launch_fast_lp(p.lp, field_f32, pf32, a, p.lds, ctx->prop.multiProcessorCount, ctx->fast_grid, ctx->compute));
                 else launch_fast<PROG_RK4>(field_f32, pf32, a, grid, p.lds, ctx->compute);
                 break;
             case DEDICATED_A3: launch_fast<PROG_RK4_3D>(field_f32, pf32, a, grid, p.lds, ctx->compute); break;

@@ -96,7 +96,13 @@ struct DCounters {
     unsigned int err_iter, pad;  // smallest iteration index (1-based) in which a particle entered an error state; 0xFFFFFFFF = none
     unsigned long long twe_key;  // smallest key of a sample (pk_exec_params.twe_key) at which a particle left a time interval; ~0 = none
     unsigned int twe_overflow, pad2;  // keys that found no slot in KArgs::twe_found (the host then trusts only twe_key)
+    // persistent A-grid launch (pk_kernels.h: fast_claim): 64-row chunks handed out so far from each XCD's share, cursor[x * PK_CURSOR_STRIDE].  One
+    // 128-byte line per share, away from the line of the counters above: atomics on one line are served one after the other, chip-wide
+    unsigned int pad3[20];  // (the counters fill 48 bytes; device allocations start on a line)
+    unsigned int cursor[8 * 32];
 };
+constexpr int PK_CURSOR_STRIDE = 32;
+static_assert(offsetof(DCounters, cursor) == 128, "the cursors start on a line of their own");
 
 // Wave-uniform constants of the fast path for XLinear_Velocity on a rectilinear A-grid with float64 coordinates
 // (pk_fast_agrid.h), folded from the grid / field descriptors by the host (pk_api.hip: fill_fast).

@@ -388,12 +388,57 @@ PK_DEV unsigned long long wave_sum(unsigned long long v) {
     return v;
 }
 
+PK_DEV unsigned long long uniform_u64(unsigned long long v) {  // a value every lane holds, in scalar registers
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+
 // blockIdx -> logical tile: the dispatcher places block b on XCD b % 8 (MI355X_MICROARCH.md); give every XCD a
 // contiguous range of (cell-sorted) particles so that its private L2 sees one compact region of the fields.
 PK_DEV unsigned xcd_swizzle(unsigned bid, unsigned nb) {
     const unsigned xcd = bid & 7u, j = bid >> 3;
     const unsigned per = nb >> 3, rem = nb & 7u;
     return xcd * per + (xcd < rem ? xcd : rem) + j;
+}
+
+// ---- persistent launch of advect_fast_kernel<.., FAST_LP_CACHE> ---------------------------------------------------------------------------
+// The one-shot launch cuts n rows into ceil(n / 512) workgroups of 8 wavefronts.  A workgroup's wave slots and its LDS are free again only when
+// its SLOWEST wavefront is done (the run time of a wavefront goes with its count of missing wave-evaluations), and every workgroup stages the
+// coordinate tables again and waits at the barrier behind them.  The persistent launch starts only as many workgroups as are resident at once
+// (pk_api.hip: plan_launch); each WAVEFRONT then claims chunks of 64 consecutive rows until none is left and runs the kernel's body on each.
+// Nothing ever waits on another workgroup or wavefront, so a grid smaller or larger than what is resident only costs speed.
+//   * Locality as xcd_swizzle gives it: XCD x = blockIdx.x & 7 owns a contiguous eighth of the chunks and walks it upwards through
+//     DCounters::cursor[x * PK_CURSOR_STRIDE] (a line of its own per share, zeroed with the launch's counters).  A wavefront whose share is used up takes from the following XCDs' shares -- the
+//     tail balance -- and leaves once all eight are: at most eight failed claims, no spinning.
+//   * A claim is one returning atomicAdd by the wavefront's first lane, broadcast through readfirstlane: the chunk and the share state stay in
+//     scalar registers, the row is chunk * 64 + lane.
+//   * A wavefront adds its steps / attempts / paused sums to the launch counters once, when it leaves (kept in scalar registers meanwhile).
+// Which lane of which wavefront steps a particle changes nothing a particle computes: every column is what the one-shot launch writes.
+// PK_FAST_PERSISTENT=0: the one-shot launch and its machine code (A/B builds).  The other instantiations of the kernel never loop.
+#ifndef PK_FAST_PERSISTENT
+#define PK_FAST_PERSISTENT 1
+#endif
+#ifdef PK_USER_KERNELS
+constexpr bool fast_persistent(int) { return false; }
+#else
+constexpr bool fast_persistent(int lp) { return PK_FAST_PERSISTENT != 0 && lp == FAST_LP_CACHE; }
+#endif
+constexpr int FAST_CHUNK = 64;  // rows per claim: one wavefront
+// -> the next chunk of this wavefront, false when every share is used up.  `tried` (wave-uniform, 0 at entry of the kernel): shares found empty so far.
+PK_DEV bool fast_claim(DCounters* cnt, unsigned nchunks, unsigned& tried, unsigned& chunk) {
+    const unsigned per = nchunks >> 3, rem = nchunks & 7u;
+    while (tried < 8u) {
+        const unsigned s = (blockIdx.x + tried) & 7u;
+        unsigned k = 0u;
+        if ((threadIdx.x & 63) == 0) k = atomicAdd(&cnt->cursor[s * PK_CURSOR_STRIDE], 1u);
+        k = (unsigned)__builtin_amdgcn_readfirstlane((int)k);
+        if (k < per + (s < rem ? 1u : 0u)) {
+            chunk = s * per + (s < rem ? s : rem) + k;  // (the share's first chunk as in xcd_swizzle)
+            return true;
+        }
+        tried++;
+    }
+    return false;
 }
 
 // KID: compile-time kernel id of a single-kernel program, or -1 for the kernel-list interpreter
@@ -723,144 +768,176 @@ __global__ void __launch_bounds__(fast_wg(LP), PK_MIN_WAVES_FAST) advect_fast_ke
         ft.fl = fast_flags(a.fast) | ((a.win_lo > -INFINITY || a.win_hi < INFINITY) ? FA_WIN : 0u) | (a.prm.dt0 > 0 ? FA_FWD : 0u) |
                 (a.prm.max_iters > 0 ? FA_MAXIT : 0u);
     }
+    // the persistent launch (fast_persistent, above): this wavefront's chunk of 64 rows and the shares it found empty, in scalar registers
+    constexpr bool PERS = fast_persistent(LP);
+    [[maybe_unused]] unsigned chunk = 0u, tried = 0u;
+    [[maybe_unused]] const unsigned nchunks = PERS ? (unsigned)((a.p.n + FAST_CHUNK - 1) / FAST_CHUNK) : 0u;
     // the row index is re-derived where it is needed (entry and exit) instead of living in two registers across the step loop
-    auto row = [&]() { return (int64_t)xcd_swizzle(blockIdx.x, gridDim.x) * WG + threadIdx.x; };
-    unsigned steps = 0, attempts = 0, paused = 0;  // per lane and launch: 32 bits are plenty
-    if (row() < a.p.n) {
-        int64_t i = row();
-        const DParticles& P = a.p;
-        const DPOut& O = a.po;
-        const pk_exec_params& prm = a.prm;
-        constexpr bool pf = PFM == 1;
-        FCtx c;
-        c.state = prm.reset_state ? PK_EVALUATE : P.state[i];  // kernel.py:188
-        if (c.state == PK_EVALUATE) {
-            unsigned it = prm.reset_state ? 0u : (unsigned)P.iter[i];
-            fctx_init(c, PK_EVALUATE, P.ei[i * P.ngrids + a.fast.grid], fast_cell_regs(LP), fast_block_regs(LP, pf));  // only the velocity grid's `ei` is touched
-            double pt = P.t[i];
-            double pz = ldp(P.z, i, pf), py = ldp(P.y, i, pf), px = ldp(P.x, i, pf);
-            double pdz = ldp(P.dz, i, pf), pdy = ldp(P.dy, i, pf), pdx = ldp(P.dx, i, pf);
-            double pdt = P.dt[i];
-            const double endtime = prm.endtime;
-            while (c.state == PK_EVALUATE) {  // :190 (no kernel of these programs sets Repeat)
-                uint32_t fl = ft.fl;  // (FastTabs::fl: the step loop's yes / no questions as scalar bit tests, not as saved lane masks)
-                asm volatile("" : "+s"(fl));
-                const bool fwd = (fl & FA_FWD) != 0;                   // sign = 1 if dt0 > 0 else -1 (kernel.py:186)
-                const double tte = fwd ? endtime - pt : -(endtime - pt);  // sign * (endtime - t), the sign of a zero included
-                if (!(tte >= 0)) break;  // :193-197
-                if ((fl & FA_MAXIT) && it >= (unsigned)prm.max_iters) break;  // pk_execute_rerun: stop where the reference raised
-                double dtc;
-                if (fwd) dtc = fmax(fmin(pdt, tte), 0.0);  // :200-203
-                else dtc = fmin(fmax(pdt, -tte), 0.0);
-                if (fl & FA_WIN) {  // field-slab streaming (some field streams through a ring of levels): step only inside the resident time window (advect_kernel)
-                    const double t1 = pt + dtc;
-                    const double lo = fmin(pt, t1), hi = fmax(pt, t1);
-                    if (lo < a.win_lo || hi > a.win_hi) { paused = 1; break; }
-                }
-                it++;
-                pdt = dtc;
-                attempts++;
-#ifdef PK_USER_KERNELS
-                // a list with user kernels: [kernels before the advection kernel ..., AdvectionRK4(_3D), kernels after it ...]
-                int adv = 0;
-                for (; adv < prm.nk && !is_rk4_id(prm.kernels[adv]); adv++) {
-                    attempts++;
-                    side_kernel_fast<FT, pf, D3>(a, ft, c, prm.kernels[adv], adv, row(), it, pt, pz, py, px, pdz, pdy, pdx, pdt);
-                }
-#else
-                constexpr int adv = 0;
-#endif
-                // AdvectionRK4(_3D), _advection.py:42-75: (u1 + 2*u2 + 2*u3 + u4) summed left to right
-                double su = 0.0, sv = 0.0, sw = 0.0, lu = 0.0, lv = 0.0, lw = 0.0;
-                // The level-pair kernels evaluate stage 1 OUTSIDE the loop: it samples the particle's own position, so the stage-position
-                // arithmetic, its select and three loop-carried 64-bit copies leave every evaluation (measured: 5.96 -> 5.74 ms on the headline
-                // run, profiles/c2_eval_trim_ab.txt; the other instantiations keep one copy of the evaluation).
-                constexpr bool peel = LP != FAST_LP_OFF;
-                if constexpr (peel) {
-                    double u, v, w;
-                    eval_uvw_fast<FT, pf, D3, LP>(a, ft, c, pt, pz, py, px, pf, u, v, w, it, adv * 1000, 1);
-                    su = lu = u; sv = lv = v; sw = lw = w;
-                }
-#pragma unroll 1
-                for (int stage = peel ? 1 : 0; stage < 4; stage++) {
-                    double st = pt, sz = pz, sy = py, sx = px;
-                    if (stage > 0) {
-                        const double cdt = stage == 3 ? 1.0 : 0.5;  // u*1.0 == u and 1.0*dt == dt exactly
-                        sx = px + lu * cdt * pdt;
-                        sy = py + lv * cdt * pdt;
-                        if (D3) sz = pz + lw * cdt * pdt;
-                        st = pt + cdt * pdt;
-                    }
-                    double u, v, w;
-                    // stages 2 / 3 share t, stage 4 and stage 1 of the next step too: the odd evaluations keep their corner block, the even
-                    // ones test it (pk_fast_agrid.h: FCtx::bei)
-                    eval_uvw_fast<FT, pf, D3, LP>(a, ft, c, st, sz, sy, sx, pf && stage == 0, u, v, w, it, adv * 1000 + stage, (stage & 1) ? 2 : 1);
-                    if (stage == 0) { su = u; sv = v; sw = w; }
-                    else if (stage == 3) { su = su + u; sv = sv + v; sw = sw + w; }
-                    else { su = su + 2 * u; sv = sv + 2 * v; sw = sw + 2 * w; }
-                    lu = u; lv = v; lw = w;
-                }
-                constexpr double sixth = 1.0 / 6.0;  // RN(1/6): su / 6.0 exactly (div_by_recip), or within an ulp (PK_FAST_LEAN: one multiplication)
-                pdx = pstore(pf, pdx + (PK_FAST_LEAN ? su * sixth : div_by_recip(su, 6.0, sixth)) * pdt);
-                pdy = pstore(pf, pdy + (PK_FAST_LEAN ? sv * sixth : div_by_recip(sv, 6.0, sixth)) * pdt);
-                if (D3) pdz = pstore(pf, pdz + (PK_FAST_LEAN ? sw * sixth : div_by_recip(sw, 6.0, sixth)) * pdt);
-                for (int k = adv + 1; k < prm.nk; k++) {  // the sampling-free recovery kernels that may follow (Delete*)
-                    const int kid = prm.kernels[k];
-                    attempts++;
-#ifdef PK_USER_KERNELS
-                    if (kid >= PK_KERNEL_USER0) {
-                        side_kernel_fast<FT, pf, D3>(a, ft, c, kid, k, row(), it, pt, pz, py, px, pdz, pdy, pdx, pdt);
-                        continue;
-                    }
-#endif
-                    if (kid == PK_KERNEL_DELETE_ON_ERROR) {
-                        if (c.state >= PK_ERROR) c.state = PK_DELETE;
-                    } else if (c.state == PK_ERROROUTOFBOUNDS || c.state == PK_ERRORTHROUGHSURFACE) {
-                        c.state = PK_DELETE;  // PK_KERNEL_DELETE_OUT_OF_BOUNDS
-                    }
-                }
-                if (c.state == PK_EVALUATE || c.state == PK_SUCCESS) {  // :219-222 -> _position_update :108-120
-                    if (tte > 0 && pt + pdt == pt) {  // dt == 0 before endtime: see advect_kernel
-                        c.state = PK_ERROR;
-                        break;
-                    }
-                    px = padd(pf, px, pdx);
-                    py = padd(pf, py, pdy);
-                    // (the level-pair kernel with the cell record searches depth only when told that z moved: a dz brought into the launch)
-                    if constexpr (fast_cell_regs(LP)) {
-                        if (__builtin_expect(!(pdz == 0), 0)) fctx_depth_moved(c, fast_block_regs(LP, pf));
-                    }
-                    pz = padd(pf, pz, pdz);
-                    pt += pdt;
-                    pdx = pdy = pdz = 0.0;
-                    steps++;
-                }
-                pdt = prm.dt0;                                                        // :225-226 (not RK45 mode)
-                if (c.state == PK_EVALUATE && pt == endtime) c.state = PK_ENDOFLOOP;  // :229-230
-            }
-            i = row();
-            asm volatile("" : "+v"(i));  // keep it re-derived: not hoisted above the loop
-            O.t[i] = pt;
-            stp(O.z, i, pz, pf);
-            stp(O.y, i, py, pf);
-            stp(O.x, i, px, pf);
-            stp(O.dz, i, pdz, pf);
-            stp(O.dy, i, pdy, pf);
-            stp(O.dx, i, pdx, pf);
-            O.dt[i] = pdt;
-            if (P.next_dt && O.next_dt != P.next_dt) O.next_dt[i] = P.next_dt[i];
-            O.state[i] = c.state;
-            for (int g = 0; g < P.ngrids; g++) O.ei[i * P.ngrids + g] = g == a.fast.grid ? c.ei : P.ei[i * P.ngrids + g];
-            O.iter[i] = (int32_t)it;
-            note_error_iteration(a, c.state, it);
+    auto row = [&]() {
+        if constexpr (PERS) {
+            unsigned tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));  // opaque: nothing derived from the lane number is hoisted out of the chunk loop and kept across the step loop
+            return (int64_t)chunk * FAST_CHUNK + (tid & 63u);
+        } else return (int64_t)xcd_swizzle(blockIdx.x, gridDim.x) * WG + threadIdx.x;
+    };
+    // The launch counters.  The persistent launch keeps a wavefront's sums in scalar registers and adds them once, when the wavefront leaves, not
+    // once per chunk: 3e5 atomics of one launch on the one line of `steps` and `attempts` are served one after the other, chip-wide, and were
+    // the floor under a launch of few steps (profiles/c2_persistent_waves_ab.txt).
+    [[maybe_unused]] unsigned long long all_steps = 0ull, all_attempts = 0ull, all_paused = 0ull;
+    do {
+        if constexpr (PERS) {
+            if (!fast_claim(a.counters, nchunks, tried, chunk)) break;
         }
-    }
-    const unsigned long long wsteps = wave_sum((unsigned long long)steps), wattempts = wave_sum((unsigned long long)attempts),
-                             wpaused = wave_sum((unsigned long long)paused);
-    if ((threadIdx.x & 63) == 0) {
-        if (wsteps) atomicAdd(&a.counters->steps, wsteps);
-        if (wattempts) atomicAdd(&a.counters->attempts, wattempts);
-        if (wpaused) atomicAdd(&a.counters->paused, wpaused);
+        unsigned steps = 0, attempts = 0, paused = 0;  // per lane and launch: 32 bits are plenty
+        if (row() < a.p.n) {
+            int64_t i = row();
+            const DParticles& P = a.p;
+            const DPOut& O = a.po;
+            const pk_exec_params& prm = a.prm;
+            constexpr bool pf = PFM == 1;
+            FCtx c;
+            c.state = prm.reset_state ? PK_EVALUATE : P.state[i];  // kernel.py:188
+            if (c.state == PK_EVALUATE) {
+                unsigned it = prm.reset_state ? 0u : (unsigned)P.iter[i];
+                fctx_init(c, PK_EVALUATE, P.ei[i * P.ngrids + a.fast.grid], fast_cell_regs(LP), fast_block_regs(LP, pf));  // only the velocity grid's `ei` is touched
+                double pt = P.t[i];
+                double pz = ldp(P.z, i, pf), py = ldp(P.y, i, pf), px = ldp(P.x, i, pf);
+                double pdz = ldp(P.dz, i, pf), pdy = ldp(P.dy, i, pf), pdx = ldp(P.dx, i, pf);
+                double pdt = P.dt[i];
+                const double endtime = prm.endtime;
+                while (c.state == PK_EVALUATE) {  // :190 (no kernel of these programs sets Repeat)
+                    uint32_t fl = ft.fl;  // (FastTabs::fl: the step loop's yes / no questions as scalar bit tests, not as saved lane masks)
+                    asm volatile("" : "+s"(fl));
+                    const bool fwd = (fl & FA_FWD) != 0;                   // sign = 1 if dt0 > 0 else -1 (kernel.py:186)
+                    const double tte = fwd ? endtime - pt : -(endtime - pt);  // sign * (endtime - t), the sign of a zero included
+                    if (!(tte >= 0)) break;  // :193-197
+                    if ((fl & FA_MAXIT) && it >= (unsigned)prm.max_iters) break;  // pk_execute_rerun: stop where the reference raised
+                    double dtc;
+                    if (fwd) dtc = fmax(fmin(pdt, tte), 0.0);  // :200-203
+                    else dtc = fmin(fmax(pdt, -tte), 0.0);
+                    if (fl & FA_WIN) {  // field-slab streaming (some field streams through a ring of levels): step only inside the resident time window (advect_kernel)
+                        const double t1 = pt + dtc;
+                        const double lo = fmin(pt, t1), hi = fmax(pt, t1);
+                        if (lo < a.win_lo || hi > a.win_hi) { paused = 1; break; }
+                    }
+                    it++;
+                    pdt = dtc;
+                    attempts++;
+#ifdef PK_USER_KERNELS
+                    // a list with user kernels: [kernels before the advection kernel ..., AdvectionRK4(_3D), kernels after it ...]
+                    int adv = 0;
+                    for (; adv < prm.nk && !is_rk4_id(prm.kernels[adv]); adv++) {
+                        attempts++;
+                        side_kernel_fast<FT, pf, D3>(a, ft, c, prm.kernels[adv], adv, row(), it, pt, pz, py, px, pdz, pdy, pdx, pdt);
+                    }
+#else
+                    constexpr int adv = 0;
+#endif
+                    // AdvectionRK4(_3D), _advection.py:42-75: (u1 + 2*u2 + 2*u3 + u4) summed left to right
+                    double su = 0.0, sv = 0.0, sw = 0.0, lu = 0.0, lv = 0.0, lw = 0.0;
+                    // The level-pair kernels evaluate stage 1 OUTSIDE the loop: it samples the particle's own position, so the stage-position
+                    // arithmetic, its select and three loop-carried 64-bit copies leave every evaluation (measured: 5.96 -> 5.74 ms on the headline
+                    // run, profiles/c2_eval_trim_ab.txt; the other instantiations keep one copy of the evaluation).
+                    constexpr bool peel = LP != FAST_LP_OFF;
+                    if constexpr (peel) {
+                        double u, v, w;
+                        eval_uvw_fast<FT, pf, D3, LP>(a, ft, c, pt, pz, py, px, pf, u, v, w, it, adv * 1000, 1);
+                        su = lu = u; sv = lv = v; sw = lw = w;
+                    }
+#pragma unroll 1
+                    for (int stage = peel ? 1 : 0; stage < 4; stage++) {
+                        double st = pt, sz = pz, sy = py, sx = px;
+                        if (stage > 0) {
+                            const double cdt = stage == 3 ? 1.0 : 0.5;  // u*1.0 == u and 1.0*dt == dt exactly
+                            sx = px + lu * cdt * pdt;
+                            sy = py + lv * cdt * pdt;
+                            if (D3) sz = pz + lw * cdt * pdt;
+                            st = pt + cdt * pdt;
+                        }
+                        double u, v, w;
+                        // stages 2 / 3 share t, stage 4 and stage 1 of the next step too: the odd evaluations keep their corner block, the even
+                        // ones test it (pk_fast_agrid.h: FCtx::bei)
+                        eval_uvw_fast<FT, pf, D3, LP>(a, ft, c, st, sz, sy, sx, pf && stage == 0, u, v, w, it, adv * 1000 + stage, (stage & 1) ? 2 : 1);
+                        if (stage == 0) { su = u; sv = v; sw = w; }
+                        else if (stage == 3) { su = su + u; sv = sv + v; sw = sw + w; }
+                        else { su = su + 2 * u; sv = sv + 2 * v; sw = sw + 2 * w; }
+                        lu = u; lv = v; lw = w;
+                    }
+                    constexpr double sixth = 1.0 / 6.0;  // RN(1/6): su / 6.0 exactly (div_by_recip), or within an ulp (PK_FAST_LEAN: one multiplication)
+                    pdx = pstore(pf, pdx + (PK_FAST_LEAN ? su * sixth : div_by_recip(su, 6.0, sixth)) * pdt);
+                    pdy = pstore(pf, pdy + (PK_FAST_LEAN ? sv * sixth : div_by_recip(sv, 6.0, sixth)) * pdt);
+                    if (D3) pdz = pstore(pf, pdz + (PK_FAST_LEAN ? sw * sixth : div_by_recip(sw, 6.0, sixth)) * pdt);
+                    for (int k = adv + 1; k < prm.nk; k++) {  // the sampling-free recovery kernels that may follow (Delete*)
+                        const int kid = prm.kernels[k];
+                        attempts++;
+#ifdef PK_USER_KERNELS
+                        if (kid >= PK_KERNEL_USER0) {
+                            side_kernel_fast<FT, pf, D3>(a, ft, c, kid, k, row(), it, pt, pz, py, px, pdz, pdy, pdx, pdt);
+                            continue;
+                        }
+#endif
+                        if (kid == PK_KERNEL_DELETE_ON_ERROR) {
+                            if (c.state >= PK_ERROR) c.state = PK_DELETE;
+                        } else if (c.state == PK_ERROROUTOFBOUNDS || c.state == PK_ERRORTHROUGHSURFACE) {
+                            c.state = PK_DELETE;  // PK_KERNEL_DELETE_OUT_OF_BOUNDS
+                        }
+                    }
+                    if (c.state == PK_EVALUATE || c.state == PK_SUCCESS) {  // :219-222 -> _position_update :108-120
+                        if (tte > 0 && pt + pdt == pt) {  // dt == 0 before endtime: see advect_kernel
+                            c.state = PK_ERROR;
+                            break;
+                        }
+                        px = padd(pf, px, pdx);
+                        py = padd(pf, py, pdy);
+                        // (the level-pair kernel with the cell record searches depth only when told that z moved: a dz brought into the launch)
+                        if constexpr (fast_cell_regs(LP)) {
+                            if (__builtin_expect(!(pdz == 0), 0)) fctx_depth_moved(c, fast_block_regs(LP, pf));
+                        }
+                        pz = padd(pf, pz, pdz);
+                        pt += pdt;
+                        pdx = pdy = pdz = 0.0;
+                        steps++;
+                    }
+                    pdt = prm.dt0;                                                        // :225-226 (not RK45 mode)
+                    if (c.state == PK_EVALUATE && pt == endtime) c.state = PK_ENDOFLOOP;  // :229-230
+                }
+                i = row();
+                asm volatile("" : "+v"(i));  // keep it re-derived: not hoisted above the loop
+                O.t[i] = pt;
+                stp(O.z, i, pz, pf);
+                stp(O.y, i, py, pf);
+                stp(O.x, i, px, pf);
+                stp(O.dz, i, pdz, pf);
+                stp(O.dy, i, pdy, pf);
+                stp(O.dx, i, pdx, pf);
+                O.dt[i] = pdt;
+                if (P.next_dt && O.next_dt != P.next_dt) O.next_dt[i] = P.next_dt[i];
+                O.state[i] = c.state;
+                for (int g = 0; g < P.ngrids; g++) O.ei[i * P.ngrids + g] = g == a.fast.grid ? c.ei : P.ei[i * P.ngrids + g];
+                O.iter[i] = (int32_t)it;
+                note_error_iteration(a, c.state, it);
+            }
+        }
+        unsigned long long wsteps = wave_sum((unsigned long long)steps), wattempts = wave_sum((unsigned long long)attempts),
+                           wpaused = wave_sum((unsigned long long)paused);
+        if constexpr (PERS) {
+            all_steps += uniform_u64(wsteps);
+            all_attempts += uniform_u64(wattempts);
+            all_paused += uniform_u64(wpaused);
+            continue;
+        }
+        if ((threadIdx.x & 63) == 0) {
+            if (wsteps) atomicAdd(&a.counters->steps, wsteps);
+            if (wattempts) atomicAdd(&a.counters->attempts, wattempts);
+            if (wpaused) atomicAdd(&a.counters->paused, wpaused);
+        }
+    } while (PERS);
+    if constexpr (PERS) {
+        if ((threadIdx.x & 63) == 0) {
+            if (all_steps) atomicAdd(&a.counters->steps, all_steps);
+            if (all_attempts) atomicAdd(&a.counters->attempts, all_attempts);
+            if (all_paused) atomicAdd(&a.counters->paused, all_paused);
+        }
     }
 }
 
@@ -1387,7 +1464,9 @@ template <int PROG>
 void launch_fast(int field_f32, int particles_f32, const KArgs& a, dim3 grid, size_t lds_bytes, hipStream_t stream);
 // AdvectionRK4 in the level-pair modes (lp: FAST_LP_REGS / FAST_LP_CACHE; a translation unit of its own): the grid is derived from the
 // mode's workgroup size, and the cache's workgroups may ask for more dynamic LDS than the 64 KB a kernel gets without saying so
-hipError_t launch_fast_lp(int lp, int field_f32, int particles_f32, const KArgs& a, size_t lds_bytes, hipStream_t stream);
+// compute_units, grid_cap: the persistent launch of the cache mode (fast_persistent) starts min(ceil(n / 512), compute_units x workgroups resident per CU)
+// workgroups, at most grid_cap of them when grid_cap > 0 (pk_set_option "fast_grid")
+hipError_t launch_fast_lp(int lp, int field_f32, int particles_f32, const KArgs& a, size_t lds_bytes, int compute_units, int grid_cap, hipStream_t stream);
 
 #define PK_LAUNCH_FAST_CASE(FT, PF) \
     hipLaunchKernelGGL((advect_fast_kernel<FT, PF, KIDV == PK_KERNEL_ADVECTION_RK4_3D>), grid, dim3(256), lds_bytes, stream, a)
@@ -1410,7 +1489,19 @@ hipError_t launch_fast_lp(int lp, int field_f32, int particles_f32, const KArgs&
             const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
             if (e != hipSuccess) return e;                                                                                          \
         }                                                                                                                           \
-        hipLaunchKernelGGL(kern, dim3((unsigned)((a.p.n + WG - 1) / WG)), dim3(WG), lds_bytes, stream, a);                          \
+        unsigned nwg = (unsigned)((a.p.n + WG - 1) / WG);                                                                           \
+        if (fast_persistent(LP)) { /* what is resident at once, at the real dynamic LDS size (asked once per size) */               \
+            static thread_local size_t q_lds = ~(size_t)0;                                                                          \
+            static thread_local int q_nb = 0;                                                                                       \
+            if (q_lds != lds_bytes) {                                                                                               \
+                const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&q_nb, kern, WG, lds_bytes);                      \
+                if (e != hipSuccess) return e;                                                                                      \
+                q_lds = lds_bytes;                                                                                                  \
+            }                                                                                                                       \
+            nwg = std::min(nwg, (unsigned)std::max(compute_units, 1) * (unsigned)std::max(q_nb, 1));                                \
+            if (grid_cap > 0) nwg = std::min(nwg, (unsigned)grid_cap);                                                              \
+        }                                                                                                                           \
+        hipLaunchKernelGGL(kern, dim3(nwg), dim3(WG), lds_bytes, stream, a);                                                        \
     } while (0)
 #define PK_LAUNCH_FAST_LP_KEYS(LP)                                                                                 \
     if (field_f32) {                                                                                               \

@@ -5,9 +5,10 @@
 #define PK_MIN_WAVES 4
 #endif
 #include "pk_kernels.h"
+#include <algorithm>
 namespace pk {
 static_assert(PK_FAST_LEAN != 0, "the level-pair modes belong to the lean build");
-hipError_t launch_fast_lp(int lp, int field_f32, int particles_f32, const KArgs& a, size_t lds_bytes, hipStream_t stream) {
+hipError_t launch_fast_lp(int lp, int field_f32, int particles_f32, const KArgs& a, size_t lds_bytes, int compute_units, int grid_cap, hipStream_t stream) {
     if (lp == FAST_LP_CACHE) {
         PK_LAUNCH_FAST_LP_KEYS(FAST_LP_CACHE)
     } else {
