@@ -469,12 +469,21 @@ int32_t pk_execute_twe_report(pk_ctx* ctx, int64_t* found, int32_t cap, int32_t*
  * * 2 + float32 particles; it must refuse (abort) what it was not built for.  flags: PK_USER_RIDE = the module carries the dedicated kernel
  * pk_generic_variant named, PK_USER_SAMPLES_* and sample_fids as above.  NULL unregisters.  A list with a user id and no launcher fails.
  * On a context with a UxGrid the variant is (key PK_USER_KEY_UX, lds 0), apart from every structured key (0 .. 11): the module carries the
- * step loop of csrc/pk_ux.h and is registered with PK_USER_UX in flags; a launch refuses a module of the other kind. */
+ * step loop of csrc/pk_ux.h and is registered with PK_USER_UX in flags; a launch refuses a module of the other kind.
+ * A list that runs the CROCO sigma loop (csrc/pk_sigma.h) -- it holds a CROCO kernel id, or its user kernels call convert_z_to_sigma_croco, which
+ * the caller announces with PK_USER_SIGMA in sample_flags -- has the variant key PK_USER_KEY_SIGMA + (float32 fields ? 4 : 0) + (curvilinear
+ * main grid ? 2 : 0) + interp_uv (0 XLinear_Velocity / 1 CGrid_Velocity): 16 .. 23, apart from the structured keys and PK_USER_KEY_UX, and lds =
+ * the dynamic LDS bytes of the launch (16 per sigma level; both the int32 and the uint64 argument of the launcher carry them).  The module
+ * instantiates advect_sigma_kernel and is registered with PK_USER_SIGMA in flags.  A launch refuses a structured or UxGrid module on a list with
+ * a CROCO kernel and a sigma module on a UxGrid or on a context without CROCO parameters (pk_set_croco); on a context that has them a sigma
+ * module runs any structured list in the sigma loop (program 7), which is how a list without a CROCO id gets its conversions served. */
 #define PK_USER_RIDE 1
 #define PK_USER_SAMPLES_UV 2
 #define PK_USER_SAMPLES_UVW 4
 #define PK_USER_UX 8
 #define PK_USER_KEY_UX 12
+#define PK_USER_SIGMA 16
+#define PK_USER_KEY_SIGMA 16
 int32_t pk_generic_variant(pk_ctx* ctx, const pk_exec_params* prm, int32_t sample_flags, int32_t nsample, const int32_t* sample_fids, int32_t* key,
                            int32_t* lds, int32_t* typed, int32_t* fast);
 int32_t pk_set_user_program(pk_ctx* ctx, void* launcher, int32_t flags, int32_t nsample, const int32_t* sample_fids);

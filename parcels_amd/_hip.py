@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get("PARCELS_HIP_LIB", os.path.join(_HERE, "libparcels_hip
 PK_ABI_VERSION = 9
 # pk_set_user_program flags / the variant key of a UxGrid user module (include/parcels_hip.h)
 PK_USER_RIDE, PK_USER_SAMPLES_UV, PK_USER_SAMPLES_UVW, PK_USER_UX, PK_USER_KEY_UX = 1, 2, 4, 8, 12
+# ... and of a module that carries the CROCO sigma loop: keys PK_USER_KEY_SIGMA + (float32 fields ? 4 : 0) + (curvilinear ? 2 : 0) + interp_uv
+PK_USER_SIGMA, PK_USER_KEY_SIGMA = 16, 16
 PK_F32, PK_F64 = 0, 1
 PK_MAX_GRIDS, PK_MAX_FIELDS, PK_MAX_KERNELS, PK_NUM_STATE_CODES = 4, 64, 8, 80
 PK_MAX_EXTRA = 8
@@ -23,6 +25,7 @@ PK_MAX_TWE = 1024
 PK_KERNEL_SAMPLE_FIELD = 10
 PK_KERNEL_ADVECTION_RK2_3D_CROCO = 11
 PK_KERNEL_SAMPLE_SIGMA_CROCO = 12
+PK_KERNEL_USER0 = 40  # the first id of a run-time compiled user kernel (parcels_amd/jit.py)
 PK_EVAL_MASKED = 0x10000  # pk_eval: or'ed into out_state where the value was zeroed for an out-of-bounds index
 PK_COMM_ID_BYTES = 128
 PK_OP_MIN, PK_OP_MAX, PK_OP_SUM = 0, 1, 2

@@ -1930,8 +1930,15 @@ static int32_t interp_key(const pk_ctx* ctx, const pk_exec_params* prm, const KA
     return (ctx->fields[prm->fU].d.dtype == PK_F32 ? 6 : 0) + (ctx->grids[a.main_grid].d.kind == 1 ? 3 : 0) + std::min<int>(prm->interp_uv, 2);
 }
 
+// The variant of the CROCO sigma loop (pk_sigma.h) a launch runs: what launch_sigma dispatches on, behind PK_USER_KEY_SIGMA
+static int32_t sigma_key(const pk_ctx* ctx, const pk_exec_params* prm, const KArgs& a) {
+    return PK_USER_KEY_SIGMA + (ctx->fields[prm->fU].d.dtype == PK_F32 ? 4 : 0) + (ctx->grids[a.main_grid].d.kind == 1 ? 2 : 0) + (prm->interp_uv ? 1 : 0);
+}
+
 // The launch arguments of `prm` apart from the descriptor tables (upload_descriptors): main field and grid, resident time window, LDS layout.
-static int32_t launch_args(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, size_t& lds_bytes, int& use_lds) {
+// planning: the arguments are wanted to name the program variant only (pk_generic_variant, asked before the first window of a streamed
+// fieldset is committed): a ring without a resident level is no error then.
+static int32_t launch_args(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, size_t& lds_bytes, int& use_lds, bool planning = false) {
     memset(&a, 0, sizeof(a));
     a.p = ctx->dev;
     a.prm = *prm;
@@ -1956,6 +1963,7 @@ static int32_t launch_args(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, siz
         int lo = 1 << 30, hi = -1, cnt = 0;
         for (int lv : f.slot_level)
             if (lv >= 0) { lo = std::min(lo, lv); hi = std::max(hi, lv); cnt++; }
+        if (cnt == 0 && planning) continue;
         if (cnt == 0) return ctx->fail("no time level of a streamed field is resident (pk_field_upload_level)");
         if (hi - lo + 1 != cnt) return ctx->fail("resident time levels are not contiguous (pk_field_evict_outside)");
         // nothing earlier / later exists at the ends of the axis: let the kernels raise code 70 there
@@ -2414,7 +2422,7 @@ static bool fill_fast_scalars(pk_ctx* ctx, const pk_exec_params* prm, FastA& F, 
 // registered; pk_generic_variant plans for the module about to be built, which has to serve every launch of its list.
 struct UserShape {
     bool present;          // the list holds user kernels (only such a list may ride in a dedicated kernel)
-    int32_t flags;         // PK_USER_RIDE | PK_USER_SAMPLES_*
+    int32_t flags;         // PK_USER_RIDE | PK_USER_SAMPLES_* | PK_USER_UX | PK_USER_SIGMA
     int nsample;           // scalar fields the user kernels sample: fids[0 .. nsample)
     const int32_t* fids;
     bool assume_guessed;   // plan as if the first search were guessed (the module is also launched after the unguessed first launch)
@@ -2435,6 +2443,8 @@ static int32_t plan_launch(pk_ctx* ctx, const pk_exec_params* prm, const UserSha
     p = LaunchPlan{PROG_GENERIC, DEDICATED_NONE, false, lds_bytes, FAST_LP_OFF};
     if (ctx_has_ugrid(ctx)) {  // a fieldset on a UxGrid: the unstructured program (pk_ux.h) and nothing else
         if (ctx->grids[a.main_grid].d.kind != PK_UX_KIND) return ctx->fail("a launch on a context with a UxGrid needs its velocity on the UxGrid");
+        if (us.present && (us.flags & PK_USER_SIGMA))
+            return ctx->fail("the registered user program was built for the CROCO sigma loop: a launch on a UxGrid needs the UxGrid variant (PK_USER_UX)");
         if (us.present && !(us.flags & PK_USER_UX))
             return ctx->fail("the registered user program was built for a structured grid: a launch on a UxGrid needs the UxGrid variant (PK_USER_UX)");
         if (prm->rk45_mode) return ctx->fail("AdvectionRK45 is not implemented on a UxGrid");
@@ -2451,9 +2461,14 @@ static int32_t plan_launch(pk_ctx* ctx, const pk_exec_params* prm, const UserSha
     if (us.present && (us.flags & PK_USER_UX)) return ctx->fail("the registered user program was built for a UxGrid: it cannot run a launch on a structured grid");
     bool croco = false;
     for (int k = 0; k < prm->nk; k++) croco = croco || prm->kernels[k] == PK_KERNEL_ADVECTION_RK2_3D_CROCO || prm->kernels[k] == PK_KERNEL_SAMPLE_SIGMA_CROCO;
-    if (croco) {  // a list with a CROCO kernel: the sigma-grid program (pk_sigma.h), whatever built-in kernels stand beside it
+    // a user module that carries the sigma loop (its kernels may call convert_z_to_sigma_croco) makes its list one, CROCO id or not
+    const bool sigma_module = us.present && (us.flags & PK_USER_SIGMA);
+    if (sigma_module && !croco && !ctx->has_sigma)
+        return ctx->fail("the registered user program was built for the CROCO sigma loop: it runs a list on a context with CROCO parameters only (pk_set_croco)");
+    if (croco || sigma_module) {  // the sigma-grid program (pk_sigma.h), whatever built-in kernels stand beside the CROCO kernels
         if (!ctx->has_sigma) return ctx->fail("a CROCO kernel needs the CROCO parameters of the context (pk_set_croco)");
-        if (us.present) return ctx->fail("user kernels are not compiled next to a CROCO kernel (they run in the host loop)");
+        if (us.present && !sigma_module)
+            return ctx->fail("the registered user program was built for the kernel-list interpreter: a list with a CROCO kernel needs the sigma variant (PK_USER_SIGMA)");
         if (ctx_is_typed(ctx)) return ctx->fail("the CROCO kernels need float64 coordinate arrays");
         if (prm->interp_uv != 0 && prm->interp_uv != 1) return ctx->fail("the CROCO program interpolates the velocity with XLinear_Velocity or CGrid_Velocity");
         p.prog = PROG_SIGMA;
@@ -2679,6 +2694,7 @@ int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
             case DEDICATED_NONE:
                 if (p.prog == PROG_UX && has_user) ctx->user_launch(&a, DEDICATED_NONE, PK_USER_KEY_UX, 0, 0, (void*)ctx->compute);
                 else if (p.prog == PROG_UX) launch_ux(pf32, a, n, ctx->compute);
+                else if (p.prog == PROG_SIGMA && has_user) ctx->user_launch(&a, DEDICATED_NONE, sigma_key(ctx, prm, a), (int32_t)p.lds, (uint64_t)p.lds, (void*)ctx->compute);
                 else if (p.prog == PROG_SIGMA) launch_sigma(field_f32, curv, prm->interp_uv, a, n, p.lds, ctx->compute);
                 else if (has_user) ctx->user_launch(&a, DEDICATED_NONE, interp_key(ctx, prm, a), use_lds, (uint64_t)p.lds, (void*)ctx->compute);
                 else launch_general(p.prog, field_f32, curv, prm, use_lds, a, grid, p.lds, ctx->compute);
@@ -2808,16 +2824,20 @@ int32_t pk_generic_variant(pk_ctx* ctx, const pk_exec_params* prm, int32_t sampl
     KArgs a;
     size_t lds_bytes = 0;
     int use_lds = 0;
-    int32_t rc = launch_args(ctx, prm, a, lds_bytes, use_lds);
+    int32_t rc = launch_args(ctx, prm, a, lds_bytes, use_lds, true);
     if (rc) return rc;
     // the module serves every launch of the list: it is asked about as a list with user kernels that may ride
     const bool ux = ctx->grids[a.main_grid].d.kind == PK_UX_KIND;  // (the module about to be built is the one this context needs)
-    const UserShape us{true, (ux ? PK_USER_UX : PK_USER_RIDE) | (sample_flags & (PK_USER_SAMPLES_UV | PK_USER_SAMPLES_UVW)), nsample, sample_fids, true, true};
+    // ... a list with a CROCO kernel, or user kernels that convert depths to sigma levels (sample_flags announces them: PK_USER_SIGMA), needs the sigma loop
+    bool sigma = (sample_flags & PK_USER_SIGMA) != 0;
+    for (int k = 0; k < prm->nk; k++) sigma = sigma || prm->kernels[k] == PK_KERNEL_ADVECTION_RK2_3D_CROCO || prm->kernels[k] == PK_KERNEL_SAMPLE_SIGMA_CROCO;
+    sigma = sigma && !ux;
+    const UserShape us{true, (ux ? PK_USER_UX : (sigma ? PK_USER_SIGMA : PK_USER_RIDE)) | (sample_flags & (PK_USER_SAMPLES_UV | PK_USER_SAMPLES_UVW)), nsample, sample_fids, true, true};
     LaunchPlan p;
     rc = plan_launch(ctx, prm, us, a, lds_bytes, use_lds, p);
     if (rc) return rc;
-    *key = interp_key(ctx, prm, a);
-    *lds = ux ? 0 : use_lds;
+    *key = p.prog == PROG_SIGMA ? sigma_key(ctx, prm, a) : interp_key(ctx, prm, a);
+    *lds = ux ? 0 : (p.prog == PROG_SIGMA ? (int32_t)p.lds : use_lds);
     *typed = ctx_is_typed(ctx) ? 1 : 0;
     *fast = p.ride ? p.kernel : DEDICATED_NONE;
     return 0;

@@ -46,6 +46,13 @@ struct Request {
     bool f32;    // sample point (y, x) comes straight from float32 particle storage
     bool zf32;   // its z does: every sample at `particles.z` (all stages of the 2-D kernels), whatever y and x are (PCtx::zpos_f32)
     bool reuse;  // scalar sample at the point of this kernel's velocity sample: the grid position may be re-used (SearchMemo)
+#ifdef PK_USER_KERNELS
+    // a generated stage whose sample belongs to a translated convert_z_to_sigma_croco call (parcels_amd/jit.py: conversion): 1 the sample of
+    // h, 2 the one of zeta, behind which the loop turns the depth cz into the sigma level (0: a plain sample).  Served by the step loop of
+    // pk_sigma.h only, which clears conv before every stage; a module of another loop is never built from such a kernel.
+    int conv;
+    double cz;
+#endif
 };
 
 // kernel-local registers (all indices are compile-time constants -> scalar-replaced into VGPRs)

@@ -17,10 +17,14 @@ namespace pk {
 
 constexpr int PROG_SIGMA = 7;  // the program of a launch with a CROCO kernel in its list (pk_exec_stats.program)
 
-// launchers (pk_prog_sigma.hip, the only translation unit that defines PK_SIGMA_KERNELS and so the kernels below)
+// launchers (pk_prog_sigma.hip: the library's translation unit that defines PK_SIGMA_KERNELS and so the kernels below; the only other one is
+// the module parcels_amd/jit.py generates for a kernel list with user kernels on a CROCO fieldset, which instantiates advect_sigma_kernel
+// with PK_USER_KERNELS)
+#ifndef PK_USER_KERNELS
 void launch_sigma(int field_f32, int curvilinear, int interp, const KArgs& a, int64_t n, size_t lds_bytes, hipStream_t stream);
 void launch_sigma_points(const KArgs& a, int64_t m, const double* t, const double* z, const double* y, const double* x, double* out,
                          size_t lds_bytes, hipStream_t stream);
+#endif
 
 #ifdef PK_SIGMA_KERNELS
 
@@ -140,6 +144,23 @@ PK_DEV bool is_conversion_stage(int kid, int stage) {
     if (kid == PK_KERNEL_SAMPLE_SIGMA_CROCO) return stage <= 1;
     return stage == 1 || stage == 2 || stage == 7 || stage == 8;
 }
+
+// A stage of a translated user kernel whose sample is one of convert_z_to_sigma_croco's (Request::conv): the loop treats it like the
+// conversion stages of the built-in kernels -- the OutsideTimeInterval of such a sample leaves the kernel list -- and folds the two samples
+// into the sigma level, which it leaves in L.r[3], where a user stage finds the value of its latest sample.  (h and its dtype wait in
+// L.r[1] / sl.h32 as in croco_consume: a generated stage never touches L.r.)  The library's own instantiations know no such stage.
+#ifdef PK_USER_KERNELS
+PK_DEV void user_stage_begin(Request& rq) { rq.conv = 0; }
+PK_DEV bool user_conversion_stage(const Request& rq) { return rq.conv != 0; }
+PK_DEV void user_conversion_consume(const KArgs& a, const pk_tab2* tab, const Request& rq, KLocal& L, SigLocal& sl, double u, bool v32) {
+    if (rq.conv == 1) { L.r[1] = u; sl.h32 = v32; }
+    else L.r[3] = croco_sigma(tab, a.sigma, L.r[1], sl.h32, u, rq.cz);
+}
+#else
+PK_DEV void user_stage_begin(Request&) {}
+PK_DEV bool user_conversion_stage(const Request&) { return false; }
+PK_DEV void user_conversion_consume(const KArgs&, const pk_tab2*, const Request&, KLocal&, SigLocal&, double, bool) {}
+#endif
 
 // prepare() of the two CROCO kernels: true when the kernel is finished
 PK_DEV bool croco_prepare(const KArgs& a, int kid, int stage, int kslot, PCtx& c, PState& p, KLocal& L, Request& rq, SigRq& sq) {
@@ -329,6 +350,7 @@ __global__ void __launch_bounds__(256, PK_SIGMA_MIN_WAVES) advect_sigma_kernel(c
                         SigRq sq;
                         sq.detached = false;
                         attempts++;
+                        user_stage_begin(rq);
 #pragma unroll 1
                         for (int stage = 0; !(croco ? croco_prepare(a, kid, stage, k, c, p, L, rq, sq) : prepare(a, kid, stage, k, c, p, L, rq)); stage++) {
                             double u, v = 0.0, w = 0.0;
@@ -336,10 +358,12 @@ __global__ void __launch_bounds__(256, PK_SIGMA_MIN_WAVES) advect_sigma_kernel(c
                             c.zpos_f32 = rq.zf32;
                             if (rq.kind == RQ_SCALAR) u = sig_eval(a, mc, c, rq.fidx, rq.t, rq.z, rq.y, rq.x, rq.f32, croco && sq.detached, v32, &raised);
                             else eval_uvw<FT, KIND, INTERP, false>(a, mc, c, rq.kind == RQ_UVW, rq.t, rq.z, rq.y, rq.x, rq.f32, u, v, w);
-                            if (raised && !(croco && is_conversion_stage(kid, stage))) raised = false;
+                            if (raised && !(croco ? is_conversion_stage(kid, stage) : user_conversion_stage(rq))) raised = false;
                             if (raised) break;  // the exception of the reference: the state stays ErrorOutsideTimeInterval
                             if (croco) croco_consume(a, tab, kid, stage, c, p, L, sl, u, v, v32);
+                            else if (user_conversion_stage(rq)) user_conversion_consume(a, tab, rq, L, sl, u, v32);
                             else consume(kid, stage, c, L, u, v, w);
+                            user_stage_begin(rq);
                         }
                     } while (c.state == PK_REPEAT && !raised);
                 }
@@ -388,6 +412,7 @@ __global__ void __launch_bounds__(256, PK_SIGMA_MIN_WAVES) advect_sigma_kernel(c
     }
 }
 
+#ifndef PK_USER_KERNELS  // (a generated user module launches the step loop only)
 // convert_z_to_sigma_croco(fieldset, t, z, y, x, None) at explicit points (pk_sigma_croco): both inner samples detached
 __global__ void __launch_bounds__(256) sigma_points_kernel(const KArgs a, int64_t m, const double* t, const double* z, const double* y,
                                                            const double* x, double* out) {
@@ -419,6 +444,7 @@ __global__ void __launch_bounds__(256) sigma_points_kernel(const KArgs a, int64_
     const double zeta = sig_eval(a, mc, c, a.sigma.fzeta, t[i], 0.0, y[i], x[i], false, true, z32);
     out[i] = croco_sigma(tab, a.sigma, h, h32, zeta, z[i]);
 }
+#endif  // !PK_USER_KERNELS
 
 #endif  // PK_SIGMA_KERNELS
 

@@ -764,8 +764,11 @@ class DeviceEngine:
         p.nk = len(kernel_ids)
         for i, k in enumerate(kernel_ids):
             p.kernels[i] = int(k)
-        if any(int(k) in (_hip.PK_KERNEL_ADVECTION_RK2_3D_CROCO, _hip.PK_KERNEL_SAMPLE_SIGMA_CROCO) for k in kernel_ids):
-            # every launch with a CROCO kernel -- fused, or one body_only pass of the host loop -- needs the CROCO parameters on the context
+        prog = self._user_program
+        sigma_module = prog is not None and prog.flags & _hip.PK_USER_SIGMA and any(int(k) >= _hip.PK_KERNEL_USER0 for k in kernel_ids)
+        if sigma_module or any(int(k) in (_hip.PK_KERNEL_ADVECTION_RK2_3D_CROCO, _hip.PK_KERNEL_SAMPLE_SIGMA_CROCO) for k in kernel_ids):
+            # every launch with a CROCO kernel -- fused, or one body_only pass of the host loop -- needs the CROCO parameters on the context, and so
+            # does a launch whose user kernels run in the sigma loop (jit.py: they may call convert_z_to_sigma_croco)
             from .kernel import croco_parameters
 
             self.set_croco(croco_parameters(fs))

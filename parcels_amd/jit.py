@@ -29,6 +29,11 @@ write-through proxy that is read when an operation consumes it (a sample later i
 reference's loop decides for the whole SET stays out: a kernel that stores ``StatusCode.Success`` (kernel.py:190-193 keeps such
 particles running while any other particle is).  tools/survey_user_kernels.py: 66 of the 86 kernels of the reference's own tests and
 tutorials compile.
+
+On a CROCO fieldset the module carries the sigma loop (csrc/pk_sigma.h, ``_TEMPLATE_SIGMA``) instead of the structured interpreter: next to
+AdvectionRK2_3D_CROCO / SampleFieldCroco tokens, and for any kernel that calls ``convert_z_to_sigma_croco(fieldset, t, z, y, x, particles)``
+-- the call is recognised by identity and becomes two marked samples of h and zeta, behind which the loop scans the levels
+(``_Translator.conversion``); a time error in them leaves the kernel list like the reference's direct ``Field.eval`` calls do.
 """
 
 from __future__ import annotations
@@ -40,6 +45,7 @@ import inspect
 import os
 import subprocess
 import textwrap
+import types
 
 import numpy as np
 
@@ -207,6 +213,7 @@ class _Translator(ast.NodeVisitor):
         self.confined: list[_V] = []  # selections whose emptiness an `if` tested: stores and samples must stay inside them
         self.conditional = False  # some sample is taken for a sub-selection: the stage machine keeps its own counter (case_body)
         self.detached = False  # some sample is taken without the particles (state and `ei` untouched)
+        self.sigma = False  # the kernel calls convert_z_to_sigma_croco: its module carries the CROCO sigma loop (csrc/pk_sigma.h)
         self.aliases: set[str] = set()  # locals bound to a bare `particles.<var>`: a write-through view on the host, not a temporary
         self.nslot = 0
 
@@ -451,21 +458,25 @@ class _Translator(ast.NodeVisitor):
             raise NotTranslatable("sample coordinates over another selection of the particles than the one passed along")
         mask = view.mask if attached else (None if dom is None else _V(dom, "b", array=True))
         if not attached:
-            # field.py:173-176: no guess from `ei`, no state update, `ei` stays.  On a rectilinear grid the search does not depend on the
-            # guess; a curvilinear search that starts from the hash returns float32-rounded cell coordinates (index_search.py:242-295)
-            if any(type(g).__name__ == "UxGrid" for g in getattr(self.fieldset, "gridset", ())):
-                # uxgrid.py:105-135: without the particles there is no guess, the face comes from the hash and its barycentric coordinates
-                # are float32-rounded (spatialhash.py:511) -- the attached form is the one the UxGrid step loop carries
-                raise NotTranslatable("sample without particles on a UxGrid (the face search starts from the hash, not from `ei`; pass the particles: "
-                                      "fieldset.F[t, z, y, x, particles])")
-            ufld = getattr(fld, "U", None)
-            curv = getattr(getattr(ufld if ufld is not None else fld, "grid", None), "is_curvilinear", None)
-            if curv is None:
-                raise NotTranslatable("sample without particles on a field whose grid is not known here")
-            if curv:
-                raise NotTranslatable("sample without particles on a curvilinear grid (the search starts from the hash, not from `ei`)")
+            self.check_detached(fld)
         # the velocity conversion on a spherical mesh is a float32 cosine when y is a float32 array (_xinterpolators.py:183-187)
         return tuple(f"(double)({v.code})" for v in pts), ("true" if pts[2].ty == "f32" else "false"), attached, mask
+
+    def check_detached(self, fld):
+        """A sample WITHOUT the particles is translated where the search does not depend on the guess: on rectilinear grids."""
+        # field.py:173-176: no guess from `ei`, no state update, `ei` stays.  On a rectilinear grid the search does not depend on the
+        # guess; a curvilinear search that starts from the hash returns float32-rounded cell coordinates (index_search.py:242-295)
+        if any(type(g).__name__ == "UxGrid" for g in getattr(self.fieldset, "gridset", ())):
+            # uxgrid.py:105-135: without the particles there is no guess, the face comes from the hash and its barycentric coordinates
+            # are float32-rounded (spatialhash.py:511) -- the attached form is the one the UxGrid step loop carries
+            raise NotTranslatable("sample without particles on a UxGrid (the face search starts from the hash, not from `ei`; pass the particles: "
+                                  "fieldset.F[t, z, y, x, particles])")
+        ufld = getattr(fld, "U", None)
+        curv = getattr(getattr(ufld if ufld is not None else fld, "grid", None), "is_curvilinear", None)
+        if curv is None:
+            raise NotTranslatable("sample without particles on a field whose grid is not known here")
+        if curv:
+            raise NotTranslatable("sample without particles on a curvilinear grid (the search starts from the hash, not from `ei`)")
 
     def sample(self, node):
         """`fieldset.F[...]` -> a stage boundary; returns the tuple of sampled components (float64 arrays on the selection sampled)."""
@@ -512,6 +523,91 @@ class _Translator(ast.NodeVisitor):
             self.emit(f"{slot} = L.r[{3 + j}];")
             out.append(_V(slot, "f64", array=True, dom=dom, explicit=True))
         return out if vector else out[0]
+
+    def callee(self, node):
+        """The object a call's callee names through the function's globals or closure: a bare name or attributes of modules; else None."""
+        if isinstance(node, ast.Name):
+            shadowed = node.id in self.locals or node.id in self.views or node.id in self.index_locals or node.id in (self.pname, self.fname)
+            return None if shadowed else self.env.get(node.id)
+        if isinstance(node, ast.Attribute):
+            base = self.callee(node.value)
+            return getattr(base, node.attr, None) if isinstance(base, types.ModuleType) else None
+        return None
+
+    def conversion(self, node):
+        """`convert_z_to_sigma_croco(fieldset, t, z, y, x, particles)` (kernels/_sigmagrids.py:6-25) -> sigma, a float64 array over the
+        selection: the samples of h and zeta at (t, 0, y, x) are two stage boundaries, marked as a conversion (Request::conv); the step loop
+        of csrc/pk_sigma.h scans the levels behind the second one and leaves sigma where a sample's value goes.  With `None` for the
+        particles both samples are taken like any sample without the particles (rectilinear grids; state and `ei` restored)."""
+        who = "convert_z_to_sigma_croco"
+        args = list(node.args)
+        if len(node.keywords) == 1 and node.keywords[0].arg == "particle" and len(args) == 5:
+            args.append(node.keywords[0].value)
+        elif node.keywords:
+            raise NotTranslatable(f"{who} with keyword arguments other than particle=")
+        if len(args) == 5:
+            args.append(ast.Constant(None))
+        if len(args) != 6:
+            raise NotTranslatable(f"{who}(fieldset, t, z, y, x, particles) called with {len(node.args)} arguments")
+        if not (isinstance(args[0], ast.Name) and args[0].id == self.fname):
+            raise NotTranslatable(f"{who}: the first argument must be the kernel's fieldset parameter '{self.fname}'")
+        if any(type(g).__name__ == "UxGrid" for g in getattr(self.fieldset, "gridset", ())):
+            raise NotTranslatable(f"{who} on a UxGrid")
+        from .kernel import croco_parameters
+
+        try:
+            croco_parameters(self.fieldset, who=self.func.__name__)
+        except (ValueError, NotImplementedError) as e:
+            raise NotTranslatable(str(e)) from None
+        depth = len(self._kids)
+        self._kids.append([])
+        try:
+            pts = [self.expr(e) for e in args[1:5]]
+        finally:
+            del self._kids[depth:]
+        for v, what in zip(pts, "tzyx"):
+            if not v.array or v.ty in ("b", "wb"):
+                raise NotTranslatable(f"{who}: {what} is not a numeric array over the particles")
+        dom = self.common_domain(pts)
+        detached = isinstance(args[5], ast.Constant) and args[5].value is None
+        if detached:
+            for name in ("h", "zeta"):
+                self.check_detached(self.fieldset.fields[name])
+            mask = None if dom is None else _V(dom, "b", array=True)
+        else:
+            view = self.view_of(args[5]) if self.is_selection(args[5]) else None
+            if view is None:
+                raise NotTranslatable(f"{who}: the last argument must be the kernel's particles, the selection the coordinates were taken from, or None")
+            if dom != view.dom:
+                raise NotTranslatable(f"{who}: coordinates over another selection of the particles than the one passed along")
+            mask = view.mask
+            self.check_confined(mask, f"the samples of {who}")
+        self.sigma = True
+        self.sampled += [int(self.field_ids["h"]), int(self.field_ids["zeta"])]
+        saved = None
+        if detached:
+            self.detached = True
+            saved = [self.new_slot("i32", "k") for _ in range(5)]
+            self.emit(f"{saved[0]} = c.state; {saved[1]} = c.ei0; {saved[2]} = c.ei1; {saved[3]} = c.ei2; {saved[4]} = c.ei3;")
+        # (the second request, a stage later, names the same point: an expression reads particle columns and locals, which no sample changes
+        # -- `particles.state` is read into a local where an operation consumes it --, so it is written out again instead of kept in registers)
+        at = [f"(double)({v.code})" for v in pts]
+        flags = f"rq.f32 = {'true' if pts[2].ty == 'f32' else 'false'}; rq.zf32 = {'true' if pts[1].ty == 'f32' else 'false'};"
+        for conv, fld in ((1, "a.sigma.fh"), (2, "a.sigma.fzeta")):  # np.zeros_like(z): h and zeta live on the surface
+            request = (f"rq.kind = RQ_SCALAR; rq.fidx = {fld}; {flags} rq.t = {at[0]}; rq.z = 0.0; rq.y = {at[2]}; rq.x = {at[3]}; "
+                       f"rq.conv = {conv}; rq.cz = {at[1]}; return false;")
+            if mask is not None:
+                self.conditional = True
+                request = f"if ({mask.code}) {{ {request} }}"
+            self.emit(_NEXT_STAGE + request)
+            self.stages.append([])
+        self._stmt_masks = {}
+        if saved:
+            self.emit(f"c.state = c.state == {int(StatusCode.ErrorOutsideTimeInterval)} ? c.state : {saved[0]}; c.ei0 = {saved[1]}; c.ei1 = {saved[2]}; "
+                      f"c.ei2 = {saved[3]}; c.ei3 = {saved[4]};")
+        slot = self.new_slot("f64", "s")
+        self.emit(f"{slot} = L.r[3];")
+        return _V(slot, "f64", array=True, dom=mask.code if mask is not None else None, explicit=True)
 
     def e_Subscript(self, node):
         if self.is_sample(node):
@@ -630,6 +726,10 @@ class _Translator(ast.NodeVisitor):
         return None
 
     def e_Call(self, node):
+        from .kernels import convert_z_to_sigma_croco
+
+        if self.callee(node.func) is convert_z_to_sigma_croco:
+            return self.conversion(node)
         name = self.np_func(node)
         if name is None or node.keywords:
             raise NotTranslatable("call of something other than a supported numpy function")
@@ -1041,8 +1141,9 @@ class _Translator(ast.NodeVisitor):
 
 
 class UserKernelSource:
-    def __init__(self, name, decl, stages, touched, sampled=(), detached=False, counter=None):
+    def __init__(self, name, decl, stages, touched, sampled=(), detached=False, counter=None, sigma=False):
         self.name, self.decl, self.stages, self.touched, self.sampled = name, decl, stages, touched, list(sampled)
+        self.sigma = sigma  # calls convert_z_to_sigma_croco: only the CROCO sigma loop serves its conversion requests
         self.detached = detached  # samples without the particles: restores PCtx::state / ei, which the dedicated kernels keep elsewhere
         # kernels that sample for a sub-selection of the particles: a lane outside it goes straight on to the statements behind the sample,
         # so the stage the caller counts (one per request) is not the place in the kernel any more -- the kernel keeps its own (this slot)
@@ -1068,7 +1169,7 @@ def translate(func, pclass, fieldset, var_slot, field_ids, next_dt_f32=False, sl
         raise NotTranslatable(f"source of {getattr(func, '__name__', func)!r} is not available: {e}") from None
     tr.run()
     counter = tr.new_slot("i32", "stage") if tr.conditional else None
-    return UserKernelSource(func.__name__, tr.decl, tr.stages, tr.touched, tr.sampled, tr.detached, counter)
+    return UserKernelSource(func.__name__, tr.decl, tr.stages, tr.touched, tr.sampled, tr.detached, counter, tr.sigma)
 
 
 def candidate_variables(func, pclass):
@@ -1159,6 +1260,42 @@ extern "C" void pk_user_launch(const void* kargs, int32_t prog, int32_t key, int
 """
 
 
+# The module of a kernel list on a CROCO fieldset: the step loop of csrc/pk_sigma.h (advect_sigma_kernel), which carries the two CROCO kernels
+# and serves the conversion requests of translated `convert_z_to_sigma_croco` calls.  Its variants are the keys PK_USER_KEY_SIGMA + (float32
+# fields ? 4 : 0) + (curvilinear ? 2 : 0) + interp_uv (0 / 1) -- what launch_sigma dispatches on; the dynamic LDS holds the level table.
+PK_USER_SIGMA, PK_USER_KEY_SIGMA = _hip.PK_USER_SIGMA, _hip.PK_USER_KEY_SIGMA
+_TEMPLATE_SIGMA = """// generated by parcels_amd/jit.py -- user kernels in the CROCO sigma loop: {names}
+#define PK_USER_KERNELS 1
+#define PK_SIGMA_KERNELS 1
+#include <stdint.h>
+namespace pk {{
+struct PkUserLocals {{
+{decl}
+}};
+}}
+#include "pk_sigma.h"
+namespace pk {{
+PK_DEV bool user_prepare(const KArgs& a, int uk, int stage, int kslot, PCtx& c, PState& p, KLocal& L, Request& rq) {{
+    switch (uk) {{
+{cases}
+        default: c.state = PK_ERROR; return true;
+    }}
+}}
+}}  // namespace pk
+extern "C" void pk_user_launch(const void* kargs, int32_t prog, int32_t key, int32_t lds, uint64_t lds_bytes, void* stream) {{
+    using namespace pk;
+    const KArgs& a = *(const KArgs*)kargs;
+    if (prog != 0 || key != {key} || a.sigma.n < 2 || lds_bytes != (uint64_t)a.sigma.n * 16 || (uint64_t)lds != lds_bytes) {{
+        fprintf(stderr, "parcels_amd user program built for the sigma variant (0, %d) with 16 LDS bytes per level, launched as (%d, %d, %d) with %llu LDS bytes for %d levels\\n",
+                {key}, prog, key, lds, (unsigned long long)lds_bytes, a.sigma.n);
+        abort();
+    }}
+    hipLaunchKernelGGL((advect_sigma_kernel<{ft}, {kind}, {interp}>), dim3((unsigned)((a.p.n + 255) / 256)), dim3(256), (size_t)lds_bytes,
+                       (hipStream_t)stream, a);
+}}
+"""
+
+
 def _csrc_hash() -> str:
     h = hashlib.sha256()
     for f in sorted(os.listdir(_CSRC)):
@@ -1186,7 +1323,8 @@ class UserProgram:
     """One compiled module: the kernel-list interpreter of ONE variant with up to PK_MAX_USER_KERNELS user kernels in it."""
 
     def __init__(self, sources: list[UserKernelSource], key: int, lds: int, fast: int = 0, particles_f32: bool = False):
-        """key / lds: the interpreter variant (pk_generic_variant; key PK_USER_KEY_UX: the step loop of a UxGrid, csrc/pk_ux.h).
+        """key / lds: the interpreter variant (pk_generic_variant; key PK_USER_KEY_UX: the step loop of a UxGrid, csrc/pk_ux.h; keys
+        PK_USER_KEY_SIGMA .. + 7: the CROCO sigma loop, csrc/pk_sigma.h, whose LDS size is the launch's and not part of the module).
         fast: 1 / 2 = also carry the dedicated A-grid kernel (2-D / 3-D) with the user kernels riding along -- only for modules whose
         kernels sample no field and leave next_dt alone."""
         if not (1 <= len(sources) <= PK_MAX_USER_KERNELS):
@@ -1196,15 +1334,18 @@ class UserProgram:
         # the locals of different kernels never live at the same time, but they are few: one struct, distinct names
         cases = "\n".join(f"        case {k}: {{\n" + textwrap.indent(s.case_body(), "            ") + "\n        }" for k, s in enumerate(sources))
         self.ux = key == PK_USER_KEY_UX
-        if not (0 <= key < 12 or self.ux):
+        self.sigma = PK_USER_KEY_SIGMA <= key < PK_USER_KEY_SIGMA + 8
+        if not (0 <= key < 12 or self.ux or self.sigma):
             raise NotTranslatable(f"unknown program variant {key}")
+        if any(s.sigma for s in sources) and not self.sigma:
+            raise NotTranslatable("convert_z_to_sigma_croco needs the module of the CROCO sigma loop (a PK_USER_KEY_SIGMA variant)")
         ft = "float" if 6 <= key < 12 else "double"
         kind, interp = (key % 6) // 3, key % 3
         # what the kernels sample decides whether the list may ride in a dedicated kernel (pk_generic_variant was asked with the same lists)
         sampled = [x for src in sources for x in src.sampled]
         self.sample_fids = sorted({x for x in sampled if isinstance(x, int)})
         self.sample_flags = (2 if "UV" in sampled else 0) | (4 if "UVW" in sampled else 0)  # PK_USER_SAMPLES_UV / _UVW
-        rides = fast and not self.ux and all("next_dt" not in src.touched and not src.detached for src in sources) and len(self.sample_fids) <= 4
+        rides = fast and not self.ux and not self.sigma and all("next_dt" not in src.touched and not src.detached for src in sources) and len(self.sample_fids) <= 4
         self.flags = (1 | self.sample_flags) if rides else self.sample_flags  # PK_USER_RIDE: the module carries the dedicated kernel
         fast_launch = ""
         if self.flags & 1:
@@ -1226,6 +1367,12 @@ class UserProgram:
                 raise NotTranslatable("the UxGrid program stages nothing in LDS")
             self.flags = PK_USER_UX | self.sample_flags
             self.source = _TEMPLATE_UX.format(names=names, decl=decl, cases=cases, key=key, pfm=1 if particles_f32 else 0)
+        elif self.sigma:
+            v = key - PK_USER_KEY_SIGMA
+            self.flags = PK_USER_SIGMA | self.sample_flags
+            self.sample_fids = self.sample_fids[:4]  # (pk_set_user_program takes four: only a dedicated kernel with riders reads them)
+            self.source = _TEMPLATE_SIGMA.format(names=names, decl=decl, cases=cases, key=key, ft="float" if v & 4 else "double", kind=(v >> 1) & 1,
+                                                 interp=v & 1)
         else:
             self.source = _TEMPLATE.format(names=names, decl=decl, cases=cases, key=key, lds=lds, ft=ft, kind=kind, interp=interp,
                                            ldsb="true" if lds else "false", fast_launch=fast_launch)
@@ -1290,6 +1437,8 @@ def compile_kernel_list(functions, builtin_id, pclass, fieldset, engine, samples
     funcs = [f for f in functions if builtin_id(f) is None]
     if not funcs:
         raise NotTranslatable("no Python function in the list")
+    if getattr(getattr(engine, "lib", None), "pk_generic_variant", None) is None:
+        raise NotTranslatable("this engine compiles no user kernels (its library has no pk_generic_variant)")
     if len(funcs) > PK_MAX_USER_KERNELS:
         raise NotTranslatable(f"more than {PK_MAX_USER_KERNELS} Python kernels in one list")
     names = {v.name: v for v in pclass.variables}
@@ -1314,10 +1463,15 @@ def compile_kernel_list(functions, builtin_id, pclass, fieldset, engine, samples
         ids.append(kid)
     # which programs this list runs as on this FieldSet: the variant of the kernel-list interpreter, and whether the dedicated A-grid kernel
     # would take it if the user kernels sample nothing
+    sigma = any(src.sigma for src in sources)
+    if sigma:  # (a list without a CROCO id: nothing else has put the CROCO parameters on the context yet)
+        from .kernel import croco_parameters
+
+        engine.set_croco(croco_parameters(fieldset))
     prm = engine.make_params(ids, endtime=0.0, dt0=1.0, context=fieldset.context, samples=samples or {})
     sampled = [x for src in sources for x in src.sampled]
     fids = sorted({x for x in sampled if isinstance(x, int)})
-    sflags = (2 if "UV" in sampled else 0) | (4 if "UVW" in sampled else 0)
+    sflags = (2 if "UV" in sampled else 0) | (4 if "UVW" in sampled else 0) | (PK_USER_SIGMA if sigma else 0)  # (announces a sigma module)
     key, lds, typed, fast = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
     cf = (C.c_int32 * 4)(*(fids + [0] * 4)[:4])
     engine.ctx.check(engine.lib.pk_generic_variant(engine.ctx.handle, C.byref(prm), sflags, min(len(fids), 4), cf, C.byref(key), C.byref(lds), C.byref(typed),

@@ -399,11 +399,7 @@ class Kernel:
         engine = pset._engine()
         pset._t_live = None
         if self.host_functions and not self._jit_tried:
-            if any(_is_croco(f) for f in self._kernels):  # no compiled user kernels next to a CROCO kernel (csrc/pk_sigma.h)
-                self._jit_tried = True
-                self.jit_report = "user kernels are not compiled next to a CROCO kernel"
-            else:
-                self._try_jit(pset)
+            self._try_jit(pset)
         engine.device_variables = list(self.device_variables)
         engine.bind_particles(pset._data)
         engine.h2d()

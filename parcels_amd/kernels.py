@@ -187,7 +187,8 @@ def convert_z_to_sigma_croco(fieldset, t, z, y, x, particle=None):
         sigma = convert_z_to_sigma_croco(fieldset, particles.t, particles.z, particles.y, particles.x, particles)
         particles.temp = fieldset.T[particles.t, sigma, particles.y, particles.x, particles]
 
-    works on the host path as in the reference."""
+    works on the host path as in the reference.  Written like that in a kernel the translator accepts (parcels_amd/jit.py), the call is
+    compiled into the fused sigma loop and this body does not run."""
     import numpy as np
 
     from .kernel import croco_parameters

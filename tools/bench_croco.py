@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Throughput of the CROCO sigma-grid kernels (csrc/pk_sigma.h).
 
-    python tools/bench_croco.py [--particles 1e6,1e7] [--repeats 5] [--steps 50] [--host-particles 1e5] [--out profiles/croco_bench.json]
+    python tools/bench_croco.py [--particles 1e6,1e7] [--repeats 5] [--steps 50] [--host-particles 1e5] [--legs a,b,..] [--out profiles/croco_bench.json]
 
 Workload: a 512 x 512 x 33-level float32 CROCO fieldset with 4 time levels (tools/make_croco_golden.py: croco_output, built through
 convert.croco_to_sgrid + FieldSet.from_sgrid_conventions), float64 particles, 50 steps of [AdvectionRK2_3D_CROCO, SampleOmegaCroco] per
@@ -9,6 +9,12 @@ launch: one cold launch, then the median of the timed ones with min / max, parti
 for scale: AdvectionRK2_3D on the same fieldset (2 field evaluations per step against 13 + 3; the particles' z is then a sigma level), the
 documented recipe as a Python kernel on the host path at --host-particles, and the registers / scratch / LDS of the kernel from
 tools/kernel_resources.sh (compile-only: VGPRs, scratch, waves per SIMD; the dynamic LDS is 16 bytes per sigma level).  Prints one JSON line per leg and writes them all to --out.
+
+Python kernels in the list (parcels_amd/jit.py compiles them into the sigma loop): croco_rk2_3d_python_delete is the list of the reference's
+CROCO tutorial, [AdvectionRK2_3D_CROCO, DeleteParticle] with its two-line Python DeleteParticle; croco_rk2_3d_python_recipe is the documented
+sampling recipe as a Python function next to AdvectionRK2_3D_CROCO, the twin of croco_rk2_3d_sample_omega (both also at --host-particles,
+to stand beside the host-path legs); host_path_python_delete is the tutorial's list with PARCELS_AMD_JIT=0.  --legs picks legs by name;
+PARCELS_HIP_LIB runs the built-in and host-path legs on another build of the library (A/B against a parent commit).
 """
 
 from __future__ import annotations
@@ -62,6 +68,8 @@ def timed(fs, kernels, x, y, z, steps, repeats, variables=()):
         wall = time.perf_counter() - t0
         st = pset._last_stats
         res.append({"wall_s": wall, "kernel_ms": float(st.get("kernel_ms", 0.0)), "steps": int(st.get("steps", 0)), "program": st.get("program")})
+        if any(pa.kernels.kernel_id(k) is None for k in kernels) and (st.get("hosted") or pset._kernel.user_program is None):
+            raise RuntimeError(f"the Python kernels of the list were not compiled: {pset._kernel.jit_report}")
     cold, warm = res[0], res[1:]
     km = sorted(r["kernel_ms"] for r in warm)
     med = km[len(km) // 2]
@@ -88,6 +96,35 @@ def host_recipe(particles, fieldset):
     particles.omega = fieldset.omega[particles.t, sigma, particles.y, particles.x, particles]
 
 
+def DeleteParticle(particles, fieldset):  # noqa: N802 -- docs/user_guide/examples/tutorial_croco_3D.ipynb
+    any_error = particles.state >= 50
+    particles[any_error].state = pa.StatusCode.Delete
+
+
+def hosted(fs, kernels, x, y, z, steps, variables=()):
+    """the list on the host path (PARCELS_AMD_JIT=0): one run, wall time"""
+    pclass = pa.get_default_particle(np.float64)
+    for v in variables:
+        pclass = pclass.add_variable(pa.Variable(v, dtype=np.float64, initial=0))
+    before = os.environ.get("PARCELS_AMD_JIT")
+    os.environ["PARCELS_AMD_JIT"] = "0"
+    try:
+        t0 = time.perf_counter()
+        pset = pa.ParticleSet(fs, pclass=pclass, x=x, y=y, z=z, t=np.zeros(x.size))
+        t1 = time.perf_counter()
+        pset.execute(kernels, dt=DT, runtime=steps * DT)
+        wall, execute_wall = time.perf_counter() - t0, time.perf_counter() - t1
+    finally:
+        if before is None:
+            del os.environ["PARCELS_AMD_JIT"]
+        else:
+            os.environ["PARCELS_AMD_JIT"] = before
+    if not pset._last_stats.get("hosted"):
+        raise RuntimeError("the list did not run on the host path")
+    # (wall_s includes the construction of the ParticleSet, as the leg always did; execute_wall_s is what `wall_s_median` of a timed leg is)
+    return {"particles": int(x.size), "steps": steps, "wall_s": wall, "execute_wall_s": execute_wall, "particle_steps_per_s": x.size * steps / wall}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--particles", default="1e6,1e7")
@@ -96,31 +133,43 @@ def main():
     ap.add_argument("--host-particles", default="1e5")
     ap.add_argument("--host-steps", type=int, default=5)
     ap.add_argument("--no-resources", action="store_true")
+    ap.add_argument("--legs", default="", help="comma-separated leg names (default: all)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     fs, coords, fields = fieldset()
     legs = []
 
+    only = {v for v in a.legs.split(",") if v}
+
+    def want(name):
+        return not only or name in only
+
     def emit(leg):
         legs.append(leg)
         print(json.dumps(leg), flush=True)
 
-    for n in [int(float(v)) for v in a.particles.split(",") if v]:
-        x, y, z = particles(coords, fields, n)
-        emit({"leg": "croco_rk2_3d_sample_omega", **timed(fs, [pa.AdvectionRK2_3D_CROCO, pa.SampleOmegaCroco], x, y, z, a.steps, a.repeats, ("omega",))})
-        x, y, z = particles(coords, fields, n, sigma_z=True)
-        emit({"leg": "advection_rk2_3d_same_fieldset", **timed(fs, [pa.AdvectionRK2_3D], x, y, z, a.steps, a.repeats)})
     nh = int(float(a.host_particles))
+    sizes = [int(float(v)) for v in a.particles.split(",") if v]
+    for n in sizes:
+        x, y, z = particles(coords, fields, n)
+        if want("croco_rk2_3d_sample_omega"):
+            emit({"leg": "croco_rk2_3d_sample_omega", **timed(fs, [pa.AdvectionRK2_3D_CROCO, pa.SampleOmegaCroco], x, y, z, a.steps, a.repeats, ("omega",))})
+        if want("advection_rk2_3d_same_fieldset"):
+            xs, ys, zs = particles(coords, fields, n, sigma_z=True)
+            emit({"leg": "advection_rk2_3d_same_fieldset", **timed(fs, [pa.AdvectionRK2_3D], xs, ys, zs, a.steps, a.repeats)})
+    for n in sizes + ([nh] if nh > 0 and nh not in sizes else []):  # (the Python lists also at the size of the host-path legs)
+        x, y, z = particles(coords, fields, n)
+        if want("croco_rk2_3d_python_delete"):
+            emit({"leg": "croco_rk2_3d_python_delete", **timed(fs, [pa.AdvectionRK2_3D_CROCO, DeleteParticle], x, y, z, a.steps, a.repeats)})
+        if want("croco_rk2_3d_python_recipe"):
+            emit({"leg": "croco_rk2_3d_python_recipe", **timed(fs, [pa.AdvectionRK2_3D_CROCO, host_recipe], x, y, z, a.steps, a.repeats, ("omega",))})
     if nh > 0:
         x, y, z = particles(coords, fields, nh)
-        t0 = time.perf_counter()
-        pclass = pa.get_default_particle(np.float64).add_variable(pa.Variable("omega", dtype=np.float64, initial=0))
-        pset = pa.ParticleSet(fs, pclass=pclass, x=x, y=y, z=z, t=np.zeros(nh))
-        pset.execute([host_recipe], dt=DT, runtime=a.host_steps * DT)
-        wall = time.perf_counter() - t0
-        emit({"leg": "host_path_recipe_sample_omega", "particles": nh, "steps": a.host_steps, "wall_s": wall,
-              "particle_steps_per_s": nh * a.host_steps / wall})
-    if not a.no_resources:
+        if want("host_path_recipe_sample_omega"):
+            emit({"leg": "host_path_recipe_sample_omega", **hosted(fs, [host_recipe], x, y, z, a.host_steps, ("omega",))})
+        if want("host_path_python_delete"):
+            emit({"leg": "host_path_python_delete", **hosted(fs, [pa.AdvectionRK2_3D_CROCO, DeleteParticle], x, y, z, a.host_steps)})
+    if not a.no_resources and want("kernel_resources"):
         emit({"leg": "kernel_resources", "lds_bytes_per_workgroup": 16 * 33, "kernels": kernel_resources()})
     if a.out:
         with open(a.out, "w") as f:
