@@ -35,6 +35,8 @@ struct FastTabs {  // LDS-resident {a, 1/width} tables of the main grid and the 
     // round trip of ~200 cycles that also drains the LDS counter)
     double tlen;
     int32_t gny, gnx;
+    // PK_FAST_CONV_STEP: the two factors of the unit conversion, made opaque scalars once per step by the step loop (pk_kernels.h)
+    double deg2m, inv_deg2m;
 };
 PK_DEV void pin_scalars(FastTabs& T, const FastA& F) {
     T.tlen = F.tlen;
@@ -512,6 +514,43 @@ constexpr bool fast_block_regs(int lp, bool pf) { return PK_FAST_BLOCK_REGS != 0
 #endif
 constexpr bool fast_time_rec(int lp, bool pf) { return PK_FAST_TIME_REC != 0 && fast_block_regs(lp, pf); }
 
+// ---- the hit path's non-arithmetic VALU (the kernels with the block in registers only) -----------------------------------------------------------
+// Counted on the path a wave-evaluation of the looped stages 2-4 takes when every lane stays in its cell and its time cell (0.79 of them):
+// 96 VALU, of which the reference's arithmetic needs about 68 (profiles/c2_hit_path_trim_ab.txt).  Each step that was kept has its macro; all at 0 compile
+// to the code before (A/B builds).  FAST_LP_REGS -- the bit-for-bit partner of the tests --, FAST_LP_OFF, the instantiations for float32
+// particle storage and modules with user kernels keep their code.
+// PK_FAST_WSUM: the stage weights of su = u1 + 2*u2 + 2*u3 + u4 as ONE fused operation, su = fma(wgt, u, su) with wgt = 2.0 or 1.0 in a
+// scalar register pair (fma3s: the three-address v_fma_f64; the translation unit is built with -ffp-contract=off, so the compiler forms
+// none itself).  The stage loop is not unrolled: for `su + 2*u` / `su + u` it formed u + u, chose between u and 2u with two v_cndmask_b32
+// and added -- 8 VALU for U and V where 2 suffice.  The same bits: 2*u is exact for every finite |u| < 2^1023, subnormals included, so
+// both forms round the same exact sum once (tests/test_wsum_fma.py).  The ONE exception: |u| >= 2^1023, where 2*u overflows to infinity
+// before the addition and the fused form may stay finite (a velocity of 1e308 m/s).
+// PK_FAST_CONV_STEP: deg2m and 1 / deg2m of the unit conversion become opaque scalars at the top of every STEP (FastTabs::deg2m, inv_deg2m;
+// pk_kernels.h).  As kernel arguments they lived across the whole kernel, were spilled to VGPR lanes and came back through six v_readlane_b32
+// in front of every conversion; a pair that lives for one step the allocator keeps in scalar registers: 6 VALU less per evaluation, 58 -> 48
+// v_readlane_b32 inside the stage loop, one scalar load per step.
+// Built and not kept: u = v = 0 filled only on the paths that return early (time error, out-of-bounds code) -- the allocator answered with
+// 48 B of scratch per lane in both float64-storage instantiations, alone and beside the other steps; the stage position reading the
+// registers the evaluation leaves u and v in (no lu, lv) -- the two copies stayed, for as long as the zero fill stands in front of them.
+#ifndef PK_FAST_WSUM
+#define PK_FAST_WSUM 1
+#endif
+#ifndef PK_FAST_CONV_STEP
+#define PK_FAST_CONV_STEP 1
+#endif
+#ifdef PK_USER_KERNELS
+constexpr bool fast_wsum(int, bool) { return false; }
+constexpr bool fast_conv_step(int, bool) { return false; }
+#else
+constexpr bool fast_wsum(int lp, bool pf) { return PK_FAST_WSUM != 0 && fast_block_regs(lp, pf); }
+constexpr bool fast_conv_step(int lp, bool pf) { return PK_FAST_CONV_STEP != 0 && fast_block_regs(lp, pf); }
+#endif
+PK_DEV double fma3s(double wgt, double b, double c) {  // fma(wgt, b, c), wgt wave-uniform: read from its scalar register pair
+    double r;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "s"(wgt), "v"(b), "v"(c));
+    return r;
+}
+
 // The status rules of eval_uvw_fast for an evaluation some index of which carries an out-of-bounds code (field.py:307-378; the record's cold path)
 PK_DEV int fast_oob_state(int s, int xi, int yi, int zi, double xsi, double eta, double zeta, double tau) {
     if ((xi == RIGHT_OUT_OF_BOUNDS || yi == RIGHT_OUT_OF_BOUNDS || zi == RIGHT_OUT_OF_BOUNDS) && s < PK_ERROROUTOFBOUNDS) s = PK_ERROROUTOFBOUNDS;
@@ -820,11 +859,12 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
     if (fl & FA_SPH) {  // _xinterpolators.py:183-187
         double conv;
         if (PF && pos_f32) conv = (double)((float)F.deg2m * cosf((float)y * DEG2RADF));
+        else if constexpr (fast_conv_step(LP, PF)) conv = T.deg2m * cos_lat_lean(y);
         else if constexpr (PK_FAST_LEAN != 0) conv = F.deg2m * cos_lat_lean(y);
         else conv = F.deg2m * cos_lat(y * DEG2RAD);
         if constexpr (PK_FAST_LEAN != 0) {  // u / conv, v / deg2m within 1.5 ulp: 7 operations instead of 22
             uu = uu * rcp_lean(conv);
-            vv = vv * F.inv_deg2m;
+            vv = vv * (fast_conv_step(LP, PF) ? T.inv_deg2m : F.inv_deg2m);
         } else {
             uu /= conv;
             vv = div_by_recip(vv, F.deg2m, F.inv_deg2m);

@@ -815,6 +815,11 @@ __global__ void __launch_bounds__(fast_wg(LP), PK_MIN_WAVES_FAST) advect_fast_ke
                 while (c.state == PK_EVALUATE) {  // :190 (no kernel of these programs sets Repeat)
                     uint32_t fl = ft.fl;  // (FastTabs::fl: the step loop's yes / no questions as scalar bit tests, not as saved lane masks)
                     asm volatile("" : "+s"(fl));
+                    if constexpr (fast_conv_step(LP, pf)) {  // (pk_fast_agrid.h: PK_FAST_CONV_STEP)
+                        ft.deg2m = a.fast.deg2m;
+                        ft.inv_deg2m = a.fast.inv_deg2m;
+                        asm volatile("" : "+s"(ft.deg2m), "+s"(ft.inv_deg2m));
+                    }
                     const bool fwd = (fl & FA_FWD) != 0;                   // sign = 1 if dt0 > 0 else -1 (kernel.py:186)
                     const double tte = fwd ? endtime - pt : -(endtime - pt);  // sign * (endtime - t), the sign of a zero included
                     if (!(tte >= 0)) break;  // :193-197
@@ -865,7 +870,11 @@ __global__ void __launch_bounds__(fast_wg(LP), PK_MIN_WAVES_FAST) advect_fast_ke
                         // stages 2 / 3 share t, stage 4 and stage 1 of the next step too: the odd evaluations keep their corner block, the even
                         // ones test it (pk_fast_agrid.h: FCtx::bei)
                         eval_uvw_fast<FT, pf, D3, LP>(a, ft, c, st, sz, sy, sx, pf && stage == 0, u, v, w, it, adv * 1000 + stage, (stage & 1) ? 2 : 1);
-                        if (stage == 0) { su = u; sv = v; sw = w; }
+                        if constexpr (fast_wsum(LP, pf)) {  // (stage 1 is peeled: stages 2 and 3 weigh 2, stage 4 weighs 1; pk_fast_agrid.h: PK_FAST_WSUM)
+                            const double wgt = stage == 3 ? 1.0 : 2.0;
+                            su = fma3s(wgt, u, su);
+                            sv = fma3s(wgt, v, sv);
+                        } else if (stage == 0) { su = u; sv = v; sw = w; }
                         else if (stage == 3) { su = su + u; sv = sv + v; sw = sw + w; }
                         else { su = su + 2 * u; sv = sv + 2 * v; sw = sw + 2 * w; }
                         lu = u; lv = v; lw = w;
