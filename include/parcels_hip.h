@@ -129,6 +129,9 @@ const char* pk_last_error(const pk_ctx* ctx); /* ctx may be NULL: error of the l
  *                      cache or the launch fails (3-D advection, a list with compiled user kernels, tables too large).  In the library's
  *                      2-D kernel 0 and 2 run one arithmetic and agree in every bit; PK_NO_BLOCK_CACHE (environment) = no cache at all,
  *                      with the lerps in the reference's order
+ *   "miss_lanes"       level-pair cache: the most missing lanes of a complete wavefront whose blocks are fetched TRANSPOSED -- sixteen lanes per
+ *                      missing lane, one load each, one round trip -- instead of by the waterfall over the level pairs: -1 (default) the
+ *                      planned value (4: one pass), 0 never, up to 64.  A speed knob only: every value gives the same bits
  *   "fast_grid"        workgroups of the persistent launch of the level-pair-cache kernel, whose wavefronts claim chunks of 64 rows until none is
  *                      left (csrc/pk_kernels.h: fast_persistent): 0 (default) as many as are resident at once, v > 0 at most v (tests and
  *                      sweeps: results do not depend on it)

@@ -202,6 +202,7 @@ struct pk_ctx {
     int no_fast_cgrid = 0;
     bool no_block_cache = false;  // PK_NO_BLOCK_CACHE: the 2-D A-grid kernel without its per-lane corner-block cache
     int block_cache = -1;         // option "block_cache": -1 plan_launch's rule, 0 none, 1 stage-pair block, 2 level-pair cache or fail
+    int miss_lanes = -1;          // option "miss_lanes": the most missing lanes of a wavefront the level-pair cache fetches transposed, -1 planned
     int fast_grid = 0;            // option "fast_grid": workgroups of the persistent A-grid launch -- 0 what is resident at once (pk_kernels.h), v > 0 at most v
     // asynchronous write-out snapshots (pk_particles_snapshot_begin / _wait): two sets of device staging columns (host row order)
     // + pinned host columns, so that the D2H and the encode of interval k overlap the launch of interval k+1
@@ -762,6 +763,10 @@ int32_t pk_set_option(pk_ctx* ctx, const char* name, int32_t value) {
     else if (n == "block_cache") {
         if (value < -1 || value > 2) return ctx->fail("pk_set_option: block_cache is -1 (planned), 0 (none), 1 (stage-pair block) or 2 (level-pair cache)");
         ctx->block_cache = value;
+    }
+    else if (n == "miss_lanes") {
+        if (value < -1 || value > 64) return ctx->fail("pk_set_option: miss_lanes is -1 (planned), 0 (never) or the most missing lanes of a wavefront, up to 64");
+        ctx->miss_lanes = value;
     }
     else if (n == "fast_grid") {
         if (value < 0) return ctx->fail("pk_set_option: fast_grid is 0 (planned) or the largest number of workgroups of the persistent A-grid launch");
@@ -2527,6 +2532,7 @@ static int32_t plan_launch(pk_ctx* ctx, const pk_exec_params* prm, const UserSha
         if (mode == 2) {
             p.lp = FAST_LP_CACHE;
             a.fast.lds_blk = a.fast.lds_n;
+            a.fast.miss_lanes = ctx->miss_lanes < 0 ? FAST_MISS_LANES_DEFAULT : ctx->miss_lanes;  // (same bits at every value: a speed knob)
             p.lds += (size_t)FAST_LP_BYTES;
         } else if (mode == 0 && lp_kernel && !ctx->no_block_cache) {
             p.lp = FAST_LP_REGS;  // the cache's arithmetic without the cache: on / off is bit-identical

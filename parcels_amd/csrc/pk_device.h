@@ -123,7 +123,8 @@ struct FastA {
     double deg2m, inv_deg2m;
     // scalar fields a compiled user kernel samples while it rides in the dedicated kernel (parcels_amd/jit.py): same grid, dtype, layout,
     // time axis and ring as U -- only the base pointer differs -- and XLinear; sfid: their field ids (what Request::fidx names)
-    int32_t ns, pad1;
+    int32_t ns;
+    int32_t miss_lanes;                         // level-pair cache: the most missing lanes of a wavefront the transposed fetch serves, 0..64 (pk_fast_agrid.h)
     int32_t sfid[4];
     const char* S[4];
 };

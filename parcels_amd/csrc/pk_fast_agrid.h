@@ -551,6 +551,122 @@ PK_DEV double fma3s(double wgt, double b, double c) {  // fma(wgt, b, c), wgt wa
     return r;
 }
 
+// ---- the miss branch, transposed (the kernels with the block in registers only) ------------------------------------------------------------------
+// 0.21 of the headline launch's wave-evaluations hold a missing lane, ~1.3 of them each, and the waterfall above runs lp_fetch for them at wave
+// width: 16 wide loads in two dependent batches, ~56 fp64 operations and 64-bit scalar row bases for one or two working lanes.  The 16 corner
+// rows of ONE missing lane are 16 independent loads, and lp_field applies the same three operations to pairs of them: work for 16 lanes.
+// PK_FAST_MISS_XPOSE: when the wavefront is complete (all 64 lanes active), no ring is in use and at most `miss_lanes` lanes miss
+// (pk_set_option; FastTabs::fl carries it), each row of 16 lanes serves one missing lane m per pass -- row g the g-th set bit of the miss mask:
+//   * m's b00, zeta and key (ti, lenT, lenZ) reach the row through ds_bpermute_b32 (the crossbar: no LDS memory);
+//   * helper j = k | r << 1 | l << 2 | f << 3 (depth row, lat row, time level, U / V) forms its own 64-bit address and issues ONE ldpair, masked
+//     out where the reference does not read the row (level ti + 1 without lenT, depth row zi + 1 without lenZ): one vmem instruction and one
+//     round trip for both fields and both levels of up to four lanes, on whichever level pairs they sit -- no waterfall;
+//   * three exchange steps (DPP), each run once by the whole wavefront, are lp_field's operations on lp_field's operands: the z lerp with
+//     lane j^1, the level difference with lane j^4, the polynomial basis with lane j^2 (tests/test_lp_transposed_model.py pins map and order);
+//   * the k = 0 lane (f, l, r) holds entry 4f + 2l + r of m's slot and writes it: one ds_write_b128 per pass.
+// Every other wave-evaluation with a missing lane -- a chunk's first one (64 missing lanes), a wavefront with deleted or finished lanes, a ring
+// launch -- takes the waterfall: the same bits, so the threshold is a speed knob only.  0 compiles to the code before (A/B builds).
+#ifndef PK_FAST_MISS_XPOSE
+#define PK_FAST_MISS_XPOSE 1
+#endif
+#ifdef PK_USER_KERNELS
+constexpr bool fast_miss_xpose(int, bool) { return false; }
+#else
+constexpr bool fast_miss_xpose(int lp, bool pf) { return PK_FAST_MISS_XPOSE != 0 && fast_block_regs(lp, pf); }
+#endif
+// Built and not kept (PK_FAST_MISS_KEEP): the hit lanes' block (FCtx::fu, fv) live across the transposed fetch, only the lanes that were served reading
+// their slot back.  The 32 registers do not fit beside the lane state and the helpers' values: 128 VGPRs and 160 B (float fields: 128 B) of scratch
+// per lane in the two instantiations, where the rule is none (profiles/c2_miss_transposed_ab.txt).
+constexpr int FAST_MISS_LANES_DEFAULT = 4;      // pk_set_option "miss_lanes" -1: one pass (profiles/c2_miss_transposed_ab.txt)
+constexpr uint32_t FA_MISS_LANES_SHIFT = 16u;   // FastTabs::fl bits 16-22: the threshold, 0..64
+// DPP controls: quad_perm [1,0,3,2] (lane j^1), quad_perm [2,3,0,1] (lane j^2), row_shr:4 (lane j - 4: j^4 for the lanes with bit 2 set)
+constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_SHR4 = 0x114;
+template <int CTRL, int BANKS>
+PK_DEV double dpp_f64(double v) {  // lanes of the banks not in BANKS keep v (all banks: every lane has a source, no old value to carry)
+    const uint64_t b = __builtin_bit_cast(uint64_t, v);
+    const int lo = (int)(uint32_t)b, hi = (int)(uint32_t)(b >> 32);
+    uint32_t rlo, rhi;
+    if constexpr (BANKS == 0xf) {
+        rlo = (uint32_t)__builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
+        rhi = (uint32_t)__builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
+    } else {
+        rlo = (uint32_t)__builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, BANKS, false);
+        rhi = (uint32_t)__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, BANKS, false);
+    }
+    return __builtin_bit_cast(double, (uint64_t)rlo | ((uint64_t)rhi << 32));
+}
+// ldpair (pk_device.h) at an address formed as an integer: the pointer says "global memory" (flat loads otherwise)
+PK_DEV void ldpair_at(uint64_t addr, double& a, double& b, double) {
+    const pk_double2 v = *reinterpret_cast<const __attribute__((address_space(1))) pk_double2*>((uintptr_t)addr);
+    a = v.x;
+    b = v.y;
+}
+PK_DEV void ldpair_at(uint64_t addr, double& a, double& b, float) {
+    const pk_float2 v = *reinterpret_cast<const __attribute__((address_space(1))) pk_float2*>((uintptr_t)addr);
+    a = (double)v.x;
+    b = (double)v.y;
+}
+PK_DEV uint32_t lane_u32(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)v); }
+// mm: the miss mask (wave-uniform, not 0); wkey, b00, zeta: each lane's own.  Requires all 64 lanes active and resident levels (no ring).
+// Written to hold FEW SCALAR REGISTERS: the stage loop around it already spills 121 SGPRs to VGPR lanes, and a first form of this block -- the lane's
+// bits k, r, l, f and its row as lane masks across the pass loop, the field bases and strides as scalars -- pushed 19 more out and put 205 more
+// v_readlane_b32 into the kernel, the hit path included: 7 % SLOWER than the parent with this block never taken.  So the lane's constants are VGPR
+// integers (opaque: not turned back into masks or scalars), the four lane numbers of a pass travel in ONE scalar, a byte each, and every mask is
+// formed where it is used.
+template <class FT>
+PK_DEV void lp_fetch_xposed(const FastA& F, const FastTabs& T, uint64_t mm, int wkey, uint32_t b00, double zeta) {
+    uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const uint64_t zb = __builtin_bit_cast(uint64_t, zeta);
+    // lane constants: the field's base, the byte offset of the lane's (depth, lat) row, the level stride (fill_fast: < 2^32)
+    const uint32_t kb = 0u - (lane & 1u), rb = 0u - ((lane >> 1) & 1u), fb = 0u - ((lane >> 3) & 1u);  // all ones where the bit is set
+    const uint64_t du = (uint64_t)(uintptr_t)F.U, dv = (uint64_t)(uintptr_t)F.V - du;
+    uint64_t fbase = du + ((uint64_t)((uint32_t)dv & fb) | ((uint64_t)((uint32_t)(dv >> 32) & fb) << 32));
+    uint64_t rowoff = (uint64_t)(F.dzb & kb) + (uint64_t)(F.dyb & rb);
+    uint32_t lvl_b = (uint32_t)F.lvl_b;
+    asm volatile("" : "+v"(fbase), "+v"(rowoff), "+v"(lvl_b), "+v"(lane));
+    do {
+        uint32_t four = 0u;  // the next four set bits of the mask, a byte each, 0xff = none (scalar)
+        for (int q = 0; q < 4; q++) {
+            four |= (mm ? (uint32_t)__builtin_ctzll(mm) : 0xffu) << (8 * q);
+            mm &= mm - 1;
+        }
+        uint32_t ln = lane;
+        asm volatile("" : "+v"(ln));  // (per pass: what is derived from it below is not hoisted into masks that live across the loop)
+        const uint32_t m = (four >> ((ln >> 4) * 8u)) & 0xffu;  // row g serves the g-th of them
+        const int src = (int)(m & 63u);
+        const uint32_t mb00 = lane_u32(b00, src), mkey = lane_u32((uint32_t)wkey, src);
+        const double mzeta = __builtin_bit_cast(double, (uint64_t)lane_u32((uint32_t)zb, src) | ((uint64_t)lane_u32((uint32_t)(zb >> 32), src) << 32));
+        const uint32_t lbit = (ln >> 2) & 1u;
+        const uint64_t addr = fbase + ((uint64_t)((mkey >> 2) + lbit) * (uint64_t)lvl_b + rowoff + (uint64_t)mb00);
+        // masked out of the load: a row without a lane to serve, the lower depth row without lenZ, level ti + 1 without lenT
+        const uint32_t skip = (m >> 7) | (ln & 1u & ~mkey) | (lbit & ~(mkey >> 1));
+        double cx = 0.0, cy = 0.0;
+        if (skip == 0u) ldpair_at(addr, cx, cy, FT());
+        // 1: the z lerp (k = 0 lanes with the row of lane j^1; what the k = 1 lanes form is read by nobody)
+        const double dx = dpp_f64<DPP_XOR1, 0xf>(cx), dy = dpp_f64<DPP_XOR1, 0xf>(cy);
+        const double zx = fma(mzeta, dx - cx, cx), zy = fma(mzeta, dy - cy, cy);
+        const bool lenZ = (mkey & 1u) != 0;
+        cx = lenZ ? zx : cx;
+        cy = lenZ ? zy : cy;
+        // 2: level ti + 1 minus level ti (l = 1 lanes: banks 1 and 3 of the row take lane j - 4), or zero where it was not read
+        const double ax = dpp_f64<DPP_SHR4, 0xa>(cx), ay = dpp_f64<DPP_SHR4, 0xa>(cy);
+        const bool lenT = (mkey & 2u) != 0;
+        const double ex = lenT ? cx - ax : 0.0, ey = lenT ? cy - ay : 0.0;
+        const bool l = lbit != 0;
+        cx = l ? ex : cx;
+        cy = l ? ey : cy;
+        // 3: the polynomial basis {P0, Px} (r = 0), {Py, Pxy} (r = 1)
+        const double h = cy - cx;
+        const double ox = dpp_f64<DPP_XOR2, 0xf>(cx), oh = dpp_f64<DPP_XOR2, 0xf>(h);
+        const bool r = (ln & 2u) != 0;
+        pk_tab2 e;
+        e.x = r ? cx - ox : cx;
+        e.y = r ? h - oh : h;
+        // the k = 0 lane (f, l, r) holds entry 4f + 2l + r of lane m's slot
+        if (((m >> 7) | (ln & 1u)) == 0u) (T.blk + ((int)m - (int)ln))[((ln >> 1) & 7u) * FAST_WG_LP] = e;
+    } while (mm);
+}
+
 // The status rules of eval_uvw_fast for an evaluation some index of which carries an out-of-bounds code (field.py:307-378; the record's cold path)
 PK_DEV int fast_oob_state(int s, int xi, int yi, int zi, double xsi, double eta, double zeta, double tau) {
     if ((xi == RIGHT_OUT_OF_BOUNDS || yi == RIGHT_OUT_OF_BOUNDS || zi == RIGHT_OUT_OF_BOUNDS) && s < PK_ERROROUTOFBOUNDS) s = PK_ERROROUTOFBOUNDS;
@@ -775,8 +891,21 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
         if (some_miss) {
             if (BR) zeta = depth_zeta();  // (its two reads are under way while the corner rows are requested)
             const int wkey = BR ? key | (lenZ ? 1 : 0) : key;
+            [[maybe_unused]] bool xposed = false;  // (wave-uniform) the transposed fetch served this wave-evaluation's missing lanes
+            if constexpr (fast_miss_xpose(LP, PF)) {  // few missing lanes of a complete wavefront, resident levels: sixteen helpers per missing lane
+                const uint64_t mm = __builtin_amdgcn_ballot_w64(miss);
+                xposed = __builtin_amdgcn_ballot_w64(true) == ~0ull && !(fl & FA_RING) &&
+                         (uint32_t)__builtin_popcountll(mm) <= ((fl >> FA_MISS_LANES_SHIFT) & 127u);
+                if (xposed) {
+                    lp_fetch_xposed<FT>(F, T, mm, wkey, b00, zeta);
+                    if (miss) {
+                        c.bei = c.ei;
+                        c.bkey = key;
+                    }
+                }
+            }
             // the waterfall over the key, as below (level bases stay in SGPRs); a lane that hit starts as done
-            for (bool done = !miss; !done;) {
+            for (bool done = !miss || xposed; !done;) {
                 const int uk = uniform_i32(wkey);
                 const int uti = uk >> 2;
                 int s0 = uti, s1 = uti + 1;
@@ -798,7 +927,7 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
             // The block goes to LDS BEHIND the waterfall, from the registers FAST_LP_REGS uses.  (Written inside it -- U's entries between the two
             // load batches, 4 VGPRs and 12 B of scratch less -- lanes of a wavefront that spans several level pairs read back other values
             // than they had formed: tests/test_gpu_level_pair_cache.py::test_staggered_release_times_and_ring.)
-            if (LP == FAST_LP_CACHE && miss) {
+            if (LP == FAST_LP_CACHE && miss && !xposed) {
                 T.blk[0] = fu.p0; T.blk[FAST_WG_LP] = fu.p1; T.blk[2 * FAST_WG_LP] = fu.d0; T.blk[3 * FAST_WG_LP] = fu.d1;
                 T.blk[4 * FAST_WG_LP] = fv.p0; T.blk[5 * FAST_WG_LP] = fv.p1; T.blk[6 * FAST_WG_LP] = fv.d0; T.blk[7 * FAST_WG_LP] = fv.d1;
                 c.bei = c.ei;

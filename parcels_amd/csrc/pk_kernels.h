@@ -774,6 +774,8 @@ __global__ void __launch_bounds__(fast_wg(LP), PK_MIN_WAVES_FAST) advect_fast_ke
         pin_scalars(ft, a.fast);
         ft.fl = fast_flags(a.fast) | ((a.win_lo > -INFINITY || a.win_hi < INFINITY) ? FA_WIN : 0u) | (a.prm.dt0 > 0 ? FA_FWD : 0u) |
                 (a.prm.max_iters > 0 ? FA_MAXIT : 0u);
+        // (pk_fast_agrid.h: PK_FAST_MISS_XPOSE -- the most missing lanes the transposed fetch serves, 0..64, beside the flags)
+        if constexpr (fast_miss_xpose(LP, PFM == 1)) ft.fl |= (uint32_t)a.fast.miss_lanes << FA_MISS_LANES_SHIFT;
     }
     // the persistent launch (fast_persistent, above): this wavefront's chunk of 64 rows and the shares it found empty, in scalar registers
     constexpr bool PERS = fast_persistent(LP);

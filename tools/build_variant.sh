@@ -4,7 +4,8 @@
 # Switches of the level-pair kernels (pk_fast_agrid.h), each 1 by default: -DPK_FAST_CELL_REGS=0 (table search in every evaluation),
 # -DPK_FAST_BLOCK_REGS=0 (the lane's block is read from LDS in every evaluation; also turns the time record off),
 # -DPK_FAST_TIME_REC=0 (the time memo instead of the time-cell record), -DPK_FAST_WSUM=0 (su + 2*u instead of the fused stage weights),
-# -DPK_FAST_CONV_STEP=0 (deg2m and 1 / deg2m as kernel arguments, not as scalars of one step)
+# -DPK_FAST_CONV_STEP=0 (deg2m and 1 / deg2m as kernel arguments, not as scalars of one step), -DPK_FAST_MISS_XPOSE=0 (the waterfall for every
+# missing lane: no transposed block fetch)
 set -e
 NAME=$1; shift
 cd "$(dirname "$0")/../parcels_amd/csrc"

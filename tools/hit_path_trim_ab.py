@@ -7,7 +7,7 @@
         no lane leaves its cell in 24 steps (at most 1e-4 m/s x 96 h = 35 m), so every wave-evaluation behind the launch's first runs the hit path.
     python tools/hit_path_trim_ab.py pmc [--uv-scale 1e-4] [--steps 24] [--out FILE] [--label TEXT]
         one rocprofv3 --pmc pass per counter group over a child that runs that one launch (a run of its own per group, no other tracing
-        than the kernel trace persistent_waves_ab.py uses), then VALU / SALU / LDS per wave-evaluation: a launch of n particles x K steps
+        than the kernel trace persistent_waves_ab.py uses), then VALU / SALU / LDS / vector-memory reads per wave-evaluation: a launch of n particles x K steps
         runs ceil(n / 64) x K x 4 wave-evaluations.
 
 The library is the one parcels_amd loads: PARCELS_HIP_LIB selects the parent's build.  --out appends the report to a text file.
@@ -25,7 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tools.persistent_waves_ab import sweep_report  # noqa: E402
 
-PMC_GROUPS = ["SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES", "SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES"]
+PMC_GROUPS = ["SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES", "SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES",
+              "SQ_INSTS_VMEM_RD SQ_INSTS_SMEM"]
 
 
 def sweep(steps, reps, particles, uv_scale, warmup=2):
@@ -96,7 +97,7 @@ def pmc(steps, particles, uv_scale):
                     meta = {"kernel": r["Kernel_Name"], **{k: int(r[c]) for k, c in (("vgpr", "VGPR_Count"), ("sgpr", "SGPR_Count"), ("scratch", "Scratch_Size")) if r.get(c)}}
     nwe = -(-int(particles) // 64) * steps * 4
     res = {"steps": steps, "particles": int(particles), "uv_scale": uv_scale, "counters": counters, "failed_groups": failed, "wave_evaluations": nwe, **meta}
-    for k in ("SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_LDS"):
+    for k in ("SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_LDS", "SQ_INSTS_VMEM_RD", "SQ_INSTS_SMEM"):
         if k in counters:
             res[k + "_per_wave_evaluation"] = counters[k] / nwe
     return res
