@@ -133,7 +133,7 @@ const char* pk_last_error(const pk_ctx* ctx); /* ctx may be NULL: error of the l
  *                      missing lane, one load each, one round trip -- instead of by the waterfall over the level pairs: -1 (default) the
  *                      planned value (4: one pass), 0 never, up to 64.  A speed knob only: every value gives the same bits
  *   "fast_grid"        workgroups of the persistent launch of the level-pair-cache kernel, whose wavefronts claim chunks of 64 rows until none is
- *                      left (csrc/pk_kernels.h: fast_persistent): 0 (default) as many as are resident at once, v > 0 at most v (tests and
+ *                      left (csrc/pk_kernels.h: fast_claim): 0 (default) as many as are resident at once, v > 0 at most v (tests and
  *                      sweeps: results do not depend on it)
  * Environment variables PK_NO_FAST, PK_NO_FAST_CGRID, PK_NO_VELOCITY_PAIRS, PK_NO_SPECIAL, PK_NO_CELL_CACHE, PK_NO_HASH_DIR, PK_NO_CELL_TABLE, PK_SORT_HORIZONTAL give the initial
  * values. */

@@ -27,30 +27,26 @@ struct FastTabs {  // LDS-resident {a, 1/width} tables of the main grid and the 
     const pk_tab2* lat;
     const pk_tab2* lon;
     pk_tab2* blk;  // this lane's corner-block cache (FCtx::bei): 4 x 16 bytes at stride FAST_WG (stage-pair block), or 8 x 16 bytes at stride
-                   // FAST_WG_LP (level-pair cache: the Z0 and D rows of U and V, eval_uvw_fast); NULL = none
+                   // FAST_WG_LP (level-pair cache: the Z0 and D rows of U and V, eval_uvw_lp); NULL = none
     uint32_t fl;   // FA_* bits of the wave-uniform yes / no questions of one evaluation (fast_flags)
-    // Scalars of FastA that every evaluation reads, PINNED in scalar registers by the kernel (pin_scalars: an opaque asm makes them values
-    // the allocator may spill to a VGPR lane -- one v_readlane where it is used -- but can no longer re-load from the kernel-argument
-    // segment: round 5's kernel did `s_load_dwordx2 ... 0x328` (tlen) + `s_waitcnt lgkmcnt(0)` in every evaluation, a scalar-cache
-    // round trip of ~200 cycles that also drains the LDS counter)
+    // Scalars of FastA that every evaluation reads, copied by the kernel (copy_scalars).  Built and not kept: pinning them in scalar registers
+    // behind an opaque asm, so that no evaluation re-loads them from the kernel-argument segment -- measured (profiles/r06c_*), the pinned
+    // build was no faster than the one that re-loads them (7.92-7.97 vs 7.60-7.63 ms on two boxes whose round-5 baselines differ by 2 %).
     double tlen;
     int32_t gny, gnx;
-    // PK_FAST_CONV_STEP: the two factors of the unit conversion, made opaque scalars once per step by the step loop (pk_kernels.h)
+    // the two factors of the unit conversion, made opaque scalars once per step by the step loop of the kernels that hold their block
+    // (fast_held; pk_kernels.h)
     double deg2m, inv_deg2m;
 };
-PK_DEV void pin_scalars(FastTabs& T, const FastA& F) {
+PK_DEV void copy_scalars(FastTabs& T, const FastA& F) {
     T.tlen = F.tlen;
     T.gny = F.gny;
     T.gnx = F.gnx;
-#ifdef PK_FAST_PIN  // measured (profiles/r06c_*): the pinned build is no faster than the one that re-loads them (7.92-7.97 vs 7.60-7.63 ms on
-                    // two boxes whose round-5 baselines differ by 2 %: within noise or slightly worse) -- off
-    asm volatile("" : "+s"(T.tlen), "+s"(T.gny), "+s"(T.gnx));
-#endif
 }
 // The wave-uniform booleans of an evaluation as bits of ONE scalar register.  Kept as separate loop-invariant i1 values the compiler
 // holds each of them as a 64-bit lane mask (`s_cselect_b64 -1, 0`): two SGPRs per question, 46 SGPRs spilled to VGPR lanes in round 5's
-// kernel and a `v_readlane_b32` -- a VALU instruction -- for every use inside the stage loop.  eval_uvw_fast re-reads the word through
-// an opaque scalar at its top, so every test is an `s_bitcmp` + `s_cbranch_scc` where it is used.
+// kernel and a `v_readlane_b32` -- a VALU instruction -- for every use inside the stage loop.  The evaluators re-read the word through
+// an opaque scalar at their top, so every test is an `s_bitcmp` + `s_cbranch_scc` where it is used.
 enum : uint32_t {
     FA_TI = 1u, FA_Z = 2u, FA_Y = 4u, FA_X = 8u, FA_SPH = 16u, FA_RING = 32u, FA_BLK = 64u,
     FA_NT2 = 128u, FA_NZ2 = 256u, FA_NY2 = 512u, FA_NX2 = 1024u,  // the axis has at least two nodes (index_search.py:45-46)
@@ -128,7 +124,7 @@ PK_DEV double cos_lat_lean(double lat_deg) {
 
 constexpr int FAST_WG = 256;                          // lanes per workgroup of advect_fast_kernel
 constexpr int FAST_BLK_BYTES = FAST_WG * 8 * 8;       // LDS of the corner-block cache per workgroup (8 doubles per lane)
-// Modes of the 2-D kernel's corner cache (template parameter LP of eval_uvw_fast / advect_fast_kernel; pk_set_option "block_cache"):
+// Modes of the 2-D kernel's corner cache (template parameter LP of advect_fast_kernel, which calls eval_uvw_fast for the first and eval_uvw_lp for the other two; pk_set_option "block_cache"):
 //   FAST_LP_OFF   the stage-pair block of FCtx::bei, or nothing (wave-uniform at run time: FA_BLK), lerps in the reference's order;
 //   FAST_LP_REGS  the level-pair arithmetic (lp_field) with Z0 / D formed in registers in every evaluation: the A/B partner of the cache;
 //   FAST_LP_CACHE the level-pair cache: Z0 / D of the lane's cell live in its LDS slot across evaluations.
@@ -142,8 +138,7 @@ constexpr int fast_wg(int lp) { return lp == FAST_LP_CACHE ? FAST_WG_LP : FAST_W
 // clip(searchsorted(arr, x, "left") - 1, 0, n-2) over the interleaved table.  Cold (a lane that moved two cells or more, or holds a
 // NaN): one bisection loop -- the unrolled three-step walk of rounds 1-5 found the same index and cost the hot path seven nesting
 // levels of saved exec masks (14 SGPRs) at each of its four inlined copies.
-PK_DEV int cell_index_tab(const pk_tab2* tab, int n, double x, int i) {
-    (void)i;
+PK_DEV int cell_index_tab(const pk_tab2* tab, int n, double x) {
     asm volatile("" : "+s"(n));  // (wave-uniform; opaque so that `0 < n` of the loop entry is not hoisted into a saved lane mask)
     if (x != x) return n - 2;
     int lo = 0, hi = n;
@@ -180,7 +175,7 @@ PK_DEV void fast_search(const pk_tab2* tab, int n, double first, double last, do
         double b1 = tab[j + 1].x;
         asm volatile("" : "+v"(b1));  // both reads in flight together (not the second one behind the first compare's short circuit)
         if (__builtin_expect(!((e2.x < x || j == 0) && (x <= b1 || j == n - 2)), 0)) {
-            j = cell_index_tab(tab, n, x, j);
+            j = cell_index_tab(tab, n, x);
             e2 = tab[j];
             b1 = tab[j + 1].x;
         }
@@ -228,12 +223,12 @@ PK_DEV void fast_search2(const pk_tab2* taba, int na, double firsta, double last
         double b1a = taba[ja + 1].x, b1b = tabb[jb + 1].x;
         asm volatile("" : "+v"(b1a), "+v"(b1b));  // all four reads issued before the first compare (not sunk behind its short circuit)
         if (__builtin_expect(!((e2a.x < xa || ja == 0) && (xa <= b1a || ja == na - 2)), 0)) {
-            ja = cell_index_tab(taba, na, xa, ja);
+            ja = cell_index_tab(taba, na, xa);
             e2a = taba[ja];
             b1a = taba[ja + 1].x;
         }
         if (__builtin_expect(!((e2b.x < xb || jb == 0) && (xb <= b1b || jb == nb - 2)), 0)) {
-            jb = cell_index_tab(tabb, nb, xb, jb);
+            jb = cell_index_tab(tabb, nb, xb);
             e2b = tabb[jb];
             b1b = tabb[jb + 1].x;
         }
@@ -259,25 +254,9 @@ PK_DEV void fast_search2(const pk_tab2* taba, int na, double firsta, double last
 }
 
 // The two x-corners of one (level, z, y) row at byte offset `off` from a wave-uniform base: one wide load in saddr form.
-// PK_ABLATE_FIELDS (measurement builds only, results are wrong on purpose; tools/build_variant.sh): what an ideal LDS field tile
-//  could buy at most.  1 = every lane reads the SAME global address (the 16 loads become one cache line per wavefront: no L2
-// / Infinity-Cache latency spread, no TA divergence); 2 = the corner values come out of LDS (ds_read_b128 from the staged coordinate
-// tables: a tile that costs nothing to maintain).
-#ifndef PK_ABLATE_FIELDS
-#define PK_ABLATE_FIELDS 0
-#endif
 template <class FT>
 PK_DEV void ldrow(const char* base, uint32_t off, double& a, double& b) {
-#if PK_ABLATE_FIELDS == 1
-    ldpair(reinterpret_cast<const FT*>(base + (off & 8u)), a, b);
-#elif PK_ABLATE_FIELDS == 2
-    extern __shared__ __attribute__((aligned(16))) double pk_ablate_smem[];
-    const pk_tab2 v = reinterpret_cast<const pk_tab2*>(pk_ablate_smem)[(off >> 4) & 63u];
-    a = v.x * 1e-9 + (double)((uintptr_t)base & 1);
-    b = v.y * 1e-9;
-#else
     ldpair(reinterpret_cast<const FT*>(base + off), a, b);
-#endif
 }
 
 // XLinear.interp (_xinterpolators.py:112-153) for one field; LT / LZ: the second time / depth level takes part (wave-uniform,
@@ -330,15 +309,8 @@ PK_DEV double interp_rows(const Rows& r, double tau, double omt, double zeta, do
     return w00 * c00 + w01 * c01 + w10 * c10 + w11 * c11;
 }
 
-// U, V (and W) of one evaluation.  PK_FAST_BATCH: 8 = the corner rows of one field are requested back to back (one memory round
-// trip per field), 16 = those of U and V together (more registers), 4 = left to the scheduler.  The fences keep the machine
-// scheduler from sinking the loads back between the arithmetic.
-#ifndef PK_FAST_BATCH
-#define PK_FAST_BATCH 8
-#endif
-#ifndef PK_FAST_BLOCK_CACHE
-#define PK_FAST_BLOCK_CACHE 1  // FCtx::bei (0: A/B builds without the corner-block cache)
-#endif
+// U, V (and W) of one evaluation.  The corner rows of one field are requested back to back (one memory round trip per field; those of
+// U and V together took more registers); the fences keep the machine scheduler from sinking the loads back between the arithmetic.
 template <class FT, bool D3, bool LT, bool LZ>
 PK_DEV void uvw_fast(const FastA& F, int64_t o0, int64_t o1, uint32_t b00, double tau, double omt, double zeta, double omz, double w00,
                      double w01, double w10, double w11, double& uu, double& vv, double& ww, pk_tab2* blk) {
@@ -348,12 +320,7 @@ PK_DEV void uvw_fast(const FastA& F, int64_t o0, int64_t o1, uint32_t b00, doubl
     asm volatile("" : "+v"(bo));
     Rows ru, rv, rw;
     load_rows<FT, LT, LZ>(ru, F.U + o0, F.U + o1, bo, F.dyb, F.dzb);
-#if PK_FAST_BATCH == 16
-    load_rows<FT, LT, LZ>(rv, F.V + o0, F.V + o1, bo, F.dyb, F.dzb);
-#endif
-#if PK_FAST_BATCH >= 8
     PK_FIELD_FENCE();
-#endif
     // the t / z-lerped corner blocks of U and V go to the lane's block cache (FCtx::bei) as soon as they exist; blk: wave-uniform NULL or not
     double c00, c01, c10, c11;
     lerp_rows<LT, LZ>(ru, tau, omt, zeta, omz, c00, c01, c10, c11);
@@ -363,12 +330,8 @@ PK_DEV void uvw_fast(const FastA& F, int64_t o0, int64_t o1, uint32_t b00, doubl
         b.x = c10; b.y = c11; blk[FAST_WG] = b;
     }
     uu = w00 * c00 + w01 * c01 + w10 * c10 + w11 * c11;
-#if PK_FAST_BATCH != 16
     load_rows<FT, LT, LZ>(rv, F.V + o0, F.V + o1, bo, F.dyb, F.dzb);
-#if PK_FAST_BATCH >= 8
     PK_FIELD_FENCE();
-#endif
-#endif
     lerp_rows<LT, LZ>(rv, tau, omt, zeta, omz, c00, c01, c10, c11);
     if (!D3 && blk) {
         pk_tab2 b;
@@ -378,9 +341,7 @@ PK_DEV void uvw_fast(const FastA& F, int64_t o0, int64_t o1, uint32_t b00, doubl
     vv = w00 * c00 + w01 * c01 + w10 * c10 + w11 * c11;
     if (D3) {
         load_rows<FT, LT, LZ>(rw, F.W + o0, F.W + o1, bo, F.dyb, F.dzb);
-#if PK_FAST_BATCH >= 8
         PK_FIELD_FENCE();
-#endif
         ww = interp_rows<LT, LZ>(rw, tau, omt, zeta, omz, w00, w01, w10, w11);
     }
 }
@@ -411,9 +372,7 @@ template <class FT, bool LT, bool LZ>
 PK_DEV void lp_field(LpField& f, const char* l0, const char* l1, uint32_t bo, uint32_t dyb, uint32_t dzb, double zeta) {
     Rows r;
     load_rows<FT, LT, LZ>(r, l0, l1, bo, dyb, dzb);
-#if PK_FAST_BATCH >= 8
     PK_FIELD_FENCE();
-#endif
     double a00 = r.c00, a01 = r.c01, a10 = r.c10, a11 = r.c11;
     if (LZ) {
         a00 = fma(zeta, r.d00 - a00, a00); a01 = fma(zeta, r.d01 - a01, a01);
@@ -444,7 +403,7 @@ PK_DEV double lp_sum(const LpField& f, double tau, double eta, double xsi) {
     return fma(eta, fma(xsi, pxy, py), fma(xsi, px, p0));
 }
 
-// lp_sum on a block that stays in its registers (PK_FAST_BLOCK_REGS): the four fma(tau, D*, P*) as the three-address v_fma_f64.  The compiler
+// lp_sum on a block that stays in its registers (fast_held): the four fma(tau, D*, P*) as the three-address v_fma_f64.  The compiler
 // selects the two-address v_fmac_f64, which accumulates into P* -- dead behind the sum when the block came out of LDS, live here: it put a
 // v_mov_b64 in front of each of the eight.  The same fused operation on the same operands.
 PK_DEV double fma3(double a, double b, double c) {
@@ -462,7 +421,7 @@ PK_DEV int uniform_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
 // ---- cell record in registers (FAST_LP_CACHE only) ---------------------------------------------------------------------------------
 // A lane's cell changes in under 1 % of its evaluations (tests/test_gpu_level_pair_cache.py: the premise), yet every evaluation read the
 // two table entries per axis of that cell from LDS, compared, handled the edge cells and ravelled the index again -- one dependent LDS round
-// trip and ~27 VALU instructions in front of the block read.  PK_FAST_CELL_REGS keeps the entries in registers (FCtx::ya ..):
+// trip and ~27 VALU instructions in front of the block read.  The cache kernel keeps the entries in registers (FCtx::ya ..):
 //   * a lane with ya < y <= yb and xa < x <= xb is in the cell of its previous evaluation: indices, `ei` and the block test stay as they
 //     are and eta, xsi are the same (x - a) * RN(1 / width) on the same operands.  The strict test accepts a subset of what the table test
 //     accepts for that cell and the search is a pure function of the coordinate, so every other lane -- first evaluation, new cell,
@@ -473,19 +432,14 @@ PK_DEV int uniform_i32(int v) { return __builtin_amdgcn_readfirstlane(v); }
 //     the stage loop and the search is keyed on FAST_Z_UNSEARCHED.  z does move where the step loop adds a dz the particle brought into the
 //     launch (ParticleSet(..., dz=...), a dz an earlier kernel left): the position update re-arms the search there (fctx_depth_moved), one
 //     compare per step.  It drops the record as well -- a same-cell lane tests no index, and the new depth may lie outside the grid.
-// 0 = the table search in every evaluation (the code before the record; A/B builds).  FAST_LP_REGS, FAST_LP_OFF and modules with user
-// kernels are not affected.  (Measured step by step -- the record alone, then without ravel and tests on a same-cell lane, then with the early
-// block read: profiles/c2_cell_registers_ab.txt.)
-#ifndef PK_FAST_CELL_REGS
-#define PK_FAST_CELL_REGS 1
-#endif
-constexpr bool fast_cell_regs(int lp) { return PK_FAST_CELL_REGS != 0 && lp == FAST_LP_CACHE; }
+// FAST_LP_REGS, FAST_LP_OFF and modules with user kernels search the table in every evaluation.  (Measured step by step -- the record alone,
+// then without ravel and tests on a same-cell lane, then with an early block read: profiles/c2_cell_registers_ab.txt.)
 
-// ---- block and time cell in registers (FAST_LP_CACHE with the cell record, float64 particle storage) ------------------------------------------
+// ---- block and time cell in registers (FAST_LP_CACHE, float64 particle storage: fast_held) ------------------------------------------------------
 // With the cell record every evaluation still read the lane's 128-byte block from LDS -- the sixteen doubles the same lane had held in the
 // same registers one evaluation earlier: 0.79 of the wave-evaluations have no missing lane -- and every second one (stages 2 and 4 bring a
 // new t) searched the time table for the cell the wavefront has sat in since the launch began.
-// PK_FAST_BLOCK_REGS: Z0 / D of U and V (FCtx::fu, fv) are lane state that survives from one evaluation to the next and from one step to the
+// The block: Z0 / D of U and V (FCtx::fu, fv) are lane state that survives from one evaluation to the next and from one step to the
 // next; the LDS slot is their backing store.
 //   * Invariant: whenever ei == bei and the level pair is that of bkey, the registers hold what the slot holds.  A wave-evaluation without a
 //     missing lane touches LDS for nothing but a time-cell miss.
@@ -493,69 +447,50 @@ constexpr bool fast_cell_regs(int lp) { return PK_FAST_CELL_REGS != 0 && lp == F
 //     lanes load the block from their slot -- so the hit lanes' registers are dead across the miss branch, whose corner rows need them.
 //   * The early returns (time error, out-of-bounds code) leave registers and slot as they are.
 //   * The final sums use the three-address v_fma_f64 (lp_sum_held): the compiler's v_fmac_f64 accumulates into P*, which now stays live, and
-//     cost a v_mov_b64 in front of each of the eight -- with them this build was 2 % SLOWER than the early read it replaces.
+//     cost a v_mov_b64 in front of each of the eight -- with them this kernel was 2 % SLOWER than the early block read it replaced.
 //   * The 32 registers come out of the depth memo: of hz, zi, zez and mzeta one register stays, FCtx::zi = zi * 2 + lenZ.  The hit path needs
 //     neither index nor weight (a new depth drops the block: lenZ is no part of the hit test, FCtx::bkey holds the level pair only); the table
 //     path forms zi * ez for its ravel; the miss branch and the out-of-bounds rules read the depth cell's entry again and form zeta from the
 //     operands the search had (depth_zeta).  Without this the headline kernel spilled 4 VGPRs once per step (16 B of scratch).
-//   * Not in the instantiations for float32 particle storage, which start 6 VGPRs higher (as with the early block read): they keep their code.
-// PK_FAST_TIME_REC: the entries of the lane's time cell -- first node, second node, 1 / width (FCtx::ta, tb, tr), index FCtx::ht -- instead of the
+//   * Not in the instantiations for float32 particle storage, which start 6 VGPRs higher: they read the block from their slot in every
+//     evaluation and keep the time and depth memo.
+// The time record: the entries of the lane's time cell -- first node, second node, 1 / width (FCtx::ta, tb, tr), index FCtx::ht -- instead of the
 // memo (mt, mtau).  A lane with ta < t <= tb takes ti from the record and tau = (t - ta) * tr, the operands and the operation of fast_bary
 // inside fast_search: the same bits.  Every other lane -- first evaluation, new level pair, t exactly on a node, t == 0, NaN, a one-level
 // axis -- runs fast_search unchanged and renews the record from the entry the search holds; the range test stays in front.  One record per
 // lane: one per wavefront in scalar registers (renewed under a ballot from the first lane outside it) was built, measured and not kept.
-// 0 / 0 compiles to the code before (A/B builds).  Measured: profiles/c2_block_registers_ab.txt.
-#ifndef PK_FAST_BLOCK_REGS
-#define PK_FAST_BLOCK_REGS 1
-#endif
-constexpr bool fast_block_regs(int lp, bool pf) { return PK_FAST_BLOCK_REGS != 0 && fast_cell_regs(lp) && !pf; }
-#ifndef PK_FAST_TIME_REC
-#define PK_FAST_TIME_REC 1
-#endif
-constexpr bool fast_time_rec(int lp, bool pf) { return PK_FAST_TIME_REC != 0 && fast_block_regs(lp, pf); }
+// Measured: profiles/c2_block_registers_ab.txt.
+constexpr bool fast_held(int lp, bool pf) { return lp == FAST_LP_CACHE && !pf; }  // this kernel holds its block and time cell in registers
 
-// ---- the hit path's non-arithmetic VALU (the kernels with the block in registers only) -----------------------------------------------------------
+// ---- the hit path's non-arithmetic VALU (fast_held kernels only) -----------------------------------------------------------------------------
 // Counted on the path a wave-evaluation of the looped stages 2-4 takes when every lane stays in its cell and its time cell (0.79 of them):
-// 96 VALU, of which the reference's arithmetic needs about 68 (profiles/c2_hit_path_trim_ab.txt).  Each step that was kept has its macro; all at 0 compile
-// to the code before (A/B builds).  FAST_LP_REGS -- the bit-for-bit partner of the tests --, FAST_LP_OFF, the instantiations for float32
-// particle storage and modules with user kernels keep their code.
-// PK_FAST_WSUM: the stage weights of su = u1 + 2*u2 + 2*u3 + u4 as ONE fused operation, su = fma(wgt, u, su) with wgt = 2.0 or 1.0 in a
+// 96 VALU, of which the reference's arithmetic needs about 68 (profiles/c2_hit_path_trim_ab.txt).  FAST_LP_REGS -- the bit-for-bit partner
+// of the tests --, FAST_LP_OFF, the instantiations for float32 particle storage and modules with user kernels are not touched by the two
+// steps that were kept.
+// Stage weights: the stage weights of su = u1 + 2*u2 + 2*u3 + u4 as ONE fused operation, su = fma(wgt, u, su) with wgt = 2.0 or 1.0 in a
 // scalar register pair (fma3s: the three-address v_fma_f64; the translation unit is built with -ffp-contract=off, so the compiler forms
 // none itself).  The stage loop is not unrolled: for `su + 2*u` / `su + u` it formed u + u, chose between u and 2u with two v_cndmask_b32
 // and added -- 8 VALU for U and V where 2 suffice.  The same bits: 2*u is exact for every finite |u| < 2^1023, subnormals included, so
 // both forms round the same exact sum once (tests/test_wsum_fma.py).  The ONE exception: |u| >= 2^1023, where 2*u overflows to infinity
 // before the addition and the fused form may stay finite (a velocity of 1e308 m/s).
-// PK_FAST_CONV_STEP: deg2m and 1 / deg2m of the unit conversion become opaque scalars at the top of every STEP (FastTabs::deg2m, inv_deg2m;
+// Unit factors: deg2m and 1 / deg2m of the unit conversion become opaque scalars at the top of every STEP (FastTabs::deg2m, inv_deg2m;
 // pk_kernels.h).  As kernel arguments they lived across the whole kernel, were spilled to VGPR lanes and came back through six v_readlane_b32
 // in front of every conversion; a pair that lives for one step the allocator keeps in scalar registers: 6 VALU less per evaluation, 58 -> 48
 // v_readlane_b32 inside the stage loop, one scalar load per step.
 // Built and not kept: u = v = 0 filled only on the paths that return early (time error, out-of-bounds code) -- the allocator answered with
 // 48 B of scratch per lane in both float64-storage instantiations, alone and beside the other steps; the stage position reading the
 // registers the evaluation leaves u and v in (no lu, lv) -- the two copies stayed, for as long as the zero fill stands in front of them.
-#ifndef PK_FAST_WSUM
-#define PK_FAST_WSUM 1
-#endif
-#ifndef PK_FAST_CONV_STEP
-#define PK_FAST_CONV_STEP 1
-#endif
-#ifdef PK_USER_KERNELS
-constexpr bool fast_wsum(int, bool) { return false; }
-constexpr bool fast_conv_step(int, bool) { return false; }
-#else
-constexpr bool fast_wsum(int lp, bool pf) { return PK_FAST_WSUM != 0 && fast_block_regs(lp, pf); }
-constexpr bool fast_conv_step(int lp, bool pf) { return PK_FAST_CONV_STEP != 0 && fast_block_regs(lp, pf); }
-#endif
 PK_DEV double fma3s(double wgt, double b, double c) {  // fma(wgt, b, c), wgt wave-uniform: read from its scalar register pair
     double r;
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "s"(wgt), "v"(b), "v"(c));
     return r;
 }
 
-// ---- the miss branch, transposed (the kernels with the block in registers only) ------------------------------------------------------------------
+// ---- the miss branch, transposed (fast_held kernels only) ----------------------------------------------------------------------------------------
 // 0.21 of the headline launch's wave-evaluations hold a missing lane, ~1.3 of them each, and the waterfall above runs lp_fetch for them at wave
 // width: 16 wide loads in two dependent batches, ~56 fp64 operations and 64-bit scalar row bases for one or two working lanes.  The 16 corner
 // rows of ONE missing lane are 16 independent loads, and lp_field applies the same three operations to pairs of them: work for 16 lanes.
-// PK_FAST_MISS_XPOSE: when the wavefront is complete (all 64 lanes active), no ring is in use and at most `miss_lanes` lanes miss
+// The transposed fetch: when the wavefront is complete (all 64 lanes active), no ring is in use and at most `miss_lanes` lanes miss
 // (pk_set_option; FastTabs::fl carries it), each row of 16 lanes serves one missing lane m per pass -- row g the g-th set bit of the miss mask:
 //   * m's b00, zeta and key (ti, lenT, lenZ) reach the row through ds_bpermute_b32 (the crossbar: no LDS memory);
 //   * helper j = k | r << 1 | l << 2 | f << 3 (depth row, lat row, time level, U / V) forms its own 64-bit address and issues ONE ldpair, masked
@@ -565,16 +500,8 @@ PK_DEV double fma3s(double wgt, double b, double c) {  // fma(wgt, b, c), wgt wa
 //     lane j^1, the level difference with lane j^4, the polynomial basis with lane j^2 (tests/test_lp_transposed_model.py pins map and order);
 //   * the k = 0 lane (f, l, r) holds entry 4f + 2l + r of m's slot and writes it: one ds_write_b128 per pass.
 // Every other wave-evaluation with a missing lane -- a chunk's first one (64 missing lanes), a wavefront with deleted or finished lanes, a ring
-// launch -- takes the waterfall: the same bits, so the threshold is a speed knob only.  0 compiles to the code before (A/B builds).
-#ifndef PK_FAST_MISS_XPOSE
-#define PK_FAST_MISS_XPOSE 1
-#endif
-#ifdef PK_USER_KERNELS
-constexpr bool fast_miss_xpose(int, bool) { return false; }
-#else
-constexpr bool fast_miss_xpose(int lp, bool pf) { return PK_FAST_MISS_XPOSE != 0 && fast_block_regs(lp, pf); }
-#endif
-// Built and not kept (PK_FAST_MISS_KEEP): the hit lanes' block (FCtx::fu, fv) live across the transposed fetch, only the lanes that were served reading
+// launch -- takes the waterfall: the same bits, so the threshold is a speed knob only.
+// Built and not kept: the hit lanes' block (FCtx::fu, fv) live across the transposed fetch, only the lanes that were served reading
 // their slot back.  The 32 registers do not fit beside the lane state and the helpers' values: 128 VGPRs and 160 B (float fields: 128 B) of scratch
 // per lane in the two instantiations, where the rule is none (profiles/c2_miss_transposed_ab.txt).
 constexpr int FAST_MISS_LANES_DEFAULT = 4;      // pk_set_option "miss_lanes" -1: one pass (profiles/c2_miss_transposed_ab.txt)
@@ -667,10 +594,11 @@ PK_DEV void lp_fetch_xposed(const FastA& F, const FastTabs& T, uint64_t mm, int 
     } while (mm);
 }
 
-// The status rules of eval_uvw_fast for an evaluation some index of which carries an out-of-bounds code (field.py:307-378; the record's cold path)
+// The status rules of the evaluators for an evaluation some index of which carries an out-of-bounds code (-1 right, -2 left; field.py:307-356)
 PK_DEV int fast_oob_state(int s, int xi, int yi, int zi, double xsi, double eta, double zeta, double tau) {
     if ((xi == RIGHT_OUT_OF_BOUNDS || yi == RIGHT_OUT_OF_BOUNDS || zi == RIGHT_OUT_OF_BOUNDS) && s < PK_ERROROUTOFBOUNDS) s = PK_ERROROUTOFBOUNDS;
     if (zi == LEFT_OUT_OF_BOUNDS && s < PK_ERRORTHROUGHSURFACE) s = PK_ERRORTHROUGHSURFACE;
+    // field.py:359-378: a non-finite barycentric coordinate makes the (wrapped-around) gather NaN, then everything is zeroed
     const bool bad = !(isfinite(xsi) && isfinite(eta) && isfinite(zeta) && isfinite(tau));
     if (bad && s < PK_ERRORINTERPOLATION) s = PK_ERRORINTERPOLATION;
     return s;
@@ -681,44 +609,46 @@ PK_DEV int fast_oob_state(int s, int xi, int yi, int zi, double xsi, double eta,
 // searched: the search is a pure function of the coordinate, and the Runge-Kutta stages revisit t (stages 2 and 3 share
 // t + dt/2; stage 4 of one step and stage 1 of the next share t + dt) and, in the 2-D kernels, never move z.
 struct FCtx {
+    // both evaluators (and eval_scalar_fast): status, ravelled index, search hints, the time / depth memo and the cell of the lane's block
     int state;
     int32_t ei;
     int ht, hz, hy, hx;
     int zi;                      // memo: index (or out-of-bounds code) of the last depth searched
     uint32_t zez;                // ... and its term zi * ez of the ravelled index (wrapped 32-bit product)
     double mt, mtau, mz, mzeta;  // memo keys (bitwise-equal coordinate => same answer) and barycentric values
-    // Corner-block cache (2-D kernels): the t / z-lerped corner values c00..c11 of U and V -- 8 doubles in the lane's LDS slot FastTabs::blk
-    // -- are a function of the cell and of (t, z) only.  Stages 2 and 3 of a Runge-Kutta step share t, stage 4 and stage 1 of the next
-    // step too, their sample points lie a fraction of a cell apart and z does not move: when EVERY lane of the wavefront samples the
+    // Corner-block cache of eval_uvw_fast (2-D kernels): the t / z-lerped corner values c00..c11 of U and V -- 8 doubles in the lane's LDS slot
+    // FastTabs::blk -- are a function of the cell and of (t, z) only.  Stages 2 and 3 of a Runge-Kutta step share t, stage 4 and stage 1 of the
+    // next step too, their sample points lie a fraction of a cell apart and z does not move: when EVERY lane of the wavefront samples the
     // cell (`bei`, its ravelled index) at the (mt, mz) its cached block was formed at, the 16 corner loads and the level lerps are skipped
     // and the bilinear sum runs on the same values -- the same operations, so the same bits (measured: 0.998 / 1.000 of the wave-evaluations
     // of those two stage pairs on BASELINE config 2).  Invariant: bei >= 0 => the slot holds the block of cell bei at (mt, mz).
+    // Level-pair cache of eval_uvw_lp (FAST_LP_CACHE): the slot holds Z0 / D of cell `bei` at depth mz for the key `bkey`.
     int32_t bei;
-    // Level-pair cache (FAST_LP_CACHE): the slot holds Z0 / D of cell `bei` at depth mz for the wave-uniform key `bkey` of eval_uvw_fast
-    // (ti << 2 | lenT << 1 | lenZ); a new depth drops the block, a new time alone does not.
+    // eval_uvw_lp only: the key of the block (ti << 2 | lenT << 1 | lenZ; a new depth drops the block, a new time alone does not), the cell
+    // record, and for fast_held the block and the time record
     int32_t bkey;
-    // Cell record (PK_FAST_CELL_REGS, FAST_LP_CACHE): the table entries of the lane's cell (hy, hx) -- first node, second node, 1 / width of lat and
-    // of lon -- held in registers for as long as the lane stays inside it.  ya = +inf: no record (the test of eval_uvw_fast fails).
+    // Cell record (FAST_LP_CACHE): the table entries of the lane's cell (hy, hx) -- first node, second node, 1 / width of lat and
+    // of lon -- held in registers for as long as the lane stays inside it.  ya = +inf: no record (the test of eval_uvw_lp fails).
     double ya, yb, yr, xa, xb, xr;
-    // PK_FAST_BLOCK_REGS: the block itself -- what the slot holds whenever ei == bei and bkey names the level pair.  FCtx::zi is zi * 2 + lenZ then.
+    // fast_held: the block itself -- what the slot holds whenever ei == bei and bkey names the level pair.  FCtx::zi is zi * 2 + lenZ then.
     LpField fu, fv;
-    // PK_FAST_TIME_REC: the entries of the lane's time cell `ht` -- first node, second node, 1 / width.  ta = +inf: no record.
+    // fast_held: the entries of the lane's time cell `ht` -- first node, second node, 1 / width.  ta = +inf: no record.
     double ta, tb, tr;
 };
 constexpr int32_t FAST_NO_BLOCK = -0x7fffffff - 1;
-constexpr int FAST_Z_UNSEARCHED = -3;  // FCtx::zi before the launch's one depth search (PK_FAST_CELL_REGS; no index, no out-of-bounds code)
-// PK_FAST_CELL_REGS: the step loop moved z by a non-zero dz -- search depth again in the next evaluation (which drops the block of the old
+constexpr int FAST_Z_UNSEARCHED = -3;  // FCtx::zi before the launch's one depth search (FAST_LP_CACHE; no index, no out-of-bounds code)
+constexpr int FAST_Z_UNSEARCHED_PACKED = -0x7fffffff - 1;  // the same for the packed depth cell of fast_held (zi * 2 + lenZ)
+// FAST_LP_CACHE: the step loop moved z by a non-zero dz -- search depth again in the next evaluation (which drops the block of the old
 // depth and forms `zez`, `ei` anew), on the table path
-constexpr int FAST_Z_UNSEARCHED_PACKED = -0x7fffffff - 1;  // the same for the packed depth cell of PK_FAST_BLOCK_REGS (zi * 2 + lenZ)
-PK_DEV void fctx_depth_moved(FCtx& c, bool packed = false) {
-    c.zi = packed ? FAST_Z_UNSEARCHED_PACKED : FAST_Z_UNSEARCHED;
+PK_DEV void fctx_depth_moved(FCtx& c, bool held) {
+    c.zi = held ? FAST_Z_UNSEARCHED_PACKED : FAST_Z_UNSEARCHED;
     c.ya = __builtin_inf();
 }
-PK_DEV void fctx_init(FCtx& c, int state, int32_t ei, bool cell_regs = false, bool packed = false) {
+PK_DEV void fctx_init(FCtx& c, int state, int32_t ei, bool cache, bool held) {  // cache: LP == FAST_LP_CACHE; held: fast_held(LP, PF)
     c.state = state;
     c.ei = ei;
     c.ht = c.hz = c.hy = c.hx = 0;
-    c.zi = packed ? FAST_Z_UNSEARCHED_PACKED : cell_regs ? FAST_Z_UNSEARCHED : 0;
+    c.zi = held ? FAST_Z_UNSEARCHED_PACKED : cache ? FAST_Z_UNSEARCHED : 0;
     c.ya = c.xa = c.ta = __builtin_inf();
     c.yb = c.xb = c.yr = c.xr = c.tb = c.tr = 0.0;
     c.zez = 0u;
@@ -729,39 +659,175 @@ PK_DEV void fctx_init(FCtx& c, int state, int32_t ei, bool cell_regs = false, bo
     c.fu.p0 = c.fu.p1 = c.fu.d0 = c.fu.d1 = c.fv.p0 = c.fv.p1 = c.fv.d0 = c.fv.d1 = pk_tab2{0.0, 0.0};
 }
 
-// VectorField.eval (field.py:250-304) + XLinear_Velocity.interp (_xinterpolators.py:169-190).  PF: the sample point may come
-// straight from float32 particle storage (pos_f32); D3: sample W as well.  bmode (wave-uniform; FCtx::bei): bit 0 = this sample may
+// ---- what the two evaluators share ------------------------------------------------------------------------------------------------------
+// (The two helpers that end an evaluation answer through ONE flag at ONE return: written with an early `return false` they compiled every
+// kernel that calls them to other code, the cache kernels to 230 instructions more -- tools/kernel_code_diff.py against the inlined form.)
+// _search_time_index (index_search.py:65-91), the range test.  -> true: t lies outside the field's time interval (the status is set).
+// (it, klo): the key of this sample (pk_device.h: twe_note -- a launch with LISTED samples runs the general program, pk_api.hip)
+PK_DEV bool fast_time_outside(const KArgs& a, const FastTabs& T, FCtx& c, double t, unsigned it, int klo) {
+    const bool out = !(0 <= t) || !(t <= T.tlen);
+    if (__builtin_expect(out, 0)) {
+        c.state = PK_ERROROUTSIDETIMEINTERVAL;
+        twe_note(a, it, klo);
+    }
+    return out;
+}
+// ... and the time memo: FCtx::ht, mtau answer for t.  drop: a new t drops the lane's block (the stage-pair block is one of (t, z))
+PK_DEV void fast_time_memo(const FastTabs& T, const FastA& F, FCtx& c, uint32_t fl, double t, bool drop) {
+    if (t != c.mt) {
+        int idx;
+        fast_search<true>(T.time, F.nt, F.t0, F.t1, t, c.ht, idx, c.mtau, (fl & FA_NT2) != 0);  // level times start at 0 (host check): idx == c.ht
+        c.mt = t;
+        if (drop) c.bei = FAST_NO_BLOCK;
+    }
+}
+// The depth memo's search: FCtx::zi, zez, mzeta answer for z; a block formed at another depth is dropped.  The caller knows when z is new:
+// by the key FCtx::mz (keyed), or because the step loop said so (FAST_Z_UNSEARCHED)
+PK_DEV void fast_depth_search(const FastTabs& T, const FastA& F, FCtx& c, uint32_t fl, double z, bool keyed) {
+    fast_search<true>(T.depth, F.gnz, F.z0, F.z1, z, c.hz, c.zi, c.mzeta, (fl & FA_NZ2) != 0);
+    c.zez = (uint32_t)c.zi * F.ez;
+    if (keyed) c.mz = z;
+    c.bei = FAST_NO_BLOCK;
+}
+// lat and lon in their tables, the ravelled index FCtx::ei and the status rules.  -> true: some index carries an out-of-bounds code
+constexpr uint32_t FA_YX2 = FA_Y | FA_X | FA_NY2 | FA_NX2;
+PK_DEV bool fast_search_yx(const FastTabs& T, const FastA& F, FCtx& c, uint32_t fl, double y, double x, int zi, double zeta, double tau, int& yi,
+                           int& xi, double& eta, double& xsi) {
+    if ((fl & FA_YX2) == FA_YX2) {
+        fast_search2(T.lat, T.gny, F.y0, F.y1, y, c.hy, yi, eta, T.lon, T.gnx, F.x0, F.x1, x, c.hx, xi, xsi);
+    } else {
+        if (fl & FA_Y) fast_search<true>(T.lat, T.gny, F.y0, F.y1, y, c.hy, yi, eta, (fl & FA_NY2) != 0);
+        if (fl & FA_X) fast_search<true>(T.lon, T.gnx, F.x0, F.x1, x, c.hx, xi, xsi, (fl & FA_NX2) != 0);
+    }
+    // ravel_index (basegrid.py:83-152): the low 32 bits of the int64 sum are the wrapped 32-bit sum.  Of its three 32-bit products (v_mul_lo_u32
+    // each) one is left, and that one at full rate: ex == 1 (the fast path needs an x axis: pk_api.hip fill_fast, ravel_strides), zi * ez changes
+    // only with the depth memo (FCtx::zez), and for an in-bounds yi both yi and ey are below the 3840 nodes a 60 KB coordinate table holds, far
+    // inside the 24 bits of v_mad_u32_u24.  An out-of-bounds code (negative) takes the wrapped 32-bit product.
+    c.ei = (int32_t)((uint32_t)xi + __umul24((uint32_t)yi, F.ey) + c.zez);
+    const bool out = (xi | yi | zi) < 0;
+    if (__builtin_expect(out, 0)) {
+        c.ei = (int32_t)((uint32_t)xi + (uint32_t)yi * F.ey + c.zez);
+        c.state = fast_oob_state(c.state, xi, yi, zi, xsi, eta, zeta, tau);
+    }
+    return out;
+}
+// The unit conversion of a spherical mesh (_xinterpolators.py:183-187).  STEP: deg2m and 1 / deg2m are the step's scalars (FastTabs::deg2m)
+template <bool PF, bool STEP>
+PK_DEV void fast_convert(const FastTabs& T, const FastA& F, double y, bool pos_f32, double& uu, double& vv) {
+    double conv;
+    if (PF && pos_f32) conv = (double)((float)F.deg2m * cosf((float)y * DEG2RADF));
+    else if constexpr (STEP) conv = T.deg2m * cos_lat_lean(y);
+    else if constexpr (PK_FAST_LEAN != 0) conv = F.deg2m * cos_lat_lean(y);
+    else conv = F.deg2m * cos_lat(y * DEG2RAD);
+    if constexpr (PK_FAST_LEAN != 0) {  // u / conv, v / deg2m within 1.5 ulp: 7 operations instead of 22
+        uu = uu * rcp_lean(conv);
+        vv = vv * (STEP ? T.inv_deg2m : F.inv_deg2m);
+    } else {
+        uu /= conv;
+        vv = div_by_recip(vv, F.deg2m, F.inv_deg2m);
+    }
+}
+// field.py:373-378 (one unordered compare answers "uu or vv is NaN"; ww: 0 in a 2-D kernel)
+PK_DEV void fast_nan_state(FCtx& c, double uu, double vv, double ww) {
+    if (__builtin_expect(__builtin_isunordered(uu, vv) || ww != ww, 0)) {
+        if (c.state < PK_ERRORINTERPOLATION) c.state = PK_ERRORINTERPOLATION;
+    }
+}
+
+// VectorField.eval (field.py:250-304) + XLinear_Velocity.interp (_xinterpolators.py:169-190), the stage-pair evaluator: lerps in the
+// reference's order, with the stage-pair block of FCtx::bei or nothing (FAST_LP_OFF; every user-kernel module).  PF: the sample point may
+// come straight from float32 particle storage (pos_f32); D3: sample W as well.  bmode (wave-uniform; FCtx::bei): bit 0 = this sample may
 // share (t, z) with the previous one -- test the cached corner block; bit 1 = the next one may share them with this one -- keep the block.
-// LP (2-D, PK_FAST_LEAN builds): FAST_LP_* -- the level-pair arithmetic, from registers or from the lane's LDS slot; bmode is not used then.
-template <class FT, bool PF, bool D3, int LP = FAST_LP_OFF>
+template <class FT, bool PF, bool D3>
 PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, double z, double y, double x, bool pos_f32, double& u,
                           double& v, double& w, unsigned it, int klo, int bmode = 0) {
     const FastA& F = a.fast;
     uint32_t fl = T.fl;
     asm volatile("" : "+s"(fl));  // opaque: every FA_* test below is a scalar bit test HERE, not a loop-invariant lane mask (FastTabs::fl)
     u = v = w = 0.0;
-    // With the cell record and without PK_FAST_BLOCK_REGS the lane's block is requested HERE, in front of the time search and the cell test, which run under its latency (the slot
-    // address is a lane constant).  A lane whose block turns out stale throws the values away: the miss branch re-reads behind its write.  Before
-    // the slot's first fill the values are whatever LDS holds -- nothing but the final sums is formed from them, and a lane without a block misses.
-    // (Not in the instantiations for float32 particle storage: they start 6 VGPRs higher, and with the 16 of the early block
-    // advect_fast_kernel<double, 1, false, FAST_LP_CACHE> spilled 4 VGPRs inside the stage loop.)
-    constexpr bool BR = fast_block_regs(LP, PF);
-    constexpr bool SPEC = fast_cell_regs(LP) && !PF && !BR;
-    LpField fu, fv;
-    if constexpr (SPEC) {
-        fu.p0 = T.blk[0]; fu.p1 = T.blk[FAST_WG_LP]; fu.d0 = T.blk[2 * FAST_WG_LP]; fu.d1 = T.blk[3 * FAST_WG_LP];
-        fv.p0 = T.blk[4 * FAST_WG_LP]; fv.p1 = T.blk[5 * FAST_WG_LP]; fv.d0 = T.blk[6 * FAST_WG_LP]; fv.d1 = T.blk[7 * FAST_WG_LP];
-    }
     int ti = 0;
     double tau = 0.0;
-    if (fl & FA_TI) {  // _search_time_index (index_search.py:65-91); (it, klo): the key of this sample (pk_device.h: twe_note -- a launch with LISTED
-                     // samples runs the general program, pk_api.hip)
-        if (__builtin_expect(!(0 <= t) || !(t <= T.tlen), 0)) {
-            c.state = PK_ERROROUTSIDETIMEINTERVAL;
-            twe_note(a, it, klo);
-            return;
+    if (fl & FA_TI) {
+        if (fast_time_outside(a, T, c, t, it, klo)) return;
+        fast_time_memo(T, F, c, fl, t, true);
+        ti = c.ht;
+        tau = c.mtau;
+    }
+    int zi = 0, yi = 0, xi = 0;
+    double zeta = 0.0, eta = 0.0, xsi = 0.0;
+    if (fl & FA_Z) {
+        if (!(z == c.mz)) {
+            fast_depth_search(T, F, c, fl, z, true);
         }
-        if constexpr (fast_time_rec(LP, PF)) {
+        zi = c.zi;
+        zeta = c.mzeta;
+    }
+    if (fast_search_yx(T, F, c, fl, y, x, zi, zeta, tau, yi, xi, eta, xsi)) return;
+    const bool lenT = tau > 0, lenZ = !(zeta <= 0);
+    const int key = (ti << 2) | (lenT ? 2 : 0) | (lenZ ? 1 : 0);
+    const uint32_t b00 = ((uint32_t)zi * F.st_z + (uint32_t)yi * F.st_y + (uint32_t)xi) * (uint32_t)sizeof(FT);
+    const double omt = 1 - tau, omz = 1 - zeta, omx = 1 - xsi, ome = 1 - eta;
+    const double w00 = omx * ome, w01 = xsi * ome, w10 = omx * eta, w11 = xsi * eta;
+    double uu = 0.0, vv = 0.0, ww = 0.0;
+    const bool bc = !D3 && (fl & FA_BLK) != 0;
+    // (in-bounds indices ravel to a non-negative `ei` that names the cell; the memo updates above already dropped a block of another (t, z))
+    bool reuse = false;
+    if (bc && (bmode & 1)) reuse = __builtin_amdgcn_ballot_w64(c.ei != c.bei) == 0;  // every active lane: same cell, same (t, z)
+    if (reuse) {
+        const pk_tab2 b0 = T.blk[0], b1 = T.blk[FAST_WG], b2 = T.blk[2 * FAST_WG], b3 = T.blk[3 * FAST_WG];
+        uu = w00 * b0.x + w01 * b0.y + w10 * b1.x + w11 * b1.y;
+        vv = w00 * b2.x + w01 * b2.y + w10 * b3.x + w11 * b3.y;
+    } else {
+        const bool keep = bc && (bmode & 2);
+        pk_tab2* const blk = keep ? T.blk : nullptr;
+        for (bool done = false; !done;) {
+            // everything derived from the wave-uniform key is formed BEFORE the lane test: inside `if (key == uk)` the optimiser
+            // may substitute the (divergent) key for uk, which would move the level arithmetic back into vector registers
+            const int uk = uniform_i32(key);
+            const int uti = uk >> 2;
+            int s0 = uti, s1 = uti + 1;  // has_ti: 0 <= ti <= nt-2; otherwise ti == 0 and the second level is never read
+            if (fl & FA_RING) {          // ring of time levels: level L lives in slot L % nslots
+                s0 = (int)((uint32_t)s0 % (uint32_t)F.nslots);
+                s1 = (int)((uint32_t)s1 % (uint32_t)F.nslots);
+            }
+            int64_t o0 = (int64_t)s0 * F.lvl_b, o1 = (int64_t)s1 * F.lvl_b;
+            int lens = uk & 3;
+            asm volatile("" : "+s"(o0), "+s"(o1), "+s"(lens));  // opaque scalars: no path back to the divergent key
+            if (key == uk) {
+                if (lens == 3) uvw_fast<FT, D3, true, true>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
+                else if (lens == 2) uvw_fast<FT, D3, true, false>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
+                else if (lens == 1) uvw_fast<FT, D3, false, true>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
+                else uvw_fast<FT, D3, false, false>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
+                done = true;
+            }
+        }
+        if (keep) c.bei = c.ei;
+    }
+    if (fl & FA_SPH) fast_convert<PF, false>(T, F, y, pos_f32, uu, vv);
+    fast_nan_state(c, uu, vv, ww);
+    u = uu;
+    v = vv;
+    w = ww;
+}
+
+// The same for the 2-D kernel in the level-pair arithmetic (PK_FAST_LEAN builds), the level-pair evaluator.  LP: FAST_LP_REGS -- the block is
+// formed in registers in every evaluation -- or FAST_LP_CACHE -- it lives in the lane's LDS slot and, for float64 particle storage (fast_held),
+// in the lane's registers.
+template <class FT, bool PF, int LP>
+PK_DEV void eval_uvw_lp(const KArgs& a, const FastTabs& T, FCtx& c, double t, double z, double y, double x, bool pos_f32, double& u, double& v,
+                        unsigned it, int klo) {
+    static_assert(LP == FAST_LP_REGS || LP == FAST_LP_CACHE, "a level-pair mode (2-D: z must not move inside a step)");
+    const FastA& F = a.fast;
+    uint32_t fl = T.fl;
+    asm volatile("" : "+s"(fl));  // (opaque: see eval_uvw_fast)
+    u = v = 0.0;
+    constexpr bool CACHE = LP == FAST_LP_CACHE, HELD = fast_held(LP, PF);
+    LpField fu, fv;
+    int ti = 0;
+    double tau = 0.0;
+    if (fl & FA_TI) {
+        if (fast_time_outside(a, T, c, t, it, klo)) return;
+        if constexpr (HELD) {
             if (__builtin_expect((c.ta < t) & (t <= c.tb), 1)) {
                 tau = fast_bary(t, c.ta, c.tb, c.tr);
             } else {
@@ -773,22 +839,15 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
                 c.ta = __builtin_inf();
                 if (two && idx >= 0) { c.ta = e.x; c.tb = a1; c.tr = e.y; }
             }
-            ti = c.ht;
         } else {
-            if (t != c.mt) {
-                int idx;
-                fast_search<true>(T.time, F.nt, F.t0, F.t1, t, c.ht, idx, c.mtau, (fl & FA_NT2) != 0);  // level times start at 0 (host check): idx == c.ht
-                c.mt = t;
-                if (LP == FAST_LP_OFF) c.bei = FAST_NO_BLOCK;  // (the level-pair block does not depend on t: its key holds ti and lenT)
-            }
-            ti = c.ht;
+            fast_time_memo(T, F, c, fl, t, false);  // (the level-pair block does not depend on t: its key holds ti and lenT)
             tau = c.mtau;
         }
+        ti = c.ht;
     }
     int zi = 0, yi = 0, xi = 0;
     double zeta = 0.0, eta = 0.0, xsi = 0.0;
-    constexpr bool CR = fast_cell_regs(LP);
-    // PK_FAST_BLOCK_REGS: zeta of the packed depth cell FCtx::zi, from the operands the search had (the miss branch and the out-of-bounds rules)
+    // fast_held: zeta of the packed depth cell FCtx::zi, from the operands the search had (the miss branch and the out-of-bounds rules)
     auto depth_zeta = [&]() -> double {
         if ((fl & (FA_Z | FA_NZ2)) != (FA_Z | FA_NZ2)) return 0.0;
         const int q = c.zi >> 1;  // the cell an out-of-bounds code was found in: the first one (left) or the last one (right), fast_search
@@ -797,7 +856,7 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
         return fast_bary(z, e.x, T.depth[h + 1].x, e.y);
     };
     if (fl & FA_Z) {
-        if constexpr (BR) {
+        if constexpr (HELD) {
             if (c.zi == FAST_Z_UNSEARCHED_PACKED) {
                 int hz = 0, idx;
                 double bz;
@@ -807,22 +866,15 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
             }
             zi = c.zi >> 1;
         } else {
-            if (CR ? c.zi == FAST_Z_UNSEARCHED : !(z == c.mz)) {
-                fast_search<true>(T.depth, F.gnz, F.z0, F.z1, z, c.hz, c.zi, c.mzeta, (fl & FA_NZ2) != 0);
-                c.zez = (uint32_t)c.zi * F.ez;
-                if (!CR) c.mz = z;
-                c.bei = FAST_NO_BLOCK;
+            if (CACHE ? c.zi == FAST_Z_UNSEARCHED : !(z == c.mz)) {
+                fast_depth_search(T, F, c, fl, z, !CACHE);
             }
             zi = c.zi;
             zeta = c.mzeta;
         }
     }
-#ifndef PK_FAST_SEARCH2
-#define PK_FAST_SEARCH2 1
-#endif
-    constexpr uint32_t YX2 = FA_Y | FA_X | FA_NY2 | FA_NX2;
-    if constexpr (CR) {
-        const bool yx2 = (fl & YX2) == YX2;
+    if constexpr (CACHE) {  // the cell record
+        const bool yx2 = (fl & FA_YX2) == FA_YX2;
         // (bitwise: four compares and three s_and, no short-circuit exec-mask blocks; a NaN fails)
         const bool same = yx2 & (c.ya < y) & (y <= c.yb) & (c.xa < x) & (x <= c.xb);
         if (__builtin_expect(same, 1)) {
@@ -837,9 +889,9 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
                 if (fl & FA_X) fast_search<true>(T.lon, T.gnx, F.x0, F.x1, x, c.hx, xi, xsi, (fl & FA_NX2) != 0);
             }
             // (cold: the wrapped 32-bit product serves indices and codes alike)
-            c.ei = (int32_t)((uint32_t)xi + (uint32_t)yi * F.ey + (BR ? (uint32_t)zi * F.ez : c.zez));
+            c.ei = (int32_t)((uint32_t)xi + (uint32_t)yi * F.ey + (HELD ? (uint32_t)zi * F.ez : c.zez));
             if (__builtin_expect((xi | yi | zi) < 0, 0)) {
-                if (BR) zeta = depth_zeta();
+                if (HELD) zeta = depth_zeta();
                 c.state = fast_oob_state(c.state, xi, yi, zi, xsi, eta, zeta, tau);
                 c.ya = __builtin_inf();
                 return;
@@ -849,163 +901,86 @@ PK_DEV void eval_uvw_fast(const KArgs& a, const FastTabs& T, FCtx& c, double t, 
                 c.xa = e.eb.x; c.xb = e.a1b; c.xr = e.eb.y;
             }
         }
+        // (a same-cell lane formed no indices: past the out-of-bounds return they are the hints)
+        yi = c.hy;
+        xi = c.hx;
     } else {
-        if (PK_FAST_SEARCH2 && (fl & YX2) == YX2) {
-            fast_search2(T.lat, T.gny, F.y0, F.y1, y, c.hy, yi, eta, T.lon, T.gnx, F.x0, F.x1, x, c.hx, xi, xsi);
-        } else {
-            if (fl & FA_Y) fast_search<true>(T.lat, T.gny, F.y0, F.y1, y, c.hy, yi, eta, (fl & FA_NY2) != 0);
-            if (fl & FA_X) fast_search<true>(T.lon, T.gnx, F.x0, F.x1, x, c.hx, xi, xsi, (fl & FA_NX2) != 0);
-        }
-        // ravel_index (basegrid.py:83-152): the low 32 bits of the int64 sum are the wrapped 32-bit sum.  Of its three 32-bit products (v_mul_lo_u32
-        // each) one is left, and that one at full rate: ex == 1 (the fast path needs an x axis: pk_api.hip fill_fast, ravel_strides), zi * ez changes
-        // only with the depth memo (FCtx::zez), and for an in-bounds yi both yi and ey are below the 3840 nodes a 60 KB coordinate table holds, far
-        // inside the 24 bits of v_mad_u32_u24.  An out-of-bounds code (negative) takes the wrapped 32-bit product.
-        c.ei = (int32_t)((uint32_t)xi + __umul24((uint32_t)yi, F.ey) + c.zez);
-        if (__builtin_expect((xi | yi | zi) < 0, 0)) {  // some index carries an out-of-bounds code (-1 right, -2 left)
-            c.ei = (int32_t)((uint32_t)xi + (uint32_t)yi * F.ey + c.zez);
-            int s = c.state;  // field.py:307-356
-            if ((xi == RIGHT_OUT_OF_BOUNDS || yi == RIGHT_OUT_OF_BOUNDS || zi == RIGHT_OUT_OF_BOUNDS) && s < PK_ERROROUTOFBOUNDS) s = PK_ERROROUTOFBOUNDS;
-            if (zi == LEFT_OUT_OF_BOUNDS && s < PK_ERRORTHROUGHSURFACE) s = PK_ERRORTHROUGHSURFACE;
-            // field.py:359-378: a non-finite barycentric coordinate makes the (wrapped-around) gather NaN, then everything is zeroed
-            const bool bad = !(isfinite(xsi) && isfinite(eta) && isfinite(zeta) && isfinite(tau));
-            if (bad && s < PK_ERRORINTERPOLATION) s = PK_ERRORINTERPOLATION;
-            c.state = s;
-            return;
-        }
+        if (fast_search_yx(T, F, c, fl, y, x, zi, zeta, tau, yi, xi, eta, xsi)) return;
     }
-    const bool lenT = tau > 0, lenZ = BR ? (c.zi & 1) != 0 : !(zeta <= 0);
-    // (PK_FAST_BLOCK_REGS: the hit test leaves lenZ out -- FCtx::bkey holds the level pair only, the waterfall's key has all three)
-    const int key = (ti << 2) | (lenT ? 2 : 0) | (!BR && lenZ ? 1 : 0);
-    // (a same-cell lane of the cell record formed no indices: past the out-of-bounds return they are the hints)
-    if (CR) { yi = c.hy; xi = c.hx; }
+    const bool lenT = tau > 0, lenZ = HELD ? (c.zi & 1) != 0 : !(zeta <= 0);
+    // (fast_held: the hit test leaves lenZ out -- FCtx::bkey holds the level pair only, the waterfall's key has all three)
+    const int key = (ti << 2) | (lenT ? 2 : 0) | (!HELD && lenZ ? 1 : 0);
     const uint32_t b00 = ((uint32_t)zi * F.st_z + (uint32_t)yi * F.st_y + (uint32_t)xi) * (uint32_t)sizeof(FT);
-    const double omt = 1 - tau, omz = 1 - zeta, omx = 1 - xsi, ome = 1 - eta;
-    const double w00 = omx * ome, w01 = xsi * ome, w10 = omx * eta, w11 = xsi * eta;
-    double uu = 0.0, vv = 0.0, ww = 0.0;
-    if constexpr (LP != FAST_LP_OFF) {
-        static_assert(!D3, "the level-pair arithmetic is the 2-D kernel's (z must not move)");
-        // FAST_LP_CACHE: only the lanes whose cell, depth or level pair changed since their block was formed fetch (a divergent branch most
-        // wave-evaluations of the odd stages skip and ~1.3 lanes take in the even ones); FAST_LP_REGS: every lane, every evaluation
-        const bool miss = LP == FAST_LP_REGS || c.ei != c.bei || key != c.bkey;
-        const bool some_miss = LP == FAST_LP_REGS || __builtin_amdgcn_ballot_w64(miss) != 0;
+    double uu = 0.0, vv = 0.0;
+    // FAST_LP_CACHE: only the lanes whose cell, depth or level pair changed since their block was formed fetch (a divergent branch most
+    // wave-evaluations of the odd stages skip and ~1.3 lanes take in the even ones); FAST_LP_REGS: every lane, every evaluation
+    const bool miss = !CACHE || c.ei != c.bei || key != c.bkey;
+    const bool some_miss = !CACHE || __builtin_amdgcn_ballot_w64(miss) != 0;
+    if (some_miss) {
+        if (HELD) zeta = depth_zeta();  // (its two reads are under way while the corner rows are requested)
+        const int wkey = HELD ? key | (lenZ ? 1 : 0) : key;
+        [[maybe_unused]] bool xposed = false;  // (wave-uniform) the transposed fetch served this wave-evaluation's missing lanes
+        if constexpr (HELD) {  // few missing lanes of a complete wavefront, resident levels: sixteen helpers per missing lane
+            const uint64_t mm = __builtin_amdgcn_ballot_w64(miss);
+            xposed = __builtin_amdgcn_ballot_w64(true) == ~0ull && !(fl & FA_RING) &&
+                     (uint32_t)__builtin_popcountll(mm) <= ((fl >> FA_MISS_LANES_SHIFT) & 127u);
+            if (xposed) {
+                lp_fetch_xposed<FT>(F, T, mm, wkey, b00, zeta);
+                if (miss) {
+                    c.bei = c.ei;
+                    c.bkey = key;
+                }
+            }
+        }
+        // the waterfall over the key, as in eval_uvw_fast (level bases stay in SGPRs); a lane that hit starts as done
+        for (bool done = !miss || xposed; !done;) {
+            const int uk = uniform_i32(wkey);
+            const int uti = uk >> 2;
+            int s0 = uti, s1 = uti + 1;
+            if (fl & FA_RING) {
+                s0 = (int)((uint32_t)s0 % (uint32_t)F.nslots);
+                s1 = (int)((uint32_t)s1 % (uint32_t)F.nslots);
+            }
+            int64_t o0 = (int64_t)s0 * F.lvl_b, o1 = (int64_t)s1 * F.lvl_b;
+            int lens = uk & 3;
+            asm volatile("" : "+s"(o0), "+s"(o1), "+s"(lens));
+            if (wkey == uk) {
+                if (lens == 3) lp_fetch<FT, true, true>(F, o0, o1, b00, zeta, fu, fv);
+                else if (lens == 2) lp_fetch<FT, true, false>(F, o0, o1, b00, zeta, fu, fv);
+                else if (lens == 1) lp_fetch<FT, false, true>(F, o0, o1, b00, zeta, fu, fv);
+                else lp_fetch<FT, false, false>(F, o0, o1, b00, zeta, fu, fv);
+                done = true;
+            }
+        }
+        // The block goes to LDS BEHIND the waterfall, from the registers FAST_LP_REGS uses.  (Written inside it -- U's entries between the two
+        // load batches, 4 VGPRs and 12 B of scratch less -- lanes of a wavefront that spans several level pairs read back other values
+        // than they had formed: tests/test_gpu_level_pair_cache.py::test_staggered_release_times_and_ring.)
+        if (CACHE && miss && !xposed) {
+            T.blk[0] = fu.p0; T.blk[FAST_WG_LP] = fu.p1; T.blk[2 * FAST_WG_LP] = fu.d0; T.blk[3 * FAST_WG_LP] = fu.d1;
+            T.blk[4 * FAST_WG_LP] = fv.p0; T.blk[5 * FAST_WG_LP] = fv.p1; T.blk[6 * FAST_WG_LP] = fv.d0; T.blk[7 * FAST_WG_LP] = fv.d1;
+            c.bei = c.ei;
+            c.bkey = key;
+        }
+    }
+    if constexpr (HELD) {
         if (some_miss) {
-            if (BR) zeta = depth_zeta();  // (its two reads are under way while the corner rows are requested)
-            const int wkey = BR ? key | (lenZ ? 1 : 0) : key;
-            [[maybe_unused]] bool xposed = false;  // (wave-uniform) the transposed fetch served this wave-evaluation's missing lanes
-            if constexpr (fast_miss_xpose(LP, PF)) {  // few missing lanes of a complete wavefront, resident levels: sixteen helpers per missing lane
-                const uint64_t mm = __builtin_amdgcn_ballot_w64(miss);
-                xposed = __builtin_amdgcn_ballot_w64(true) == ~0ull && !(fl & FA_RING) &&
-                         (uint32_t)__builtin_popcountll(mm) <= ((fl >> FA_MISS_LANES_SHIFT) & 127u);
-                if (xposed) {
-                    lp_fetch_xposed<FT>(F, T, mm, wkey, b00, zeta);
-                    if (miss) {
-                        c.bei = c.ei;
-                        c.bkey = key;
-                    }
-                }
-            }
-            // the waterfall over the key, as below (level bases stay in SGPRs); a lane that hit starts as done
-            for (bool done = !miss || xposed; !done;) {
-                const int uk = uniform_i32(wkey);
-                const int uti = uk >> 2;
-                int s0 = uti, s1 = uti + 1;
-                if (fl & FA_RING) {
-                    s0 = (int)((uint32_t)s0 % (uint32_t)F.nslots);
-                    s1 = (int)((uint32_t)s1 % (uint32_t)F.nslots);
-                }
-                int64_t o0 = (int64_t)s0 * F.lvl_b, o1 = (int64_t)s1 * F.lvl_b;
-                int lens = uk & 3;
-                asm volatile("" : "+s"(o0), "+s"(o1), "+s"(lens));
-                if (wkey == uk) {
-                    if (lens == 3) lp_fetch<FT, true, true>(F, o0, o1, b00, zeta, fu, fv);
-                    else if (lens == 2) lp_fetch<FT, true, false>(F, o0, o1, b00, zeta, fu, fv);
-                    else if (lens == 1) lp_fetch<FT, false, true>(F, o0, o1, b00, zeta, fu, fv);
-                    else lp_fetch<FT, false, false>(F, o0, o1, b00, zeta, fu, fv);
-                    done = true;
-                }
-            }
-            // The block goes to LDS BEHIND the waterfall, from the registers FAST_LP_REGS uses.  (Written inside it -- U's entries between the two
-            // load batches, 4 VGPRs and 12 B of scratch less -- lanes of a wavefront that spans several level pairs read back other values
-            // than they had formed: tests/test_gpu_level_pair_cache.py::test_staggered_release_times_and_ring.)
-            if (LP == FAST_LP_CACHE && miss && !xposed) {
-                T.blk[0] = fu.p0; T.blk[FAST_WG_LP] = fu.p1; T.blk[2 * FAST_WG_LP] = fu.d0; T.blk[3 * FAST_WG_LP] = fu.d1;
-                T.blk[4 * FAST_WG_LP] = fv.p0; T.blk[5 * FAST_WG_LP] = fv.p1; T.blk[6 * FAST_WG_LP] = fv.d0; T.blk[7 * FAST_WG_LP] = fv.d1;
-                c.bei = c.ei;
-                c.bkey = key;
-            }
+            c.fu.p0 = T.blk[0]; c.fu.p1 = T.blk[FAST_WG_LP]; c.fu.d0 = T.blk[2 * FAST_WG_LP]; c.fu.d1 = T.blk[3 * FAST_WG_LP];
+            c.fv.p0 = T.blk[4 * FAST_WG_LP]; c.fv.p1 = T.blk[5 * FAST_WG_LP]; c.fv.d0 = T.blk[6 * FAST_WG_LP]; c.fv.d1 = T.blk[7 * FAST_WG_LP];
         }
-        if constexpr (BR) {
-            if (some_miss) {
-                c.fu.p0 = T.blk[0]; c.fu.p1 = T.blk[FAST_WG_LP]; c.fu.d0 = T.blk[2 * FAST_WG_LP]; c.fu.d1 = T.blk[3 * FAST_WG_LP];
-                c.fv.p0 = T.blk[4 * FAST_WG_LP]; c.fv.p1 = T.blk[5 * FAST_WG_LP]; c.fv.d0 = T.blk[6 * FAST_WG_LP]; c.fv.d1 = T.blk[7 * FAST_WG_LP];
-            }
-            uu = lp_sum_held(c.fu, tau, eta, xsi);
-            vv = lp_sum_held(c.fv, tau, eta, xsi);
-        } else {
-            if (LP == FAST_LP_CACHE && (!SPEC || some_miss)) {
-                fu.p0 = T.blk[0]; fu.p1 = T.blk[FAST_WG_LP]; fu.d0 = T.blk[2 * FAST_WG_LP]; fu.d1 = T.blk[3 * FAST_WG_LP];
-                fv.p0 = T.blk[4 * FAST_WG_LP]; fv.p1 = T.blk[5 * FAST_WG_LP]; fv.d0 = T.blk[6 * FAST_WG_LP]; fv.d1 = T.blk[7 * FAST_WG_LP];
-            }
-            uu = lp_sum(fu, tau, eta, xsi);
-            vv = lp_sum(fv, tau, eta, xsi);
-        }
+        uu = lp_sum_held(c.fu, tau, eta, xsi);
+        vv = lp_sum_held(c.fv, tau, eta, xsi);
     } else {
-        const bool bc = !D3 && PK_FAST_BLOCK_CACHE && (fl & FA_BLK) != 0;
-        // (in-bounds indices ravel to a non-negative `ei` that names the cell; the memo updates above already dropped a block of another (t, z))
-        bool reuse = false;
-        if (bc && (bmode & 1)) reuse = __builtin_amdgcn_ballot_w64(c.ei != c.bei) == 0;  // every active lane: same cell, same (t, z)
-        if (reuse) {
-            const pk_tab2 b0 = T.blk[0], b1 = T.blk[FAST_WG], b2 = T.blk[2 * FAST_WG], b3 = T.blk[3 * FAST_WG];
-            uu = w00 * b0.x + w01 * b0.y + w10 * b1.x + w11 * b1.y;
-            vv = w00 * b2.x + w01 * b2.y + w10 * b3.x + w11 * b3.y;
-        } else {
-            const bool keep = bc && (bmode & 2);
-            pk_tab2* const blk = keep ? T.blk : nullptr;
-            for (bool done = false; !done;) {
-                // everything derived from the wave-uniform key is formed BEFORE the lane test: inside `if (key == uk)` the optimiser
-                // may substitute the (divergent) key for uk, which would move the level arithmetic back into vector registers
-                const int uk = uniform_i32(key);
-                const int uti = uk >> 2;
-                int s0 = uti, s1 = uti + 1;  // has_ti: 0 <= ti <= nt-2; otherwise ti == 0 and the second level is never read
-                if (fl & FA_RING) {          // ring of time levels: level L lives in slot L % nslots
-                    s0 = (int)((uint32_t)s0 % (uint32_t)F.nslots);
-                    s1 = (int)((uint32_t)s1 % (uint32_t)F.nslots);
-                }
-                int64_t o0 = (int64_t)s0 * F.lvl_b, o1 = (int64_t)s1 * F.lvl_b;
-                int lens = uk & 3;
-                asm volatile("" : "+s"(o0), "+s"(o1), "+s"(lens));  // opaque scalars: no path back to the divergent key
-                if (key == uk) {
-                    if (lens == 3) uvw_fast<FT, D3, true, true>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
-                    else if (lens == 2) uvw_fast<FT, D3, true, false>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
-                    else if (lens == 1) uvw_fast<FT, D3, false, true>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
-                    else uvw_fast<FT, D3, false, false>(F, o0, o1, b00, tau, omt, zeta, omz, w00, w01, w10, w11, uu, vv, ww, blk);
-                    done = true;
-                }
-            }
-            if (keep) c.bei = c.ei;
+        if (CACHE) {
+            fu.p0 = T.blk[0]; fu.p1 = T.blk[FAST_WG_LP]; fu.d0 = T.blk[2 * FAST_WG_LP]; fu.d1 = T.blk[3 * FAST_WG_LP];
+            fv.p0 = T.blk[4 * FAST_WG_LP]; fv.p1 = T.blk[5 * FAST_WG_LP]; fv.d0 = T.blk[6 * FAST_WG_LP]; fv.d1 = T.blk[7 * FAST_WG_LP];
         }
+        uu = lp_sum(fu, tau, eta, xsi);
+        vv = lp_sum(fv, tau, eta, xsi);
     }
-    if (fl & FA_SPH) {  // _xinterpolators.py:183-187
-        double conv;
-        if (PF && pos_f32) conv = (double)((float)F.deg2m * cosf((float)y * DEG2RADF));
-        else if constexpr (fast_conv_step(LP, PF)) conv = T.deg2m * cos_lat_lean(y);
-        else if constexpr (PK_FAST_LEAN != 0) conv = F.deg2m * cos_lat_lean(y);
-        else conv = F.deg2m * cos_lat(y * DEG2RAD);
-        if constexpr (PK_FAST_LEAN != 0) {  // u / conv, v / deg2m within 1.5 ulp: 7 operations instead of 22
-            uu = uu * rcp_lean(conv);
-            vv = vv * (fast_conv_step(LP, PF) ? T.inv_deg2m : F.inv_deg2m);
-        } else {
-            uu /= conv;
-            vv = div_by_recip(vv, F.deg2m, F.inv_deg2m);
-        }
-    }
-    // field.py:373-378 (one unordered compare answers "uu or vv is NaN")
-    if (__builtin_expect(__builtin_isunordered(uu, vv) || (D3 && ww != ww), 0)) {
-        if (c.state < PK_ERRORINTERPOLATION) c.state = PK_ERRORINTERPOLATION;
-    }
+    if (fl & FA_SPH) fast_convert<PF, HELD>(T, F, y, pos_f32, uu, vv);
+    fast_nan_state(c, uu, vv, 0.0);
     u = uu;
     v = vv;
-    w = ww;
 }
 
 #ifdef PK_USER_KERNELS
@@ -1049,12 +1024,7 @@ PK_DEV double eval_scalar_fast(const KArgs& a, const FastTabs& T, FCtx& c, int s
     if (F.has_x) fast_search(T.lon, F.gnx, F.x0, F.x1, x, c.hx, xi, xsi);
     c.ei = (int32_t)((uint32_t)xi * F.ex + (uint32_t)yi * F.ey + (uint32_t)zi * F.ez);
     if ((xi | yi | zi) < 0) {
-        int s = c.state;
-        if ((xi == RIGHT_OUT_OF_BOUNDS || yi == RIGHT_OUT_OF_BOUNDS || zi == RIGHT_OUT_OF_BOUNDS) && s < PK_ERROROUTOFBOUNDS) s = PK_ERROROUTOFBOUNDS;
-        if (zi == LEFT_OUT_OF_BOUNDS && s < PK_ERRORTHROUGHSURFACE) s = PK_ERRORTHROUGHSURFACE;
-        const bool bad = !(isfinite(xsi) && isfinite(eta) && isfinite(zeta) && isfinite(tau));
-        if (bad && s < PK_ERRORINTERPOLATION) s = PK_ERRORINTERPOLATION;
-        c.state = s;
+        c.state = fast_oob_state(c.state, xi, yi, zi, xsi, eta, zeta, tau);
         return 0.0;
     }
     const bool lenT = tau > 0, lenZ = !(zeta <= 0);

@@ -421,15 +421,7 @@ PK_DEV unsigned xcd_swizzle(unsigned bid, unsigned nb) {
 //     scalar registers, the row is chunk * 64 + lane.
 //   * A wavefront adds its steps / attempts / paused sums to the launch counters once, when it leaves (kept in scalar registers meanwhile).
 // Which lane of which wavefront steps a particle changes nothing a particle computes: every column is what the one-shot launch writes.
-// PK_FAST_PERSISTENT=0: the one-shot launch and its machine code (A/B builds).  The other instantiations of the kernel never loop.
-#ifndef PK_FAST_PERSISTENT
-#define PK_FAST_PERSISTENT 1
-#endif
-#ifdef PK_USER_KERNELS
-constexpr bool fast_persistent(int) { return false; }
-#else
-constexpr bool fast_persistent(int lp) { return PK_FAST_PERSISTENT != 0 && lp == FAST_LP_CACHE; }
-#endif
+// The other instantiations of the kernel never loop: one launch of ceil(n / 256) workgroups.
 constexpr int FAST_CHUNK = 64;  // rows per claim: one wavefront
 // -> the next chunk of this wavefront, false when every share is used up.  `tried` (wave-uniform, 0 at entry of the kernel): shares found empty so far.
 PK_DEV bool fast_claim(DCounters* cnt, unsigned nchunks, unsigned& tried, unsigned& chunk) {
@@ -771,14 +763,14 @@ __global__ void __launch_bounds__(fast_wg(LP), PK_MIN_WAVES_FAST) advect_fast_ke
         ft.lat = s_tab + a.fast.lds_lat;
         ft.lon = s_tab + a.fast.lds_lon;
         ft.blk = s_tab + a.fast.lds_blk + threadIdx.x;  // (read only where lds_blk != 0)
-        pin_scalars(ft, a.fast);
+        copy_scalars(ft, a.fast);
         ft.fl = fast_flags(a.fast) | ((a.win_lo > -INFINITY || a.win_hi < INFINITY) ? FA_WIN : 0u) | (a.prm.dt0 > 0 ? FA_FWD : 0u) |
                 (a.prm.max_iters > 0 ? FA_MAXIT : 0u);
-        // (pk_fast_agrid.h: PK_FAST_MISS_XPOSE -- the most missing lanes the transposed fetch serves, 0..64, beside the flags)
-        if constexpr (fast_miss_xpose(LP, PFM == 1)) ft.fl |= (uint32_t)a.fast.miss_lanes << FA_MISS_LANES_SHIFT;
+        // (pk_fast_agrid.h: lp_fetch_xposed -- the most missing lanes the transposed fetch serves, 0..64, beside the flags)
+        if constexpr (fast_held(LP, PFM == 1)) ft.fl |= (uint32_t)a.fast.miss_lanes << FA_MISS_LANES_SHIFT;
     }
-    // the persistent launch (fast_persistent, above): this wavefront's chunk of 64 rows and the shares it found empty, in scalar registers
-    constexpr bool PERS = fast_persistent(LP);
+    // the persistent launch (FAST_LP_CACHE, above): this wavefront's chunk of 64 rows and the shares it found empty, in scalar registers
+    constexpr bool PERS = LP == FAST_LP_CACHE;
     [[maybe_unused]] unsigned chunk = 0u, tried = 0u;
     [[maybe_unused]] const unsigned nchunks = PERS ? (unsigned)((a.p.n + FAST_CHUNK - 1) / FAST_CHUNK) : 0u;
     // the row index is re-derived where it is needed (entry and exit) instead of living in two registers across the step loop
@@ -808,7 +800,7 @@ __global__ void __launch_bounds__(fast_wg(LP), PK_MIN_WAVES_FAST) advect_fast_ke
             c.state = prm.reset_state ? PK_EVALUATE : P.state[i];  // kernel.py:188
             if (c.state == PK_EVALUATE) {
                 unsigned it = prm.reset_state ? 0u : (unsigned)P.iter[i];
-                fctx_init(c, PK_EVALUATE, P.ei[i * P.ngrids + a.fast.grid], fast_cell_regs(LP), fast_block_regs(LP, pf));  // only the velocity grid's `ei` is touched
+                fctx_init(c, PK_EVALUATE, P.ei[i * P.ngrids + a.fast.grid], LP == FAST_LP_CACHE, fast_held(LP, pf));  // only the velocity grid's `ei` is touched
                 double pt = P.t[i];
                 double pz = ldp(P.z, i, pf), py = ldp(P.y, i, pf), px = ldp(P.x, i, pf);
                 double pdz = ldp(P.dz, i, pf), pdy = ldp(P.dy, i, pf), pdx = ldp(P.dx, i, pf);
@@ -817,7 +809,7 @@ __global__ void __launch_bounds__(fast_wg(LP), PK_MIN_WAVES_FAST) advect_fast_ke
                 while (c.state == PK_EVALUATE) {  // :190 (no kernel of these programs sets Repeat)
                     uint32_t fl = ft.fl;  // (FastTabs::fl: the step loop's yes / no questions as scalar bit tests, not as saved lane masks)
                     asm volatile("" : "+s"(fl));
-                    if constexpr (fast_conv_step(LP, pf)) {  // (pk_fast_agrid.h: PK_FAST_CONV_STEP)
+                    if constexpr (fast_held(LP, pf)) {  // (pk_fast_agrid.h: the unit factors of one step)
                         ft.deg2m = a.fast.deg2m;
                         ft.inv_deg2m = a.fast.inv_deg2m;
                         asm volatile("" : "+s"(ft.deg2m), "+s"(ft.inv_deg2m));
@@ -854,9 +846,9 @@ __global__ void __launch_bounds__(fast_wg(LP), PK_MIN_WAVES_FAST) advect_fast_ke
                     // run, profiles/c2_eval_trim_ab.txt; the other instantiations keep one copy of the evaluation).
                     constexpr bool peel = LP != FAST_LP_OFF;
                     if constexpr (peel) {
-                        double u, v, w;
-                        eval_uvw_fast<FT, pf, D3, LP>(a, ft, c, pt, pz, py, px, pf, u, v, w, it, adv * 1000, 1);
-                        su = lu = u; sv = lv = v; sw = lw = w;
+                        double u, v;
+                        eval_uvw_lp<FT, pf, LP>(a, ft, c, pt, pz, py, px, pf, u, v, it, adv * 1000);
+                        su = lu = u; sv = lv = v;
                     }
 #pragma unroll 1
                     for (int stage = peel ? 1 : 0; stage < 4; stage++) {
@@ -868,11 +860,12 @@ __global__ void __launch_bounds__(fast_wg(LP), PK_MIN_WAVES_FAST) advect_fast_ke
                             if (D3) sz = pz + lw * cdt * pdt;
                             st = pt + cdt * pdt;
                         }
-                        double u, v, w;
-                        // stages 2 / 3 share t, stage 4 and stage 1 of the next step too: the odd evaluations keep their corner block, the even
-                        // ones test it (pk_fast_agrid.h: FCtx::bei)
-                        eval_uvw_fast<FT, pf, D3, LP>(a, ft, c, st, sz, sy, sx, pf && stage == 0, u, v, w, it, adv * 1000 + stage, (stage & 1) ? 2 : 1);
-                        if constexpr (fast_wsum(LP, pf)) {  // (stage 1 is peeled: stages 2 and 3 weigh 2, stage 4 weighs 1; pk_fast_agrid.h: PK_FAST_WSUM)
+                        double u, v, w = 0.0;
+                        // stages 2 / 3 share t, stage 4 and stage 1 of the next step too: the odd evaluations of the stage-pair evaluator keep their
+                        // corner block, the even ones test it (pk_fast_agrid.h: FCtx::bei)
+                        if constexpr (peel) eval_uvw_lp<FT, pf, LP>(a, ft, c, st, sz, sy, sx, pf && stage == 0, u, v, it, adv * 1000 + stage);
+                        else eval_uvw_fast<FT, pf, D3>(a, ft, c, st, sz, sy, sx, pf && stage == 0, u, v, w, it, adv * 1000 + stage, (stage & 1) ? 2 : 1);
+                        if constexpr (fast_held(LP, pf)) {  // (stage 1 is peeled: stages 2 and 3 weigh 2, stage 4 weighs 1; pk_fast_agrid.h: fma3s)
                             const double wgt = stage == 3 ? 1.0 : 2.0;
                             su = fma3s(wgt, u, su);
                             sv = fma3s(wgt, v, sv);
@@ -908,8 +901,8 @@ __global__ void __launch_bounds__(fast_wg(LP), PK_MIN_WAVES_FAST) advect_fast_ke
                         px = padd(pf, px, pdx);
                         py = padd(pf, py, pdy);
                         // (the level-pair kernel with the cell record searches depth only when told that z moved: a dz brought into the launch)
-                        if constexpr (fast_cell_regs(LP)) {
-                            if (__builtin_expect(!(pdz == 0), 0)) fctx_depth_moved(c, fast_block_regs(LP, pf));
+                        if constexpr (LP == FAST_LP_CACHE) {
+                            if (__builtin_expect(!(pdz == 0), 0)) fctx_depth_moved(c, fast_held(LP, pf));
                         }
                         pz = padd(pf, pz, pdz);
                         pt += pdt;
@@ -1482,7 +1475,7 @@ template <int PROG>
 void launch_fast(int field_f32, int particles_f32, const KArgs& a, dim3 grid, size_t lds_bytes, hipStream_t stream);
 // AdvectionRK4 in the level-pair modes (lp: FAST_LP_REGS / FAST_LP_CACHE; a translation unit of its own): the grid is derived from the
 // mode's workgroup size, and the cache's workgroups may ask for more dynamic LDS than the 64 KB a kernel gets without saying so
-// compute_units, grid_cap: the persistent launch of the cache mode (fast_persistent) starts min(ceil(n / 512), compute_units x workgroups resident per CU)
+// compute_units, grid_cap: the persistent launch of the cache mode (fast_claim) starts min(ceil(n / 512), compute_units x workgroups resident per CU)
 // workgroups, at most grid_cap of them when grid_cap > 0 (pk_set_option "fast_grid")
 hipError_t launch_fast_lp(int lp, int field_f32, int particles_f32, const KArgs& a, size_t lds_bytes, int compute_units, int grid_cap, hipStream_t stream);
 
@@ -1508,7 +1501,7 @@ hipError_t launch_fast_lp(int lp, int field_f32, int particles_f32, const KArgs&
             if (e != hipSuccess) return e;                                                                                          \
         }                                                                                                                           \
         unsigned nwg = (unsigned)((a.p.n + WG - 1) / WG);                                                                           \
-        if (fast_persistent(LP)) { /* what is resident at once, at the real dynamic LDS size (asked once per size) */               \
+        if (LP == FAST_LP_CACHE) { /* what is resident at once, at the real dynamic LDS size (asked once per size) */               \
             static thread_local size_t q_lds = ~(size_t)0;                                                                          \
             static thread_local int q_nb = 0;                                                                                       \
             if (q_lds != lds_bytes) {                                                                                               \

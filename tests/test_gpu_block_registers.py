@@ -1,4 +1,4 @@
-"""The block in registers of the level-pair kernel (csrc/pk_fast_agrid.h: PK_FAST_BLOCK_REGS).
+"""The block in registers of the level-pair kernel (csrc/pk_fast_agrid.h: fast_held, FCtx::fu).
 
 With the level-pair cache (option "block_cache" 2) and the cell record, a lane keeps Z0 / D of U and V -- the sixteen doubles of its LDS slot
 -- in registers from one evaluation to the next and from one step to the next; a wave-evaluation without a missing lane reads nothing of

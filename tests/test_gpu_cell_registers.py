@@ -1,4 +1,4 @@
-"""The cell record of the level-pair kernel (csrc/pk_fast_agrid.h: PK_FAST_CELL_REGS).
+"""The cell record of the level-pair kernel (csrc/pk_fast_agrid.h: eval_uvw_lp, FCtx::ya).
 
 With the level-pair cache (option "block_cache" 2) a lane keeps the coordinate-table entries of its cell -- first node, second node and
 1 / width of lat and of lon -- in registers, and an evaluation inside that cell touches neither the tables nor the cell index; depth is

@@ -1,4 +1,4 @@
-"""The stage weights of the level-pair kernel as one fused operation (csrc/pk_fast_agrid.h: PK_FAST_WSUM).
+"""The stage weights of the level-pair kernel as one fused operation (csrc/pk_fast_agrid.h: fma3s).
 
 The kernels that keep their block in registers (option "block_cache" 2, float64 particle storage) accumulate the Runge-Kutta sum of the looped
 stages as su = fma(wgt, u, su) with wgt = 2 or 1; option 0 goes on computing su + 2*u and su + u.  2*u is exact below 2^1023, so the two round

@@ -1,4 +1,4 @@
-"""The transposed block fetch of the level-pair cache (csrc/pk_fast_agrid.h: PK_FAST_MISS_XPOSE, option "miss_lanes").
+"""The transposed block fetch of the level-pair cache (csrc/pk_fast_agrid.h: lp_fetch_xposed, option "miss_lanes").
 
 When at most `miss_lanes` lanes of a complete wavefront miss their block, sixteen helper lanes per missing lane fetch its corner rows in one
 round trip and form lp_field's values with three cross-lane exchanges (tests/test_lp_transposed_model.py pins the lane map); every other

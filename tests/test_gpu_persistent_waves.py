@@ -1,4 +1,4 @@
-"""The persistent launch of the level-pair-cache A-grid kernel (csrc/pk_kernels.h: fast_persistent, fast_claim; option "fast_grid").
+"""The persistent launch of the level-pair-cache A-grid kernel (csrc/pk_kernels.h: advect_fast_kernel, fast_claim; option "fast_grid").
 
 The launch starts only as many workgroups as are resident at once; every wavefront claims chunks of 64 consecutive rows -- from its XCD's
 eighth of the chunks first, then from the other XCDs' -- until none is left.  Which lane steps a particle changes nothing a particle

@@ -1,4 +1,4 @@
-"""The transposed block fetch of the level-pair cache (csrc/pk_fast_agrid.h: PK_FAST_MISS_XPOSE) forms lp_field's bits, on the host.
+"""The transposed block fetch of the level-pair cache (csrc/pk_fast_agrid.h: lp_fetch_xposed) forms lp_field's bits, on the host.
 
 Sixteen helper lanes hold one corner row {cx, cy} each of a missing lane's cell -- lane j: bit 0 = k (depth row), bit 1 = r (lat row), bit 2 = l
 (time level), bit 3 = f (U / V) -- and run three exchange steps: the z lerp with lane j^1, the level difference with lane j^4, the polynomial basis

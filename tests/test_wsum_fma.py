@@ -1,4 +1,4 @@
-"""fma(w, u, s) == s + w*u in every bit for w = 1 and w = 2 (csrc/pk_fast_agrid.h: PK_FAST_WSUM), on the host.
+"""fma(w, u, s) == s + w*u in every bit for w = 1 and w = 2 (csrc/pk_fast_agrid.h: fma3s), on the host.
 
 w*u is exact for w = 1, and for w = 2 whenever |u| < 2^1023 (a change of the exponent; a subnormal doubles exactly), so both forms round the
 same exact sum once.  |u| >= 2^1023 is the documented exception (2*u overflows before the addition) and is left out.  A small C function, built

@@ -1,11 +1,8 @@
 #!/bin/bash
 # A/B builds of the fast kernels: tools/build_variant.sh NAME -DPK_MIN_WAVES_FAST=5 ... -> parcels_amd/libparcels_hip_NAME.so
 # (select it at run time with PARCELS_HIP_LIB=...; the other objects are those of the last `make`)
-# Switches of the level-pair kernels (pk_fast_agrid.h), each 1 by default: -DPK_FAST_CELL_REGS=0 (table search in every evaluation),
-# -DPK_FAST_BLOCK_REGS=0 (the lane's block is read from LDS in every evaluation; also turns the time record off),
-# -DPK_FAST_TIME_REC=0 (the time memo instead of the time-cell record), -DPK_FAST_WSUM=0 (su + 2*u instead of the fused stage weights),
-# -DPK_FAST_CONV_STEP=0 (deg2m and 1 / deg2m as kernel arguments, not as scalars of one step), -DPK_FAST_MISS_XPOSE=0 (the waterfall for every
-# missing lane: no transposed block fetch)
+# Switches that select code: -DPK_FAST_LEAN=0 (pk_fast_agrid.h), -DPK_CG_LEAN=0 / -DPK_CG_NEAR=0 (pk_fast_cgrid.h); knobs: PK_MIN_WAVES_*, PK_CG_CACHE*
+# (pk_kernels.h).  A change of the kernels themselves is compared against a build of the parent commit, selected the same way.
 set -e
 NAME=$1; shift
 cd "$(dirname "$0")/../parcels_amd/csrc"

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The `miss_lanes` threshold of the transposed block fetch on the headline launch (pk_fast_agrid.h: PK_FAST_MISS_XPOSE; DESIGN.md §4,
+"""The `miss_lanes` threshold of the transposed block fetch on the headline launch (pk_fast_agrid.h: lp_fetch_xposed; DESIGN.md §4,
 profiles/c2_miss_transposed_ab.txt).
 
     python tools/miss_transposed_ab.py [--values 0,1,2,4,8,16,64] [--steps 24] [--rounds 3] [--reps 3] [--uv-scale 1.0] [--out FILE]
