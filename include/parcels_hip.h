@@ -354,7 +354,7 @@ int32_t pk_particles_restore(pk_ctx* ctx);
 int32_t pk_particles_snapshot_begin(pk_ctx* ctx, uint32_t column_mask, int32_t slot);
 int32_t pk_particles_snapshot_wait(pk_ctx* ctx, int32_t slot, pk_particles_desc* out_host_columns);
 /* The same snapshot, but only of the rows that pass ParticleFile's write filter `|t_p - t| <= |dt|/2` (particlefile.py:198-221) at output
- * time t -- selected and packed ON THE DEVICE in host row order (csrc/pk_select.inc): only the rows a table holds cross PCIe, and the
+ * time t -- selected and packed ON THE DEVICE in host row order (csrc/pk_api.hip: select_flags): only the rows a table holds cross PCIe, and the
  * writer thread has nothing left to filter.  pk_particles_snapshot_wait reports their number in pk_particles_desc.n. */
 int32_t pk_particles_snapshot_filtered(pk_ctx* ctx, uint32_t column_mask, int32_t slot, double t);
 /* device pointers of the bound columns in CURRENT device order (for RCCL all-gather of the output

@@ -3,260 +3,15 @@
 // Owns device memory (grids, field-level rings, particle columns), two HIP streams (compute + copy, so that
 // the upload of the next time level overlaps the RK sub-steps of the current one) and the launch logic.
 // gfx950 only; no CUDA/other-backend paths.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <array>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <thread>
-#include <vector>
+#include "pk_api_ctx.h"
 
 #include <rocprim/rocprim.hpp>
 
-#include "pk_hashbuild.h"
-#include "pk_neighbors.h"
-#include "pk_interact.h"
-#include "pk_density.h"
-#include "pk_connectivity.h"
-#include "pk_host_stage.h"
-#include "pk_kernels.h"
-#include "pk_ux.h"
-#include "pk_sigma.h"
+using namespace pkapi;
 
-using namespace pk;
-
-namespace {
+namespace pkapi {
 std::string g_init_error;
 }
-
-struct HostGrid {
-    pk_grid_desc desc;
-    DGrid d;
-    std::vector<void*> allocs;
-    int64_t h_nentries = 0;
-};
-
-struct HostField {
-    pk_field_desc desc;
-    DField d;
-    void* dev_data = nullptr;
-    double* dev_time = nullptr;
-    size_t level_bytes = 0;
-    std::vector<double> time;
-    bool owns_data = true;   // false for followers of a packed group (the leader owns the interleaved buffer)
-    int pack_used = 1;       // leader: components handed out so far
-    std::vector<int32_t> slot_level;    // committed (usable) level per ring slot, -1 = empty
-    std::vector<int32_t> slot_pending;  // level being copied into the slot (async upload), -1 = none
-    std::vector<uint64_t> slot_gen;     // stamp of the last upload into the slot (pk_ctx::upload_counter): tells a re-upload of the same level apart
-};
-
-// ---- the particle columns: ONE table -------------------------------------------------------------------
-// Every operation on the particle columns (allocate, free, copy, sort, compact, checkpoint, snapshot, exchange) walks this list, in this
-// order: it is the bit order of the PK_COL_* masks, the layout of the checkpoint buffer and the order of the exchange.
-//   X(member of pk_particles_desc and of DParticles, mask bit, element bytes, `ngrids` values per row, exists only where the host binds one)
-// COL_SPATIAL: 4 or 8 bytes by pk_particles_desc::spatial_dtype.  Behind these rows come the PK_MAX_EXTRA user columns (index
-// PK_COL_EXTRA_FIRST + k, bit PK_COL_EXTRA0 << k, 4 or 8 bytes by extra_dtype[k], optional, no launch writes them) and the device-only
-// `iter` (index PK_NCOLS of particle_columns: no bit, 4 bytes, written by a launch).
-constexpr int COL_SPATIAL = 0;
-// the columns an advection launch writes: with `iter`, the members of DPOut (pk_device.h)
-#define PK_LAUNCH_COLUMNS(X)                       \
-    X(t, PK_COL_T, 8, false, false)                \
-    X(z, PK_COL_Z, COL_SPATIAL, false, false)      \
-    X(y, PK_COL_Y, COL_SPATIAL, false, false)      \
-    X(x, PK_COL_X, COL_SPATIAL, false, false)      \
-    X(dz, PK_COL_DZ, COL_SPATIAL, false, false)    \
-    X(dy, PK_COL_DY, COL_SPATIAL, false, false)    \
-    X(dx, PK_COL_DX, COL_SPATIAL, false, false)    \
-    X(dt, PK_COL_DT, 8, false, false)              \
-    X(next_dt, PK_COL_NEXT_DT, 8, false, true)     \
-    X(state, PK_COL_STATE, 4, false, false)        \
-    X(ei, PK_COL_EI, 4, true, false)
-#define PK_COLUMNS(X) PK_LAUNCH_COLUMNS(X) X(particle_id, PK_COL_PARTICLE_ID, 8, false, false)
-
-struct ColInfo { uint32_t bit; int elem; bool per_grid, optional; };
-#define X(m, bit, elem, per_grid, optional) {bit, elem, per_grid, optional},
-constexpr ColInfo PK_COL_INFO[] = {PK_COLUMNS(X)};
-#undef X
-#define X(m, bit, elem, per_grid, optional) | bit
-constexpr uint32_t PK_LAUNCH_MASK = 0u PK_LAUNCH_COLUMNS(X);
-#undef X
-constexpr int PK_COL_EXTRA_FIRST = (int)(sizeof(PK_COL_INFO) / sizeof(PK_COL_INFO[0]));
-constexpr int PK_NCOLS = PK_COL_EXTRA_FIRST + PK_MAX_EXTRA;
-constexpr bool col_bits_in_table_order() {
-    for (int k = 0; k < PK_COL_EXTRA_FIRST; k++)
-        if (PK_COL_INFO[k].bit != 1u << k) return false;
-    return PK_COL_EXTRA0 == 1u << PK_COL_EXTRA_FIRST;
-}
-static_assert(col_bits_in_table_order(), "the table lists the columns in the bit order of the PK_COL_* masks (parcels_hip.h)");
-
-constexpr int PK_STAGE_BUFFERS = 3;  // pinned staging chunks of the level stream (see stage_acquire)
-
-// device scratch of the write filter (pk_select.inc): flag per host row, exclusive scan of the flags
-struct PkSelect {
-    uint32_t* d_flag = nullptr;
-    uint32_t* d_offs = nullptr;
-    int64_t cap = 0;
-    void* d_tmp = nullptr;
-    size_t tmp_bytes = 0;
-};
-struct PkComm;
-// {a, 1/width} rows of the coordinate vectors a dedicated kernel stages in LDS, built once per (grid, field) by coord_table
-struct CoordTable {
-    double* d = nullptr;  // device copy, `cap` doubles
-    size_t cap = 0;
-    int grid = -1, field = -1;
-    bool ok = false;       // every cell width has a well-scaled reciprocal and the table fits the kernel's LDS
-    int32_t off[5] = {};   // first row of each vector, then the row count
-};
-struct pk_ctx {
-    int device = 0;
-    hipStream_t compute = nullptr, copy = nullptr;
-    hipStream_t probe = nullptr;     // the clock probe runs beside the advection kernel (created on first use)
-    hipEvent_t ev_probe = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-    hipEvent_t ev_p0 = nullptr, ev_p1 = nullptr;  // around the pair-copy packing of a launch (ensure_velocity_pairs)
-    int fl_packs = 0;                             // pairs packed ahead of the launch in flight
-    bool copy_pending = false;
-    std::string err;
-    std::vector<HostGrid> grids;
-    std::vector<HostField> fields;
-    // particles
-    pk_particles_desc host{};
-    DParticles dev{};
-    int64_t capacity = 0;
-    bool bound = false;
-    // sorted-order bookkeeping
-    int64_t* d_perm = nullptr;      // device row -> host row (valid when has_perm)
-    bool has_perm = false;
-    int64_t* d_perm_alt = nullptr;
-    DParticles alt{};               // second set of columns (ping-pong target of the cell sort, staging of d2h)
-    unsigned long long *d_keys = nullptr, *d_keys_alt = nullptr;
-    uint32_t *d_idx = nullptr, *d_idx_alt = nullptr;
-    void* d_sort_tmp = nullptr;
-    size_t sort_tmp_bytes = 0;
-    void* d_pack_tmp = nullptr;  // device staging of one field level before it is interleaved into a packed group
-    size_t pack_tmp_bytes = 0;
-    // scratch
-    DCounters* d_counters = nullptr;
-    // device copy of the grid / field descriptors the kernels read through KArgs::grids / fields (pk_device.h), and its pinned source
-    char *d_desc = nullptr, *h_desc = nullptr;
-    size_t desc_bytes = 0;
-    unsigned long long* d_summary = nullptr;  // PK_NUM_STATE_CODES counts + 2 ordered-double slots
-    // pinned staging ring for async level uploads
-    void* stage[PK_STAGE_BUFFERS] = {};
-    size_t stage_bytes[PK_STAGE_BUFFERS] = {};
-    size_t stage_chunk = 0;  // bytes per staging chunk: the largest streamed level (x its packed components), at most PK_STAGE_CHUNK_BYTES
-    hipEvent_t stage_ev[PK_STAGE_BUFFERS] = {};
-    int stage_next = 0;
-    double stage_fill_s = 0, stage_wait_s = 0, stage_bytes_total = 0;  // pk_upload_stats
-    hipDeviceProp_t prop;
-    // an advection launch in flight (pk_execute_begin .. pk_execute_end)
-    bool in_flight = false;
-    int fl_launches = 0;
-    int fl_program = 0;
-    // the last advection launch wrote into the second column set, which now is `dev`; `alt` still holds what it read
-    bool rerun_valid = false;
-    pk_exec_params rerun_prm{};
-    // launcher of the run-time compiled kernel-list interpreter that carries the user kernels (pk_set_user_program)
-    void (*user_launch)(const void*, int32_t, int32_t, int32_t, uint64_t, void*) = nullptr;
-    int32_t user_flags = 0;
-    int32_t user_nsample = 0;       // scalar fields the module's user kernels sample (PK_USER_RIDE modules)
-    int32_t user_sample_fid[4] = {0, 0, 0, 0};
-    // pk_particles_checkpoint: one packed device copy of every column (+ the row permutation of the cell sort)
-    char* d_chk = nullptr;
-    size_t chk_bytes = 0;
-    bool chk_valid = false, chk_has_perm = false;
-    int64_t chk_n = 0;
-    bool fl_sorted = false;
-    int64_t fl_n = 0;
-    DCounters* h_counters = nullptr;          // pinned: the async D2H of the counters must not block the host
-    DCounters h_counters0;                    // initial values of a launch's counters (pageable: the H2D copy stages it at once)
-    unsigned long long* d_twe = nullptr;      // PK_MAX_TWE keys: the failing samples a launch knows (pk_exec_params.twe_key)
-    unsigned long long* d_twe_found = nullptr;  // TWE_FOUND_SLOTS: hash set of the unlisted failing samples of a launch (pk_device.h: twe_note_all)
-    unsigned int* d_twe_hit = nullptr;          // PK_MAX_TWE: listed sample k was justified by a lane of the launch (twe_justify)
-    std::vector<int64_t> twe_found_host;        // ... of the last completed launch, ascending (pk_execute_twe_report)
-    std::vector<uint8_t> twe_hit_host;
-    bool twe_overflow_host = false;
-    int fl_twe_n = 0;                           // listed keys of the launch in flight
-    std::vector<int64_t> rerun_keys;          // the keys of the last launch (pk_execute_rerun repeats it with them)
-    unsigned long long* h_summary = nullptr;  // pinned
-    unsigned long long* d_tstats = nullptr;   // pk_particles_t_stats: {ordered min, ordered max, NaN count} (its own 24 bytes: not the clock-probe buffer)
-    unsigned long long* d_clk = nullptr;      // clock probes around the advection kernel: [before | after][XCD 0..7]{shader-clock counter, 100 MHz counter}
-    unsigned long long* h_clk = nullptr;      // pinned
-    // CROCO sigma grids (pk_set_croco): the {s_k, Cs_k} pairs on the device and what the kernels need beside them (pk_sigma.h)
-    double* d_sigma = nullptr;
-    SigmaA sigma{};
-    bool has_sigma = false;
-    int sort_horizontal_major = -1;  // tuning knobs (environment: PK_SORT_HORIZONTAL = 0/1 forces, PK_NO_SPECIAL, PK_NO_CELL_CACHE)
-    int no_special = 0;
-    bool eval_points_f32 = false;  // pk_eval: the sample points are float32 particle columns (np.cos(np.deg2rad(y)) is then a float32 cosine)
-    int no_cell_cache = 0;
-    int no_hash_dir = 0;
-    int no_cell_table = 0;
-    int no_fast = 0;
-    int no_fast_cgrid = 0;
-    bool no_block_cache = false;  // PK_NO_BLOCK_CACHE: the 2-D A-grid kernel without its per-lane corner-block cache
-    int block_cache = -1;         // option "block_cache": -1 plan_launch's rule, 0 none, 1 stage-pair block, 2 level-pair cache or fail
-    int miss_lanes = -1;          // option "miss_lanes": the most missing lanes of a wavefront the level-pair cache fetches transposed, -1 planned
-    int fast_grid = 0;            // option "fast_grid": workgroups of the persistent A-grid launch -- 0 what is resident at once (pk_kernels.h), v > 0 at most v
-    // asynchronous write-out snapshots (pk_particles_snapshot_begin / _wait): two sets of device staging columns (host row order)
-    // + pinned host columns, so that the D2H and the encode of interval k overlap the launch of interval k+1
-    struct Snapshot {
-        void* dev[PK_NCOLS] = {};
-        void* host[PK_NCOLS] = {};
-        int64_t capacity = 0;  // rows the buffers were sized for
-        int64_t n = 0;         // rows of the snapshot in flight
-        uint32_t mask = 0;
-        int ngrids = 0;
-        size_t ss = 0;
-        size_t extra_elem[PK_MAX_EXTRA] = {};
-        hipEvent_t ready = nullptr, done = nullptr;
-        bool in_flight = false;
-    } snap[2];
-    // coordinate tables of the fast A-grid path (pk_fast_agrid.h: time | depth | lat | lon) and of the fast C-grid path (pk_fast_cgrid.h:
-    // time | depth), cached per (main grid, main field)
-    CoordTable tab_a, tab_c;
-    // fast C-grid path: per-cell records of one grid
-    double* d_ct2 = nullptr;
-    int ct2_grid = -1;
-    int ct2_near = 0;  // FastC::near_edges of that grid
-    // cell-packed pair copies of the staggered velocity for the 2-D dedicated C-grid kernels (pk_device.h: FastC::vp)
-    char* d_vp = nullptr;
-    size_t vp_bytes = 0;
-    int vp_fU = -1, vp_fV = -1;
-    std::vector<int32_t> vp_level;        // pair held by every pair slot, -1 = none
-    std::vector<uint64_t> vp_gen;         // 4 stamps per pair slot: U and V uploads of both levels it was packed from
-    int clock_probe = 0;        // measure the shader clock behind every advection kernel (option "clock_probe"; bench.py switches it on)
-    bool fl_clock_probe = false;
-    int no_velocity_pairs = 1;  // OPT-IN since round 5 (option "velocity_pairs" / PK_VELOCITY_PAIRS=1): packing a pair costs more than the
-                                // launch it serves saves at BASELINE config 5 (pk_exec_stats.pack_ms)
-    uint64_t upload_counter = 0;
-
-    PkSelect sel;                   // write filter on the device rows (pk_select.inc): the filtered snapshot and the multi-GPU exchange use it
-    struct PkComm* comm = nullptr;  // the multi-GPU exchange (pk_comm.inc: RCCL communicator + staging), NULL until pk_comm_init
-    pk::Neighbors* nbr = nullptr;   // neighbour search (pk_neighbors.hip: cell list + scratch), NULL until pk_neighbors_build
-    pk::Interact* inter = nullptr;  // counters of the interaction loop (pk_interact.hip), NULL until pk_interact_prologue
-
-    int32_t fail(const char* where, hipError_t e) {
-        err = std::string(where) + ": " + hipGetErrorString(e);
-        return -1;
-    }
-    int32_t fail(const std::string& msg) {
-        err = msg;
-        return -2;
-    }
-};
-
-#define PK_HIP(ctx, call)                                  \
-    do {                                                   \
-        hipError_t e_ = (call);                            \
-        if (e_ != hipSuccess) return (ctx)->fail(#call, e_); \
-    } while (0)
 
 // ---- small device kernels owned by this TU ------------------------------------------------------------
 namespace pk {
@@ -311,101 +66,8 @@ __global__ void __launch_bounds__(256) summarize_kernel(const int32_t* state, co
     }
 }
 
-// Field.eval / VectorField.eval at explicit points (no particles): what >= 0 scalar field, -1 UV, -2 UVW
-template <class FT, int INTERP, bool TYPED>
-__global__ void __launch_bounds__(256) eval_kernel(const KArgs a, int what, int64_t m, const double* t, const double* z,
-                                                   const double* y, const double* x, double* ou, double* ov, double* ow,
-                                                   int32_t* ost) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    const DField& mf = kfield(a, a.main_field);
-    const DGrid& mg = kgrid(a, a.main_grid);
-    Coords mc{CellCache{nullptr, nullptr, nullptr}, mf.time, mg.depth, mg.lat, mg.lon, mf.tfirst, mf.tlast, mg.zfirst, mg.zlast, mg.yfirst, mg.ylast, mg.xfirst, mg.xlast};
-    PCtx c;
-    c.state = PK_EVALUATE;
-    c.pf = false;
-    c.hz = c.hy = c.hx = c.ht = 0;
-    c.hyx_valid = false;
-    c.first_eval = 0xFu;
-    c.u32 = c.v32 = false;
-    c.oob = false;
-    c.ei0 = c.ei1 = c.ei2 = c.ei3 = 0;
-    c.it = 0u;  // not inside the loop of kernel.py:190: the caller of pk_eval owns the batch (parcels_amd/field.py: _eval_key)
-    c.klo = 0;
-    const bool pos_f32 = a.prm.reset_state != 0;  // (pk_eval's own use of the field: option "eval_points_f32")
-    c.zpos_f32 = pos_f32;
-    if (what < 0) {
-        double u, v, w;
-        eval_uvw<FT, -1, INTERP, TYPED>(a, mc, c, what == -2, t[i], z[i], y[i], x[i], pos_f32, u, v, w);
-        ou[i] = u;
-        if (ov) ov[i] = v;
-        if (ow) ow[i] = w;
-    } else {
-        ou[i] = eval_scalar<FT, TYPED>(a, mc, c, what, t[i], z[i], y[i], x[i], pos_f32);
-    }
-    if (ost) ost[i] = c.state | (c.oob ? PK_EVAL_MASKED : 0);
-}
-
-// One pk_eval call is one batch of the reference: lenT = 2 if np.any(tau > 0) else 1, lenZ likewise over the WHOLE batch
-// (_xinterpolators.py:130-131,401-402,575-576).  flags: bit 0 any(tau > 0), bit 1 any(zeta > 0).
-__global__ void __launch_bounds__(256) batch_len_kernel(const DField f, const DGrid g, int64_t m, const double* t, const double* z, unsigned* flags) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    unsigned fl = 0;
-    if (i < m) {
-        GPos p;
-        if (time_search(f, f.time, t[i], 0, p) && p.tau > 0) fl |= 1u;
-        if (g.has_z) {
-            search_1d(g.depth, g.nz, g.depth[0], g.depth[g.nz - 1], z[i], g.depth_f32 != 0, false, 0, p.zi, p.zeta);
-            if (p.zeta > 0) fl |= 2u;
-        }
-    }
-    if (__any(fl & 1u) && (threadIdx.x & 63) == 0) atomicOr(flags, 1u);
-    if (__any(fl & 2u) && (threadIdx.x & 63) == 0) atomicOr(flags, 2u);
-}
-
-// XGrid.search + ravel_index without a guess (ParticleSet.populate_indices, particleset.py:252-262)
-__global__ void __launch_bounds__(256) search_kernel(const DGrid g, int64_t m, const double* z, const double* y, const double* x,
-                                                     int32_t* ei_out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    PCtx c;
-    c.state = PK_EVALUATE;
-    c.pf = false;
-    c.hz = c.hy = c.hx = c.ht = 0;
-    c.hyx_valid = false;
-    c.zpos_f32 = false;
-    GPos p;
-    int32_t ei = 0;
-    grid_search<-1, false>(g, nullptr, z[i], y[i], x[i], false, &ei, c, false, p);  // indices only: dtype emulation of the bcoords is irrelevant
-    ei_out[i] = ei;
-}
-
 // ---- cell sort ----------------------------------------------------------------------------------------
-// key = linear cell index of the particle's current position on the main grid (z-major like the field layout),
-// so that the 64 lanes of a wavefront gather from neighbouring cells (coalesced, L2-friendly).
-__global__ void __launch_bounds__(256) sort_key_kernel(const DGrid g, const DParticles P, unsigned long long* keys, uint32_t* idx,
-                                                       int horizontal_major) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= P.n) return;
-    const bool pf = P.spatial_f32 != 0;
-    const double z = pf ? (double)((const float*)P.z)[i] : ((const double*)P.z)[i];
-    const double y = pf ? (double)((const float*)P.y)[i] : ((const double*)P.y)[i];
-    const double x = pf ? (double)((const float*)P.x)[i] : ((const double*)P.x)[i];
-    unsigned long long zi = 0, h = 0;
-    if (g.has_z && g.nz >= 2) zi = (unsigned long long)cell_index(g.depth, g.nz, z, 0);
-    if (g.kind == 1) {
-        // depth-major like the field layout, then the 30-bit Morton code of the hash grid (neighbouring codes = neighbouring
-        // cells).  Measured on C3: depth-major 295 ms vs horizontal-major 308 ms per 3.6e8 particle-steps.
-        h = morton_code(g, make_qpoint(g, y, x));
-        keys[i] = horizontal_major ? ((h << 12) | (zi & 0xFFFull)) : ((zi << 30) | h);
-    } else {
-        unsigned long long yi = (g.has_y && g.ny >= 2) ? (unsigned long long)cell_index(g.lat, g.ny, y, 0) : 0;
-        unsigned long long xi = (g.has_x && g.nx >= 2) ? (unsigned long long)cell_index(g.lon, g.nx, x, 0) : 0;
-        keys[i] = (zi * (unsigned long long)g.ny + yi) * (unsigned long long)g.nx + xi;
-    }
-    idx[i] = (uint32_t)i;
-}
-
+// (its key kernel, sort_key_kernel, is compiled in pk_api_sample.hip, behind sort_keys: see there)
 template <class T>
 __global__ void __launch_bounds__(256) gather_rows_kernel(const T* __restrict__ in, T* __restrict__ out,
                                                           const uint32_t* __restrict__ perm, int64_t n, int width) {
@@ -689,7 +351,7 @@ static int32_t upload(pk_ctx* ctx, HostGrid& g, const T* host, size_t n, const T
     return 0;
 }
 
-static void free_particles(pk_ctx* ctx);  // the particles section
+namespace pkapi { static void free_particles(pk_ctx* ctx); }  // the particles section
 
 // ---- context -------------------------------------------------------------------------------------------
 extern "C" {
@@ -1349,32 +1011,11 @@ int32_t pk_field_slots(pk_ctx* ctx, int32_t field_id, int32_t* levels, int32_t* 
 
 }  // extern "C" (helpers with C++ linkage follow)
 
+namespace pkapi {
+
 // ---- particles -----------------------------------------------------------------------------------------
 static size_t spatial_size(const pk_ctx* ctx) { return ctx->host.spatial_dtype == PK_F32 ? 4 : 8; }
-// Every per-column operation below derives from the table at the top of this file (PK_COLUMNS).  The column pointers of a descriptor or of a device column set, in table order: named columns, then the extras
-template <class S>
-static std::array<void*, PK_NCOLS> column_pointers(const S& s) {
-    std::array<void*, PK_NCOLS> p{};
-    int k = 0;
-#define X(m, bit, elem, per_grid, optional) p[k++] = s.m;
-    PK_COLUMNS(X)
-#undef X
-    for (int e = 0; e < PK_MAX_EXTRA; e++) p[k++] = s.extra[e];
-    return p;
-}
-// ... and the way back: every column member of `s` <- p[0 .. n_cols), n_cols = PK_COL_EXTRA_FIRST (named columns only) or PK_NCOLS
-template <class S>
-static void set_column_pointers(S& s, void* const* p, int n_cols) {
-    int k = 0;
-#define X(m, bit, elem, per_grid, optional) s.m = static_cast<decltype(s.m)>(p[k++]);
-    PK_COLUMNS(X)
-#undef X
-    for (; k < n_cols; k++) s.extra[k - PK_COL_EXTRA_FIRST] = p[k];
-}
-
-// one column: host array, device column, alt/staging device column; launch_output: an advection launch writes it (pk_device.h: DPOut)
-struct ColRef { void *h, *d, *a; size_t elem; int width; bool launch_output; };
-static std::vector<ColRef> particle_columns(pk_ctx* ctx) {
+std::vector<ColRef> particle_columns(pk_ctx* ctx) {
     const auto h = column_pointers(ctx->host), d = column_pointers(ctx->dev), a = column_pointers(ctx->alt);
     std::vector<ColRef> cols;
     for (int k = 0; k < PK_COL_EXTRA_FIRST; k++) {
@@ -1436,11 +1077,11 @@ static void swap_columns(pk_ctx* ctx, bool launch_outputs_only) {
     std::swap(d.iter, a.iter);
     if (!launch_outputs_only) ctx->rerun_valid = false;  // the second set no longer holds the state before the last launch
 }
-static void swap_column_sets(pk_ctx* ctx) { swap_columns(ctx, false); }    // after the cell sort and the compaction wrote the new order into `alt`
+void swap_column_sets(pk_ctx* ctx) { swap_columns(ctx, false); }    // after the cell sort and the compaction wrote the new order into `alt`
 static void swap_launch_outputs(pk_ctx* ctx) { swap_columns(ctx, true); }  // the launch read `dev` and wrote `alt`
 
 // second column set + permutation buffers, allocated on first use (only when cell sorting is requested)
-static int32_t ensure_alt(pk_ctx* ctx) {
+int32_t ensure_alt(pk_ctx* ctx) {
     if (ctx->alt.t) return 0;
     const int64_t cap = ctx->capacity;
     const int32_t rc = alloc_column_set(ctx, ctx->alt, cap);
@@ -1454,7 +1095,7 @@ static int32_t ensure_alt(pk_ctx* ctx) {
     return 0;
 }
 
-// The row kernels (pk_kernels.h, pk_select.inc) are templates on the unsigned integer of the column's element size and take
+// The row kernels (above, and select_rows_kernel of the write filter) are templates on the unsigned integer of the column's element size and take
 // (const T* src, T* dst, ...): launch the instantiation that fits `elem`, one lane per row, on the compute stream.
 #define PK_LAUNCH_ROWS(ctx, kernel, elem, n, src, dst, ...)                                                                                            \
     do {                                                                                                                                               \
@@ -1478,7 +1119,7 @@ static int32_t sort_particles(pk_ctx* ctx, int main_grid, int horizontal_major) 
     if (rc) return rc;
     const DGrid& g = ctx->grids[main_grid].d;
     const dim3 grid((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(sort_key_kernel, grid, dim3(256), 0, ctx->compute, g, ctx->dev, ctx->d_keys, ctx->d_idx, horizontal_major);
+    sort_keys(ctx, g, horizontal_major);
     PK_HIP(ctx, hipGetLastError());
     unsigned long long kmax;
     const unsigned long long nzc = (g.has_z && g.nz >= 2) ? (unsigned long long)g.nz : 1ull;
@@ -1521,7 +1162,7 @@ static int32_t copy_particles(pk_ctx* ctx, bool to_device, uint32_t mask = 0xFFF
         if (to_device) {
             PK_HIP(ctx, hipMemcpyAsync(c.d, c.h, bytes, hipMemcpyHostToDevice, ctx->compute));
         } else if (ctx->has_perm) {  // undo the cell sort: host row perm[i] <- device row i
-            PK_LAUNCH_ROWS(ctx, scatter_rows_kernel, c.elem, n, c.d, c.a, ctx->d_perm, n, c.width);
+            scatter_rows(ctx, c, c.a, n);
             PK_HIP(ctx, hipMemcpyAsync(c.h, c.a, bytes, hipMemcpyDeviceToHost, ctx->compute));
         } else {
             PK_HIP(ctx, hipMemcpyAsync(c.h, c.d, bytes, hipMemcpyDeviceToHost, ctx->compute));
@@ -1531,7 +1172,98 @@ static int32_t copy_particles(pk_ctx* ctx, bool to_device, uint32_t mask = 0xFFF
     return 0;
 }
 
-#include "pk_select.inc"
+// undo the cell sort for one column: dst[host row perm[i]] <- device row i of the n rows, on the compute stream (scatter_rows_kernel has
+// its one home in this unit: the D2H copy, the snapshot and pk_interact_host_order of pk_api_analysis.hip all come through here)
+void scatter_rows(pk_ctx* ctx, const ColRef& c, void* dst, int64_t n) {
+    PK_LAUNCH_ROWS(ctx, scatter_rows_kernel, c.elem, n, c.d, dst, ctx->d_perm, n, c.width);
+}
+
+}  // namespace pkapi
+
+// ---- write filter ----------------------------------------------------------------------------------------
+// The write filter of ParticleFile (particlefile.py:198-221: `|t_p - t| <= |dt|/2`, finite t) on the DEVICE rows, and the
+// packing of the rows that pass it in HOST row order (whatever the cell sort did to the device order).  Two callers: the filtered snapshot of
+// the asynchronous write-out (pk_particles_snapshot_filtered: only the rows a table holds cross PCIe, and the writer thread has nothing to
+// filter) and the multi-GPU exchange (pk_api_comm.hip: through pk_api_ctx.h).
+namespace pk {
+
+// flag[host row] = the device row passes the filter (apply = 0: every row)
+__global__ void write_filter_kernel(const double* __restrict__ tp, const double* __restrict__ dt, const int64_t* __restrict__ perm, int64_t n,
+                                    double t, int apply, uint32_t* __restrict__ flag) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t f = 1u;
+    if (apply) {
+        const double p = tp[i], d = dt[i];
+        const double h = fabs(d / 2);
+        const bool sel = ((t - h <= p) && (t + h >= p)) || (d != d && p == t);
+        f = (sel && isfinite(p)) ? 1u : 0u;
+    }
+    flag[perm ? perm[i] : i] = f;
+}
+// dst[offs[host row]] = src[device row] for the flagged rows: the selected rows in host row order, packed
+template <class T>
+__global__ void select_rows_kernel(const T* __restrict__ src, T* __restrict__ dst, const int64_t* __restrict__ perm, const uint32_t* __restrict__ flag,
+                                   const uint32_t* __restrict__ offs, int64_t n, int width) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t h = perm ? perm[i] : i;
+    if (!flag[h]) return;
+    const int64_t o = (int64_t)offs[h];
+    for (int w = 0; w < width; w++) dst[o * width + w] = src[i * width + w];
+}
+
+}  // namespace pk
+
+namespace pkapi {
+
+// flags + exclusive scan of the bound device rows at output time t; -> the number of selected rows (one small read-back)
+int32_t select_flags(pk_ctx* ctx, double t, int apply_filter, int64_t* n_sel) {
+    using namespace pk;
+    PkSelect& S = ctx->sel;
+    const int64_t n = ctx->dev.n;
+    *n_sel = 0;
+    if (n >= (1ll << 31)) return ctx->fail("the device write filter supports < 2^31 particles per device");
+    if (n == 0) return 0;
+    if (S.cap < n) {
+        if (S.d_flag) PK_HIP(ctx, hipFree(S.d_flag));
+        if (S.d_offs) PK_HIP(ctx, hipFree(S.d_offs));
+        S.d_flag = S.d_offs = nullptr;
+        S.cap = 0;
+        PK_HIP(ctx, hipMalloc((void**)&S.d_flag, sizeof(uint32_t) * (size_t)n));
+        PK_HIP(ctx, hipMalloc((void**)&S.d_offs, sizeof(uint32_t) * (size_t)n));
+        S.cap = n;
+    }
+    const int64_t* perm = ctx->has_perm ? ctx->d_perm : nullptr;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(write_filter_kernel, grid, dim3(256), 0, ctx->compute, (const double*)ctx->dev.t, (const double*)ctx->dev.dt, perm, n, t,
+                       apply_filter, S.d_flag);
+    PK_HIP(ctx, hipGetLastError());
+    size_t tmp = 0;
+    PK_HIP(ctx, rocprim::exclusive_scan(nullptr, tmp, S.d_flag, S.d_offs, 0u, (size_t)n, rocprim::plus<uint32_t>(), ctx->compute));
+    if (S.tmp_bytes < tmp || !S.d_tmp) {
+        if (S.d_tmp) PK_HIP(ctx, hipFree(S.d_tmp));
+        S.d_tmp = nullptr;
+        PK_HIP(ctx, hipMalloc(&S.d_tmp, std::max<size_t>(tmp, 256)));
+        S.tmp_bytes = std::max<size_t>(tmp, 256);
+    }
+    PK_HIP(ctx, rocprim::exclusive_scan(S.d_tmp, tmp, S.d_flag, S.d_offs, 0u, (size_t)n, rocprim::plus<uint32_t>(), ctx->compute));
+    uint32_t last[2] = {0, 0};
+    PK_HIP(ctx, hipMemcpyAsync(&last[0], S.d_offs + (n - 1), 4, hipMemcpyDeviceToHost, ctx->compute));
+    PK_HIP(ctx, hipMemcpyAsync(&last[1], S.d_flag + (n - 1), 4, hipMemcpyDeviceToHost, ctx->compute));
+    PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
+    *n_sel = (int64_t)last[0] + (int64_t)last[1];
+    return 0;
+}
+// the selected rows of one column into `dst` (room for them: the caller's business), on the compute stream
+void select_column(pk_ctx* ctx, const ColRef& c, void* dst) {
+    using namespace pk;
+    const int64_t n = ctx->dev.n;
+    const int64_t* perm = ctx->has_perm ? ctx->d_perm : nullptr;
+    PK_LAUNCH_ROWS(ctx, select_rows_kernel, c.elem, n, c.d, dst, perm, ctx->sel.d_flag, ctx->sel.d_offs, n, c.width);
+}
+
+}  // namespace pkapi
 
 extern "C" {
 
@@ -1740,7 +1472,7 @@ static int32_t snapshot_begin(pk_ctx* ctx, uint32_t mask, int32_t slot, bool fil
 int32_t pk_particles_snapshot_begin(pk_ctx* ctx, uint32_t mask, int32_t slot) { return snapshot_begin(ctx, mask, slot, false, 0.0); }
 int32_t pk_particles_snapshot_filtered(pk_ctx* ctx, uint32_t mask, int32_t slot, double t) { return snapshot_begin(ctx, mask, slot, true, t); }
 }  // extern "C"
-// filtered: only the rows that pass the write filter of particlefile.py:198-221 at output time t_out, packed in host row order (pk_select.inc)
+// filtered: only the rows that pass the write filter of particlefile.py:198-221 at output time t_out, packed in host row order (select_flags)
 static int32_t snapshot_begin(pk_ctx* ctx, uint32_t mask, int32_t slot, bool filtered, double t_out) {
     if (!ctx) return -2;
     if (slot < 0 || slot > 1) return ctx->fail("snapshot slot must be 0 or 1");
@@ -1797,7 +1529,7 @@ static int32_t snapshot_begin(pk_ctx* ctx, uint32_t mask, int32_t slot, bool fil
             if (!((mask >> k) & 1u) || !c.d) continue;
             const size_t bytes = (size_t)n * c.elem * c.width;
             if (ctx->has_perm) {  // undo the cell sort: host row perm[i] <- device row i
-                PK_LAUNCH_ROWS(ctx, scatter_rows_kernel, c.elem, n, c.d, sn.dev[k], ctx->d_perm, n, c.width);
+                scatter_rows(ctx, c, sn.dev[k], n);
             } else {
                 PK_HIP(ctx, hipMemcpyAsync(sn.dev[k], c.d, bytes, hipMemcpyDeviceToDevice, ctx->compute));
             }
@@ -1907,6 +1639,10 @@ int32_t pk_particles_compact(pk_ctx* ctx, const pk_particles_desc* new_host, int
     return 0;
 }
 
+}  // extern "C" (the planner's helpers: C++ linkage, some are called from pk_api_sample.hip)
+
+namespace pkapi {
+
 // ---- execution -----------------------------------------------------------------------------------------
 // pk_exec_stats.program of a launch that runs a dedicated kernel (other launches report their PROG_*, pk_kernels.h)
 enum { PROGRAM_FAST_AGRID = 100, PROGRAM_FAST_CGRID = 101 };
@@ -1916,14 +1652,14 @@ enum Dedicated { DEDICATED_NONE = 0, DEDICATED_A2 = 1, DEDICATED_A3 = 2, DEDICAT
 
 // Some grid stores a coordinate as float32: NumPy's float32 arithmetic on coordinate / barycentric arrays has to be reproduced
 // (pk_device.h: TYPED), which only the PROG_TYPED program and the typed sampling kernels carry.
-static bool ctx_is_typed(const pk_ctx* ctx) {
+bool ctx_is_typed(const pk_ctx* ctx) {
     for (const HostGrid& g : ctx->grids)
         if (g.d.lon_f32 || g.d.lat_f32 || g.d.depth_f32) return true;
     return false;
 }
 
 // some grid of the context is a UxGrid (pk_ugrid_create)
-static bool ctx_has_ugrid(const pk_ctx* ctx) {
+bool ctx_has_ugrid(const pk_ctx* ctx) {
     for (const HostGrid& g : ctx->grids)
         if (g.d.kind == PK_UX_KIND) return true;
     return false;
@@ -1943,7 +1679,7 @@ static int32_t sigma_key(const pk_ctx* ctx, const pk_exec_params* prm, const KAr
 // The launch arguments of `prm` apart from the descriptor tables (upload_descriptors): main field and grid, resident time window, LDS layout.
 // planning: the arguments are wanted to name the program variant only (pk_generic_variant, asked before the first window of a streamed
 // fieldset is committed): a ring without a resident level is no error then.
-static int32_t launch_args(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, size_t& lds_bytes, int& use_lds, bool planning = false) {
+int32_t launch_args(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, size_t& lds_bytes, int& use_lds, bool planning) {
     memset(&a, 0, sizeof(a));
     a.p = ctx->dev;
     a.prm = *prm;
@@ -2017,7 +1753,7 @@ static int32_t launch_args(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, siz
 
 // Descriptor tables: [grids][fields] in one device buffer, refreshed on the compute stream when anything changed since the last launch (ring
 // slots move with every streamed level).  In stream order, so a kernel still running keeps reading the old values.
-static int32_t upload_descriptors(pk_ctx* ctx, KArgs& a) {
+int32_t upload_descriptors(pk_ctx* ctx, KArgs& a) {
     const size_t gb = ctx->grids.size() * sizeof(DGrid), fb = ctx->fields.size() * sizeof(DField);
     const size_t need = gb + fb;
     if (need > ctx->desc_bytes) {
@@ -2564,6 +2300,10 @@ static void launch_general(int prog, int field_f32, int curv, const pk_exec_para
     }
 }
 
+}  // namespace pkapi
+
+extern "C" {
+
 int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
     if (!ctx || !prm) return -2;
     if (!ctx->bound) return ctx->fail("no particles bound");
@@ -2897,196 +2637,6 @@ int32_t pk_execute(pk_ctx* ctx, const pk_exec_params* prm, pk_exec_stats* stats)
     return pk_execute_end(ctx, stats);
 }
 
-// ---- sampling ------------------------------------------------------------------------------------------
-// pk_eval (ei == nullptr) and pk_eval_attached (ei: the particles' `ei` on the sampled field's grid, in / out; have_guess: np.any(ei))
-static int32_t eval_points(pk_ctx* ctx, const pk_exec_params* prm, int32_t what, int64_t m, const double* t, const double* z, const double* y,
-                           const double* x, int32_t* ei, int32_t have_guess, double* out_u, double* out_v, double* out_w, int32_t* out_state) {
-    if (!ctx || !prm || !t || !z || !y || !x || !out_u) return -2;
-    PK_HIP(ctx, hipSetDevice(ctx->device));
-    if (m <= 0) return 0;
-    pk_exec_params p2 = *prm;
-    p2.twe_n = 0;
-    p2.reset_state = ctx->eval_points_f32 ? 1 : 0;  // read by eval_kernel as "sample points are float32 columns"
-    if (ei) p2.have_guess0 = have_guess ? 1 : 0;
-    if (what >= 0) {  // scalar sampling: the main grid is the sampled field's grid
-        if (what >= (int)ctx->fields.size()) return ctx->fail("unknown field id");
-        if (p2.fU < 0) { p2.fU = what; p2.fV = what; }
-    }
-    if (ei) {
-        const int fs_ = what >= 0 ? what : p2.fU;
-        if (what < -2 || fs_ < 0 || fs_ >= (int)ctx->fields.size() || ctx->grids[ctx->fields[fs_].d.grid].d.kind != PK_UX_KIND)
-            return ctx->fail("pk_eval_attached: the sampled field does not live on a UxGrid");
-    }
-    DParticles saved = ctx->dev;
-    const bool was_bound = ctx->bound;
-    KArgs a;
-    size_t lds_bytes;
-    int use_lds;
-    ctx->bound = true;
-    int32_t rc = launch_args(ctx, &p2, a, lds_bytes, use_lds);
-    if (!rc) rc = upload_descriptors(ctx, a);
-    ctx->bound = was_bound;
-    ctx->dev = saved;
-    if (rc) return rc;
-    a.win_lo = -INFINITY;
-    a.win_hi = INFINITY;
-    double* d = nullptr;
-    int32_t* ds = nullptr;
-    PK_HIP(ctx, hipMalloc((void**)&d, sizeof(double) * m * 7));
-    PK_HIP(ctx, hipMalloc((void**)&ds, sizeof(int32_t) * m * (ei ? 2 : 1)));
-    int32_t* de = nullptr;  // attached samples only: the second half of ds
-    if (ei) {
-        de = ds + m;
-        PK_HIP(ctx, hipMemcpyAsync(de, ei, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->compute));
-    }
-    double *dt_ = d, *dz = d + m, *dy = d + 2 * m, *dx = d + 3 * m, *du = d + 4 * m, *dv = d + 5 * m, *dw = d + 6 * m;
-    PK_HIP(ctx, hipMemcpyAsync(dt_, t, sizeof(double) * m, hipMemcpyHostToDevice, ctx->compute));
-    PK_HIP(ctx, hipMemcpyAsync(dz, z, sizeof(double) * m, hipMemcpyHostToDevice, ctx->compute));
-    PK_HIP(ctx, hipMemcpyAsync(dy, y, sizeof(double) * m, hipMemcpyHostToDevice, ctx->compute));
-    PK_HIP(ctx, hipMemcpyAsync(dx, x, sizeof(double) * m, hipMemcpyHostToDevice, ctx->compute));
-    const dim3 grid((unsigned)((m + 255) / 256));
-    const int fsel = what >= 0 ? what : p2.fU;
-    const bool f32 = ctx->fields[fsel].d.dtype == PK_F32;
-    const bool ux = ctx_has_ugrid(ctx);
-    if (!ux && ((what >= 0 && ctx->fields[fsel].d.is_const == 4) || (what < 0 && p2.interp_uv >= 2))) {  // batch-global lenT / lenZ
-        unsigned* dflags = (unsigned*)ds;  // reused as the state output afterwards
-        PK_HIP(ctx, hipMemsetAsync(dflags, 0, sizeof(unsigned), ctx->compute));
-        hipLaunchKernelGGL(batch_len_kernel, grid, dim3(256), 0, ctx->compute, ctx->fields[fsel].d, ctx->grids[ctx->fields[fsel].d.grid].d, m, dt_, dz, dflags);
-        unsigned hflags = 0;
-        PK_HIP(ctx, hipMemcpyAsync(&hflags, dflags, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->compute));
-        PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
-        a.prm.force_lent = (hflags & 1u) ? 2 : 1;
-        a.prm.force_lenz = (hflags & 2u) ? 2 : 1;
-    }
-    const bool typed = ctx_is_typed(ctx);
-    if (ux) {
-        const int eg = ctx->fields[what >= 0 ? what : p2.fU].d.grid;
-        if (ctx->grids[eg].d.kind != PK_UX_KIND && what < 0) return ctx->fail("a vector field next to a UxGrid must live on the UxGrid");
-        if (ei) launch_ux_eval_attached(a, what, m, dt_, dz, dy, dx, de, du, dv, dw, ds, ctx->compute);
-        else launch_ux_eval(a, what, m, dt_, dz, dy, dx, du, dv, dw, ds, ctx->compute);
-    } else {
-#define PK_EVAL(FT, IN, TY) hipLaunchKernelGGL((eval_kernel<FT, IN, TY>), grid, dim3(256), 0, ctx->compute, a, what, m, dt_, dz, dy, dx, du, dv, dw, ds)
-#define PK_EVAL_T(FT, IN) do { if (typed) PK_EVAL(FT, IN, true); else PK_EVAL(FT, IN, false); } while (0)
-    const int ik = p2.interp_uv >= 2 ? 2 : p2.interp_uv;
-    if (f32) {
-        if (ik == 2) PK_EVAL_T(float, 2); else if (ik == 1) PK_EVAL_T(float, 1); else PK_EVAL_T(float, 0);
-    } else {
-        if (ik == 2) PK_EVAL_T(double, 2); else if (ik == 1) PK_EVAL_T(double, 1); else PK_EVAL_T(double, 0);
-    }
-#undef PK_EVAL_T
-#undef PK_EVAL
-    }
-    PK_HIP(ctx, hipGetLastError());
-    PK_HIP(ctx, hipMemcpyAsync(out_u, du, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->compute));
-    if (out_v) PK_HIP(ctx, hipMemcpyAsync(out_v, dv, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->compute));
-    if (out_w) PK_HIP(ctx, hipMemcpyAsync(out_w, dw, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->compute));
-    if (out_state) PK_HIP(ctx, hipMemcpyAsync(out_state, ds, sizeof(int32_t) * m, hipMemcpyDeviceToHost, ctx->compute));
-    if (ei) PK_HIP(ctx, hipMemcpyAsync(ei, de, sizeof(int32_t) * m, hipMemcpyDeviceToHost, ctx->compute));
-    PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
-    PK_HIP(ctx, hipFree(d));
-    PK_HIP(ctx, hipFree(ds));
-    return 0;
-}
-
-int32_t pk_eval(pk_ctx* ctx, const pk_exec_params* prm, int32_t what, int64_t m, const double* t, const double* z,
-                const double* y, const double* x, double* out_u, double* out_v, double* out_w, int32_t* out_state) {
-    return eval_points(ctx, prm, what, m, t, z, y, x, nullptr, 0, out_u, out_v, out_w, out_state);
-}
-
-int32_t pk_eval_attached(pk_ctx* ctx, const pk_exec_params* prm, int32_t what, int32_t have_guess, int64_t m, const double* t, const double* z,
-                         const double* y, const double* x, int32_t* ei, double* out_u, double* out_v, double* out_w, int32_t* out_state) {
-    if (!ei) return -2;
-    return eval_points(ctx, prm, what, m, t, z, y, x, ei, have_guess, out_u, out_v, out_w, out_state);
-}
-
-int32_t pk_search(pk_ctx* ctx, int32_t grid_id, int64_t m, const double* z, const double* y, const double* x, int32_t* ei_out) {
-    if (!ctx || !z || !y || !x || !ei_out) return -2;
-    if (grid_id < 0 || grid_id >= (int)ctx->grids.size()) return ctx->fail("unknown grid id");
-    PK_HIP(ctx, hipSetDevice(ctx->device));
-    if (m <= 0) return 0;
-    double* d = nullptr;
-    int32_t* de = nullptr;
-    PK_HIP(ctx, hipMalloc((void**)&d, sizeof(double) * m * 3));
-    PK_HIP(ctx, hipMalloc((void**)&de, sizeof(int32_t) * m));
-    PK_HIP(ctx, hipMemcpyAsync(d, z, sizeof(double) * m, hipMemcpyHostToDevice, ctx->compute));
-    PK_HIP(ctx, hipMemcpyAsync(d + m, y, sizeof(double) * m, hipMemcpyHostToDevice, ctx->compute));
-    PK_HIP(ctx, hipMemcpyAsync(d + 2 * m, x, sizeof(double) * m, hipMemcpyHostToDevice, ctx->compute));
-    if (ctx->grids[grid_id].d.kind == PK_UX_KIND) launch_ux_search(ctx->grids[grid_id].d, m, d, d + m, d + 2 * m, de, ctx->compute);
-    else hipLaunchKernelGGL(search_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->compute, ctx->grids[grid_id].d, m, d, d + m, d + 2 * m, de);
-    PK_HIP(ctx, hipGetLastError());
-    PK_HIP(ctx, hipMemcpyAsync(ei_out, de, sizeof(int32_t) * m, hipMemcpyDeviceToHost, ctx->compute));
-    PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
-    PK_HIP(ctx, hipFree(d));
-    PK_HIP(ctx, hipFree(de));
-    return 0;
-}
-
-// ---- CROCO sigma grids (pk_sigma.h) ---------------------------------------------------------------------
-int32_t pk_set_croco(pk_ctx* ctx, int32_t field_h, int32_t field_zeta, double hc, int32_t n, const double* sigma_levels, const double* cs_w,
-                     int32_t cs_w_f32) {
-    if (!ctx || !sigma_levels || !cs_w) return -2;
-    const int nf = (int)ctx->fields.size();
-    if (field_h < 0 || field_h >= nf || field_zeta < 0 || field_zeta >= nf) return ctx->fail("pk_set_croco: h / zeta name no field");
-    if (n < 2) return ctx->fail("pk_set_croco: at least two sigma levels");
-    if ((size_t)n * 16 > 48 * 1024) return ctx->fail("pk_set_croco: too many sigma levels for the workgroup's LDS");
-    if (ctx->in_flight) return ctx->fail("pk_set_croco: a launch is in flight (call pk_execute_end)");
-    PK_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<double> pairs((size_t)n * 2);
-    for (int k = 0; k < n; k++) {
-        pairs[2 * k] = sigma_levels[k];
-        pairs[2 * k + 1] = cs_w[k];
-    }
-    PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
-    if (ctx->d_sigma) (void)hipFree(ctx->d_sigma);
-    ctx->d_sigma = nullptr;
-    ctx->has_sigma = false;
-    PK_HIP(ctx, hipMalloc((void**)&ctx->d_sigma, pairs.size() * sizeof(double)));
-    PK_HIP(ctx, hipMemcpy(ctx->d_sigma, pairs.data(), pairs.size() * sizeof(double), hipMemcpyHostToDevice));
-    ctx->sigma = SigmaA{ctx->d_sigma, n, field_h, field_zeta, cs_w_f32 ? 1 : 0, hc};
-    ctx->has_sigma = true;
-    return 0;
-}
-
-int32_t pk_sigma_croco(pk_ctx* ctx, int64_t m, const double* t, const double* z, const double* y, const double* x, double* out_sigma) {
-    if (!ctx || !t || !z || !y || !x || !out_sigma) return -2;
-    if (!ctx->has_sigma) return ctx->fail("pk_sigma_croco needs the CROCO parameters of the context (pk_set_croco)");
-    if (ctx_is_typed(ctx)) return ctx->fail("the CROCO conversion needs float64 coordinate arrays");
-    PK_HIP(ctx, hipSetDevice(ctx->device));
-    if (m <= 0) return 0;
-    pk_exec_params p2;
-    memset(&p2, 0, sizeof(p2));
-    p2.nk = 1;
-    p2.fU = p2.fV = ctx->sigma.fh;
-    p2.fW = p2.fKh_zonal = p2.fKh_meridional = -1;
-    DParticles saved = ctx->dev;
-    const bool was_bound = ctx->bound;
-    KArgs a;
-    size_t lds_bytes;
-    int use_lds;
-    ctx->bound = true;
-    int32_t rc = launch_args(ctx, &p2, a, lds_bytes, use_lds);
-    if (!rc) rc = upload_descriptors(ctx, a);
-    ctx->bound = was_bound;
-    ctx->dev = saved;
-    if (rc) return rc;
-    a.sigma = ctx->sigma;
-    double* d = nullptr;
-    PK_HIP(ctx, hipMalloc((void**)&d, sizeof(double) * m * 5));
-    hipError_t e = hipSuccess;  // (no early return between hipMalloc and hipFree)
-    const double* src[4] = {t, z, y, x};
-    for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipMemcpyAsync(d + k * m, src[k], sizeof(double) * m, hipMemcpyHostToDevice, ctx->compute);
-    if (e == hipSuccess) {
-        launch_sigma_points(a, m, d, d + m, d + 2 * m, d + 3 * m, d + 4 * m, (size_t)ctx->sigma.n * 2 * sizeof(double), ctx->compute);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_sigma, d + 4 * m, sizeof(double) * m, hipMemcpyDeviceToHost, ctx->compute);
-    const hipError_t es = hipStreamSynchronize(ctx->compute);
-    (void)hipFree(d);
-    PK_HIP(ctx, e);
-    PK_HIP(ctx, es);
-    return 0;
-}
-
 int32_t pk_measure_copy_bandwidth(pk_ctx* ctx, int64_t bytes, int32_t iters, double* gbps) {
     if (!ctx || !gbps || bytes < 16 || iters < 1) return -2;
     PK_HIP(ctx, hipSetDevice(ctx->device));
@@ -3110,312 +2660,4 @@ int32_t pk_measure_copy_bandwidth(pk_ctx* ctx, int64_t bytes, int32_t iters, dou
     return 0;
 }
 
-// ---- neighbour search (pk_neighbors.hip) ---------------------------------------------------------------
-int32_t pk_neighbors_build(pk_ctx* ctx, int64_t n, const double* x, const double* y, const double* z, const uint8_t* sources, double radius,
-                           int32_t flags) {
-    if (!ctx) return -2;
-    PK_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->nbr) ctx->nbr = neighbors_create();
-    std::string msg;
-    if (neighbors_build(ctx->nbr, ctx->compute, n, x, y, z, sources, radius, flags, &msg)) return ctx->fail(msg);
-    return 0;
-}
-
-int32_t pk_neighbors_counts(pk_ctx* ctx, int64_t* counts, int64_t* total) {
-    if (!ctx) return -2;
-    if (!ctx->nbr) return ctx->fail("pk_neighbors_counts: no cell list (pk_neighbors_build first)");
-    PK_HIP(ctx, hipSetDevice(ctx->device));
-    std::string msg;
-    if (neighbors_counts(ctx->nbr, ctx->compute, counts, total, &msg)) return ctx->fail(msg);
-    return 0;
-}
-
-int32_t pk_neighbors_nearest(pk_ctx* ctx, int64_t* j, double* dist) {
-    if (!ctx) return -2;
-    if (!ctx->nbr) return ctx->fail("pk_neighbors_nearest: no cell list (pk_neighbors_build first)");
-    PK_HIP(ctx, hipSetDevice(ctx->device));
-    std::string msg;
-    if (neighbors_nearest(ctx->nbr, ctx->compute, j, dist, &msg)) return ctx->fail(msg);
-    return 0;
-}
-
-int32_t pk_neighbors_pairs(pk_ctx* ctx, int64_t total, int64_t* starts, int64_t* j, double* dx, double* dy, double* dz, double* dist) {
-    if (!ctx) return -2;
-    if (!ctx->nbr) return ctx->fail("pk_neighbors_pairs: no cell list (pk_neighbors_build first)");
-    PK_HIP(ctx, hipSetDevice(ctx->device));
-    std::string msg;
-    if (neighbors_pairs(ctx->nbr, ctx->compute, total, starts, j, dx, dy, dz, dist, &msg)) return ctx->fail(msg);
-    return 0;
-}
-
-int32_t pk_neighbors_info(pk_ctx* ctx, pk_neighbors_info_t* out) {
-    if (!ctx || !out) return -2;
-    NeighborsInfo i;
-    neighbors_info(ctx->nbr, &i);
-    out->n = i.n;
-    out->nvalid = i.nvalid;
-    out->ncx = i.ncx;
-    out->ncy = i.ncy;
-    out->total = i.total;
-    out->cell_size = i.h;
-    out->doublings = i.doublings;
-    out->reserved0 = 0;
-    return 0;
-}
-
-int32_t pk_neighbors_build_spherical(pk_ctx* ctx, int64_t n, const double* x, const double* y, const double* z, const uint8_t* sources,
-                                     double radius_m, double sphere_radius_m, int32_t flags) {
-    if (!ctx) return -2;
-    PK_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->nbr) ctx->nbr = neighbors_create();
-    std::string msg;
-    if (neighbors_build_spherical(ctx->nbr, ctx->compute, n, x, y, z, sources, radius_m, sphere_radius_m, flags, &msg)) return ctx->fail(msg);
-    return 0;
-}
-
-int32_t pk_neighbors_info_spherical(pk_ctx* ctx, pk_neighbors_info_spherical_t* out) {
-    if (!ctx || !out) return -2;
-    NeighborsSphInfo i;
-    neighbors_info_spherical(ctx->nbr, &i);
-    out->n = i.n;
-    out->nvalid = i.nvalid;
-    out->bands = i.bands;
-    out->cells = i.cells;
-    out->total = i.total;
-    out->band_height = i.band_height;
-    out->periodic = i.periodic;
-    out->doublings = i.doublings;
-    return 0;
-}
-
-int32_t pk_neighbors_release(pk_ctx* ctx) {
-    if (!ctx) return -2;
-    if (!ctx->nbr) return 0;
-    PK_HIP(ctx, hipSetDevice(ctx->device));
-    PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
-    neighbors_release(ctx->nbr);
-    return 0;
-}
-
-// ---- built-in interaction kernels on the device-resident columns (pk_interact.hip) ------------------------
-static int32_t interact_ready(pk_ctx* ctx, const char* who, bool host_order) {
-    if (!ctx->bound) return ctx->fail(std::string(who) + ": no particles bound");
-    if (ctx->in_flight) return ctx->fail(std::string(who) + ": a launch is in flight (call pk_execute_end)");
-    if (host_order && ctx->has_perm) return ctx->fail(std::string(who) + ": the device rows are cell-sorted (pk_interact_host_order first)");
-    PK_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->nbr) ctx->nbr = neighbors_create();
-    if (!ctx->inter) ctx->inter = interact_create();
-    ctx->rerun_valid = false;  // the columns change in place
-    ctx->chk_valid = false;
-    return 0;
-}
-static InteractColumns interact_columns(const pk_ctx* ctx) {
-    const DParticles& d = ctx->dev;
-    InteractColumns c;
-    c.n = d.n;
-    c.f32 = d.spatial_f32;
-    c.t = d.t;
-    c.x = d.x; c.y = d.y; c.z = d.z;
-    c.dx = d.dx; c.dy = d.dy; c.dz = d.dz;
-    c.dt = d.dt;
-    c.state = d.state;
-    c.mask = d.iter;
-    return c;
-}
-
-int32_t pk_interact_host_order(pk_ctx* ctx) {
-    if (!ctx) return -2;
-    int32_t rc = interact_ready(ctx, "pk_interact_host_order", false);
-    if (rc) return rc;
-    const int64_t n = ctx->dev.n;
-    if (!ctx->has_perm) return 0;
-    if (n > 0) {
-        rc = ensure_alt(ctx);
-        if (rc) return rc;
-        for (const ColRef& c : particle_columns(ctx)) {  // host row perm[i] <- device row i, as pk_particles_d2h does on its way out
-            if (!c.d || !c.a) continue;
-            PK_LAUNCH_ROWS(ctx, scatter_rows_kernel, c.elem, n, c.d, c.a, ctx->d_perm, n, c.width);
-        }
-        PK_HIP(ctx, hipGetLastError());
-        PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
-        swap_column_sets(ctx);
-    }
-    ctx->has_perm = false;
-    return 0;
-}
-
-int32_t pk_interact_sources(pk_ctx* ctx, const uint8_t* sources) {
-    if (!ctx) return -2;
-    int32_t rc = interact_ready(ctx, "pk_interact_sources", false);
-    if (rc) return rc;
-    std::string msg;
-    if (neighbors_set_sources(ctx->nbr, ctx->compute, ctx->dev.n, sources, &msg)) return ctx->fail(msg);
-    return 0;
-}
-
-int32_t pk_interact_prologue(pk_ctx* ctx, double endtime, double dt0, int32_t reset_state, int32_t clip, int64_t* n_evaluated, int64_t* n_active) {
-    if (!ctx || !n_evaluated || !n_active) return -2;
-    int32_t rc = interact_ready(ctx, "pk_interact_prologue", true);
-    if (rc) return rc;
-    std::string msg;
-    if (interact_prologue(ctx->inter, ctx->compute, interact_columns(ctx), endtime, dt0, reset_state, clip, n_evaluated, n_active, &msg))
-        return ctx->fail(msg);
-    return 0;
-}
-
-int32_t pk_interact_epilogue(pk_ctx* ctx, double endtime, double dt0, int64_t* steps, int64_t* state_counts, int64_t* next_evaluated,
-                             int64_t* next_active) {
-    if (!ctx || !steps || !state_counts || !next_evaluated || !next_active) return -2;
-    int32_t rc = interact_ready(ctx, "pk_interact_epilogue", true);
-    if (rc) return rc;
-    std::string msg;
-    if (interact_epilogue(ctx->inter, ctx->compute, interact_columns(ctx), endtime, dt0, steps, state_counts, next_evaluated, next_active, &msg))
-        return ctx->fail(msg);
-    return 0;
-}
-
-int32_t pk_interact_attract(pk_ctx* ctx, double radius, double velocity, double sphere_radius_m, int32_t use_z, int32_t use_sources, int64_t max_pairs,
-                            int64_t* total, double* phase_ms) {
-    if (!ctx || !total) return -2;
-    int32_t rc = interact_ready(ctx, "pk_interact_attract", true);
-    if (rc) return rc;
-    if (!(velocity == velocity) || std::isinf(velocity)) return ctx->fail("pk_interact_attract: velocity must be finite");
-    if (max_pairs < 0) return ctx->fail("pk_interact_attract: max_pairs must not be negative");
-    std::string msg;
-    if (interact_attract(ctx->nbr, ctx->compute, interact_columns(ctx), radius, velocity, sphere_radius_m, use_z, use_sources, max_pairs, total, phase_ms,
-                         &msg))
-        return ctx->fail(msg);
-    return 0;
-}
-
-int32_t pk_interact_merge(pk_ctx* ctx, double radius, double sphere_radius_m, int32_t use_z, int32_t mass_extra, double* phase_ms) {
-    if (!ctx) return -2;
-    int32_t rc = interact_ready(ctx, "pk_interact_merge", true);
-    if (rc) return rc;
-    if (mass_extra < 0 || mass_extra >= PK_MAX_EXTRA || !ctx->dev.extra[mass_extra])
-        return ctx->fail("pk_interact_merge: mass_extra must name a device Variable of the bound particles (pk_particles_desc.extra)");
-    std::string msg;
-    if (interact_merge(ctx->nbr, ctx->compute, interact_columns(ctx), ctx->dev.extra[mass_extra], ctx->dev.extra_f32[mass_extra], radius, sphere_radius_m,
-                       use_z, phase_ms, &msg))
-        return ctx->fail(msg);
-    return 0;
-}
-
-// ---- particles per grid cell on the device-resident columns (pk_density.hip) ------------------------------
-int32_t pk_particles_density(pk_ctx* ctx, int32_t grid_id, int32_t levels, int32_t weight_kind, int32_t weight_extra, int32_t weight_dtype,
-                             const double* weights_host, int64_t ncells, void* out, int64_t* n_outside, pk_density_info_t* info) {
-    if (!ctx || !out || !n_outside) return -2;
-    if (!ctx->bound) return ctx->fail("pk_particles_density: no particles bound");
-    if (ctx->in_flight) return ctx->fail("pk_particles_density: a launch is in flight (call pk_execute_end)");
-    if (grid_id < 0 || grid_id >= (int)ctx->grids.size()) return ctx->fail("pk_particles_density: unknown grid id");
-    if (ncells <= 0) return ctx->fail("pk_particles_density: ncells must be positive");
-    DensityWeights w;
-    w.kind = weight_kind;
-    w.dtype = weight_dtype;
-    if (weight_kind == PK_DENSITY_W_EXTRA) {
-        if (weight_extra < 0 || weight_extra >= PK_MAX_EXTRA || !ctx->dev.extra[weight_extra])
-            return ctx->fail("pk_particles_density: weight_extra must name a device Variable of the bound particles (pk_particles_desc.extra)");
-        if (weight_dtype < PK_DENSITY_F32 || weight_dtype > PK_DENSITY_I64)
-            return ctx->fail("pk_particles_density: weight_dtype must be PK_DENSITY_F32, _F64, _I32 or _I64");
-        const bool four = weight_dtype == PK_DENSITY_F32 || weight_dtype == PK_DENSITY_I32;
-        if (four != (ctx->dev.extra_f32[weight_extra] != 0))
-            return ctx->fail("pk_particles_density: weight_dtype does not have the element size of the device Variable");
-        w.dev = ctx->dev.extra[weight_extra];
-    } else if (weight_kind == PK_DENSITY_W_HOST) {
-        if (!weights_host && ctx->dev.n > 0) return ctx->fail("pk_particles_density: PK_DENSITY_W_HOST needs weights_host");
-        w.host = weights_host;
-    } else if (weight_kind != PK_DENSITY_W_NONE) {
-        return ctx->fail("pk_particles_density: weight_kind must be PK_DENSITY_W_NONE, _EXTRA or _HOST");
-    }
-    PK_HIP(ctx, hipSetDevice(ctx->device));
-    const DParticles& d = ctx->dev;  // the column set that is current (a launch leaves what it wrote there)
-    DensityColumns c;
-    c.n = d.n;
-    c.f32 = d.spatial_f32;
-    c.x = d.x; c.y = d.y; c.z = d.z;
-    c.perm = ctx->has_perm ? ctx->d_perm : nullptr;
-    std::string msg;
-    if (density_run(ctx->compute, ctx->grids[grid_id].d, c, levels, w, ncells, out, n_outside, info, &msg)) return ctx->fail(msg);
-    return 0;
-}
-
-// ---- labels of the bound rows and origin-to-destination counts (pk_connectivity.hip) ------------------------
-static int32_t conn_ready(pk_ctx* ctx, const char* who, int32_t grid_id, int32_t regions_dtype, const void* regions_host, int64_t ncells) {
-    const std::string w(who);
-    if (!ctx->bound) return ctx->fail(w + ": no particles bound");
-    if (ctx->in_flight) return ctx->fail(w + ": a launch is in flight (call pk_execute_end)");
-    if (grid_id < 0 || grid_id >= (int)ctx->grids.size()) return ctx->fail(w + ": unknown grid id");
-    if (ncells <= 0) return ctx->fail(w + ": ncells must be positive");
-    if (regions_host && regions_dtype != PK_DENSITY_I32 && regions_dtype != PK_DENSITY_I64)
-        return ctx->fail(w + ": regions_dtype must be PK_DENSITY_I32 or PK_DENSITY_I64");
-    return 0;
-}
-
-static DensityColumns conn_columns(pk_ctx* ctx) {
-    const DParticles& d = ctx->dev;  // the column set that is current (a launch leaves what it wrote there)
-    DensityColumns c;
-    c.n = d.n;
-    c.f32 = d.spatial_f32;
-    c.x = d.x; c.y = d.y; c.z = d.z;
-    c.perm = ctx->has_perm ? ctx->d_perm : nullptr;
-    return c;
-}
-
-int32_t pk_particles_cells(pk_ctx* ctx, int32_t grid_id, int32_t levels, int32_t regions_dtype, const void* regions_host, int64_t ncells,
-                           int64_t* labels_out) {
-    if (!ctx) return -2;
-    if (int32_t rc = conn_ready(ctx, "pk_particles_cells", grid_id, regions_dtype, regions_host, ncells)) return rc;
-    if (!labels_out && ctx->dev.n > 0) return ctx->fail("pk_particles_cells: labels_out is NULL");
-    ConnLabels l;
-    l.regions = regions_host;
-    l.regions_dtype = regions_dtype;
-    PK_HIP(ctx, hipSetDevice(ctx->device));
-    std::string msg;
-    if (cells_run(ctx->compute, ctx->grids[grid_id].d, conn_columns(ctx), levels, l, ncells, labels_out, &msg)) return ctx->fail(msg);
-    return 0;
-}
-
-int32_t pk_particles_connectivity(pk_ctx* ctx, int32_t grid_id, int32_t levels, int32_t regions_dtype, const void* regions_host, int64_t ncells,
-                                  int32_t origin_kind, int32_t origin_extra, int32_t origin_dtype, const void* origin_host, int64_t n_origin,
-                                  int64_t n_dest, int32_t path, int64_t* dense_out, int64_t* keys_out, int64_t* counts_out, int64_t max_pairs,
-                                  pk_connectivity_info_t* info) {
-    if (!ctx || !info) return -2;
-    if (int32_t rc = conn_ready(ctx, "pk_particles_connectivity", grid_id, regions_dtype, regions_host, ncells)) return rc;
-    if (origin_dtype != PK_DENSITY_I32 && origin_dtype != PK_DENSITY_I64)
-        return ctx->fail("pk_particles_connectivity: origin_dtype must be PK_DENSITY_I32 or PK_DENSITY_I64");
-    ConnLabels l;
-    l.regions = regions_host;
-    l.regions_dtype = regions_dtype;
-    l.origin_dtype = origin_dtype;
-    l.n_origin = n_origin;
-    l.n_dest = n_dest;
-    if (origin_kind == PK_DENSITY_W_EXTRA) {
-        if (origin_extra < 0 || origin_extra >= PK_MAX_EXTRA || !ctx->dev.extra[origin_extra])
-            return ctx->fail("pk_particles_connectivity: origin_extra must name a device Variable of the bound particles (pk_particles_desc.extra)");
-        if ((origin_dtype == PK_DENSITY_I32) != (ctx->dev.extra_f32[origin_extra] != 0))
-            return ctx->fail("pk_particles_connectivity: origin_dtype does not have the element size of the device Variable");
-        l.origin_dev = ctx->dev.extra[origin_extra];
-    } else if (origin_kind == PK_DENSITY_W_HOST) {
-        if (!origin_host && ctx->dev.n > 0) return ctx->fail("pk_particles_connectivity: PK_DENSITY_W_HOST needs origin_host");
-        l.origin_host = origin_host;
-    } else {
-        return ctx->fail("pk_particles_connectivity: origin_kind must be PK_DENSITY_W_EXTRA or PK_DENSITY_W_HOST");
-    }
-    if (path == PK_CONN_SPARSE) {
-        if (max_pairs < 0 || (max_pairs > 0 && (!keys_out || !counts_out))) return ctx->fail("pk_particles_connectivity: PK_CONN_SPARSE needs keys_out and counts_out with room for max_pairs");
-    } else if (path == PK_CONN_LDS || path == PK_CONN_GLOBAL) {
-        if (!dense_out && n_origin > 0) return ctx->fail("pk_particles_connectivity: PK_CONN_LDS / PK_CONN_GLOBAL need dense_out");
-    } else {
-        return ctx->fail("pk_particles_connectivity: path must be PK_CONN_LDS, PK_CONN_GLOBAL or PK_CONN_SPARSE");
-    }
-    PK_HIP(ctx, hipSetDevice(ctx->device));
-    std::string msg;
-    if (connectivity_run(ctx->compute, ctx->grids[grid_id].d, conn_columns(ctx), levels, l, ncells, path, dense_out, keys_out, counts_out, max_pairs, info,
-                         &msg))
-        return ctx->fail(msg);
-    return 0;
-}
-
 }  // extern "C"
-
-#include "pk_comm.inc"

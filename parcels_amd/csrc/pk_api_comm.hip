@@ -1,5 +1,5 @@
-// pk_comm.inc -- the multi-GPU exchange of the path through the C ABI (pk_allgather_output; 8e): RCCL over xGMI, one
-// pk_ctx (= one process, one GPU) per rank.  Included by pk_api.hip (it works on pk_ctx's device columns, streams and row permutation).
+// pk_api_comm.hip -- the multi-GPU exchange of the path through the C ABI (pk_allgather_output; 8e): RCCL over xGMI, one
+// pk_ctx (= one process, one GPU) per rank.  It works on pk_ctx's device columns, streams and row permutation (pk_api_ctx.h).
 //
 // What is exchanged (the path has no data-path collective: particles are independent, fields replicated):
 //   * the periodic write-out: the rows that pass the reference's write filter |t_p - t| <= |dt|/2 (particlefile.py:198-221) -- applied ON THE
@@ -10,8 +10,12 @@
 // Ranks may hold different, also zero, row counts (the counts are all-gathered first; the rows travel as grouped ncclSend / ncclRecv of
 // bytes -- an all-gather-v).  Rounds 1-5 did all of this in Python over torch.distributed (parcels_amd/distributed.py); that module is now a
 // thin caller of these entry points whenever the process group is RCCL, and keeps its torch path for gloo (the N > 1 CPU tests).
+#include "pk_api_ctx.h"
+
 #include <dlfcn.h>
 #include <rccl/rccl.h>
+
+using namespace pkapi;
 
 namespace {
 
@@ -82,7 +86,7 @@ bool rccl_load() {
 struct PkComm {
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;
-    // device staging: this rank's selected rows (pk_select.inc) and the gathered rows, per column
+    // device staging: this rank's selected rows (pk_api.hip: select_column) and the gathered rows, per column
     void* d_sel[PK_NCOLS] = {};
     size_t sel_bytes[PK_NCOLS] = {};
     void* d_all[PK_NCOLS] = {};
@@ -114,7 +118,7 @@ static int32_t comm_grow(pk_ctx* ctx, void** p, size_t* have, size_t need) {
     return 0;
 }
 
-// The selected rows of the masked columns, packed in host row order in PkComm::d_sel (pk_select.inc); -> their number
+// The selected rows of the masked columns, packed in host row order in PkComm::d_sel (pk_api.hip: select_flags, select_column); -> their number
 static int32_t comm_select(pk_ctx* ctx, PkComm& cm, double t, int apply_filter, uint32_t mask, int64_t* n_sel) {
     const std::vector<ColRef> cols = particle_columns(ctx);
     cm.mask = 0;

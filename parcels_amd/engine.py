@@ -625,7 +625,7 @@ class DeviceEngine:
             else:
                 b._stale -= set(columns)
 
-    # ---- the multi-GPU exchange through the C ABI (csrc/pk_comm.inc: RCCL opened by the library) -------------------
+    # ---- the multi-GPU exchange through the C ABI (csrc/pk_api_comm.hip: RCCL opened by the library) -------------------
     def comm_init(self, rank: int, world: int, unique_id: bytes):
         """pk_comm_init: this engine's context joins a communicator of `world` ranks (the 128-byte id: comm_unique_id() of one rank)."""
         buf = (C.c_uint8 * _hip.PK_COMM_ID_BYTES).from_buffer_copy(bytes(unique_id))

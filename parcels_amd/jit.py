@@ -1297,9 +1297,10 @@ extern "C" void pk_user_launch(const void* kargs, int32_t prog, int32_t key, int
 
 
 def _csrc_hash() -> str:
+    # (not the host side of the ABI, csrc/pk_api_*: no user module includes it, and a host edit must not invalidate every cached module)
     h = hashlib.sha256()
     for f in sorted(os.listdir(_CSRC)):
-        if f.endswith((".h", ".hip")) and f not in ("pk_api.hip",):
+        if f.endswith((".h", ".hip")) and not f.startswith("pk_api"):
             h.update(open(os.path.join(_CSRC, f), "rb").read())
     h.update(open(os.path.join(_INCLUDE, "parcels_hip.h"), "rb").read())
     return h.hexdigest()[:16]

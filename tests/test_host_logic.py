@@ -26,6 +26,49 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert lib.pk_abi_version() == _hip.PK_ABI_VERSION == 9
 
 
+def test_host_units_are_listed_and_define_every_entry_point_once(monkeypatch):
+    """The host side of the ABI is one csrc/pk_api_*.hip unit per subsystem: both build lists name each of them (and no unit that is not
+    there), every function include/parcels_hip.h declares is defined in exactly one .hip file, and the hash that keys the cached user
+    modules reads none of them."""
+    csrc = os.path.join(ROOT, "parcels_amd", "csrc")
+    units = sorted(f[:-4] for f in os.listdir(csrc) if f.startswith("pk_api") and f.endswith(".hip"))
+    assert units, "no csrc/pk_api*.hip"
+    makefile = open(os.path.join(csrc, "Makefile")).read()
+    objs = re.search(r"^OBJS\s*=\s*(.*)$", makefile, re.M).group(1).split()
+    assert sorted(o[:-2] for o in objs if o.startswith("pk_api")) == units
+    # the pattern rule rebuilds every unit when the shared host header changes, and names no file that is gone
+    prereqs = re.search(r"^%\.o: %\.hip (.*)$", makefile, re.M).group(1).split()
+    assert "pk_api_ctx.h" in prereqs
+    assert [p for p in prereqs if not os.path.exists(os.path.join(csrc, p))] == []
+    assert [f for f in os.listdir(csrc) if f.endswith(".inc")] == []  # no unit is textually included into another
+    variant = open(os.path.join(ROOT, "tools", "build_variant.sh")).read()
+    listed = re.search(r"^for o in (.*); do$", variant, re.M).group(1).split()
+    assert sorted(o for o in listed if o.startswith("pk_api")) == units
+    assert sorted(o[:-2] for o in objs) == sorted(listed)  # the two lists name the same objects
+
+    header = open(os.path.join(ROOT, "include", "parcels_hip.h")).read()
+    declared = sorted(set(re.findall(r"\b(pk_[a-z0-9_]+)\s*\(", header)))
+    defined = {}
+    for f in sorted(os.listdir(csrc)):  # (.cpp: pk_host_stage_selftest lives in the host-only unit, behind `extern "C"` on its own line)
+        if f.endswith((".hip", ".cpp")):
+            for name in re.findall(r"^(?:extern \"C\" )?(?:int32_t|const char\*) (pk_[a-z0-9_]+)\(", open(os.path.join(csrc, f)).read(), re.M):
+                defined.setdefault(name, []).append(f)
+    assert {n: defined.get(n, []) for n in declared if len(defined.get(n, [])) != 1} == {}
+
+    from parcels_amd import jit
+
+    read = []
+
+    def recording_open(path, *a, **k):
+        read.append(os.path.basename(path))
+        return open(path, *a, **k)
+
+    monkeypatch.setattr(jit, "open", recording_open, raising=False)
+    jit._csrc_hash()
+    assert "pk_device.h" in read and "parcels_hip.h" in read
+    assert [f for f in read if f.startswith("pk_api")] == []
+
+
 def test_ctypes_structs_match_header_layout(tmp_path):
     """sizeof() of every struct of include/parcels_hip.h as gcc lays it out == the ctypes mirror in parcels_amd/_hip.py."""
     import subprocess

@@ -107,7 +107,7 @@ def test_info_struct_matches_the_header_layout(tmp_path):
 def test_the_spherical_code_is_in_the_listed_object():
     """No new object: the spherical kernels live in pk_neighbors.hip, which both build lists already name."""
     csrc = os.path.join(ROOT, "parcels_amd", "csrc")
-    assert "pk_neighbors_build_spherical" in open(os.path.join(csrc, "pk_api.hip")).read()
+    assert "pk_neighbors_build_spherical" in open(os.path.join(csrc, "pk_api_analysis.hip")).read()
     assert "neighbors_build_spherical" in open(os.path.join(csrc, "pk_neighbors.hip")).read()
     assert not os.path.exists(os.path.join(csrc, "pk_neighbors_sph.hip"))
     assert "pk_neighbors.o" in open(os.path.join(csrc, "Makefile")).read()

@@ -1,9 +1,11 @@
 #!/usr/bin/env python
 """Which kernels of two builds of a translation unit have other INSTRUCTIONS (an object-code diff beside tools/kernel_code_hash.py).
 
-    python tools/kernel_code_diff.py OLD.o NEW.o
+    python tools/kernel_code_diff.py OLD.o NEW.o [NEW2.o ...]
 
-Disassembles the gfx950 code object of both host objects and compares every function instruction by instruction.  A kernel that only moved
+Disassembles the gfx950 code object of the host objects and compares every function instruction by instruction.  Several NEW objects are one
+translation unit split up: their functions are taken together, a function that two of them hold with the same code (a linkonce copy) counts
+once, and one they hold with different code is `CHANGED`.  A kernel that only moved
 inside .text differs in the bytes of its pc-relative displacements -- the two literals behind an `s_getpc_b64` that form the address of a
 called function -- and in nothing else: those literals are masked, so such a kernel counts as unchanged and is reported as `moved`.
 A kernel whose instructions differ, but which has the same NUMBER of instructions, the same multiset of mnemonics and the same resources
@@ -74,14 +76,36 @@ def functions(obj, tmp):
             exact = ins
         out[name][0].append(ins)
         out[name][1].append(exact)
+    # the fill behind a function's last instruction (up to the next function's alignment, or the end of .text) belongs to where the function
+    # lies, not to the function: a unit that was split up lays its functions out anew
+    # -- cut only behind an instruction that ends the function (no fall-through into the fill), and only what is fill
+    fill = ("s_nop 0", "s_code_end", "...")  # ("...": the disassembler's run of zero bytes)
+    for masked, exact, _ in out.values():
+        n = len(masked)
+        while n and masked[n - 1] in fill:
+            n -= 1
+        if n and masked[n - 1].split(" ")[0] in ("s_endpgm", "s_setpc_b64", "s_branch"):
+            del masked[n:], exact[n:]
     return out
 
 
 def main():
-    old, new = sys.argv[1], sys.argv[2]
-    with tempfile.TemporaryDirectory() as t1, tempfile.TemporaryDirectory() as t2:
-        fa, fb = functions(old, t1), functions(new, t2)
+    old, news = sys.argv[1], sys.argv[2:]
     changed = 0
+    with tempfile.TemporaryDirectory() as t1:
+        fa = functions(old, t1)
+    fb = {}
+    for new in news:  # the functions of all NEW objects together: identical linkonce copies count once
+        with tempfile.TemporaryDirectory() as t2:
+            sections = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "-SW", new], check=True, capture_output=True, text=True).stdout
+            if ".hip_fatbin" not in sections:  # a host-only part of the split unit
+                print("no device code:", new)
+                continue
+            for n, f in functions(new, t2).items():
+                if n in fb and (fb[n][0], fb[n][2]) != (f[0], f[2]):
+                    print(f"CHANGED {n}: two NEW objects hold it with different code ({len(fb[n][0])} and {len(f[0])} instructions)")
+                    changed += 1
+                fb.setdefault(n, f)
     for n in sorted(set(fa) | set(fb)):
         a, b = fa.get(n), fb.get(n)
         if a is None or b is None:
