@@ -302,5 +302,9 @@ int32_t upload_descriptors(pk_ctx* ctx, KArgs& a);
 // pk_api_sample.hip
 void sort_keys(pk_ctx* ctx, const DGrid& g, int horizontal_major);
 
+// pk_prog_eval_attached.hip: the sampler of pk_eval_attached on structured grids (ik: 0 XLinear_Velocity / scalar, 1 CGrid_Velocity, 2 slip)
+void launch_eval_attached(bool f32, int ik, bool typed, const KArgs& a, int what, int64_t m, const double* t, const double* z, const double* y,
+                          const double* x, int32_t* ei, double* ou, double* ov, double* ow, int32_t* ost, hipStream_t stream);
+
 }  // namespace pkapi
 #pragma GCC visibility pop

@@ -131,8 +131,9 @@ static int32_t eval_points(pk_ctx* ctx, const pk_exec_params* prm, int32_t what,
     }
     if (ei) {
         const int fs_ = what >= 0 ? what : p2.fU;
-        if (what < -2 || fs_ < 0 || fs_ >= (int)ctx->fields.size() || ctx->grids[ctx->fields[fs_].d.grid].d.kind != PK_UX_KIND)
-            return ctx->fail("pk_eval_attached: the sampled field does not live on a UxGrid");
+        if (what < -2 || fs_ < 0 || fs_ >= (int)ctx->fields.size()) return ctx->fail("pk_eval_attached: unknown field");
+        if (ctx_has_ugrid(ctx) && ctx->grids[ctx->fields[fs_].d.grid].d.kind != PK_UX_KIND)
+            return ctx->fail("pk_eval_attached: next to a UxGrid only fields on the UxGrid are sampled with the particles");
     }
     DParticles saved = ctx->dev;
     const bool was_bound = ctx->bound;
@@ -185,7 +186,8 @@ static int32_t eval_points(pk_ctx* ctx, const pk_exec_params* prm, int32_t what,
 #define PK_EVAL(FT, IN, TY) hipLaunchKernelGGL((eval_kernel<FT, IN, TY>), grid, dim3(256), 0, ctx->compute, a, what, m, dt_, dz, dy, dx, du, dv, dw, ds)
 #define PK_EVAL_T(FT, IN) do { if (typed) PK_EVAL(FT, IN, true); else PK_EVAL(FT, IN, false); } while (0)
     const int ik = p2.interp_uv >= 2 ? 2 : p2.interp_uv;
-    if (f32) {
+    if (ei) launch_eval_attached(f32, ik, typed, a, what, m, dt_, dz, dy, dx, de, du, dv, dw, ds, ctx->compute);
+    else if (f32) {
         if (ik == 2) PK_EVAL_T(float, 2); else if (ik == 1) PK_EVAL_T(float, 1); else PK_EVAL_T(float, 0);
     } else {
         if (ik == 2) PK_EVAL_T(double, 2); else if (ik == 1) PK_EVAL_T(double, 1); else PK_EVAL_T(double, 0);

@@ -1761,6 +1761,83 @@ PK_DEV double eval_scalar(const KArgs& a, const Coords& mc, PCtx& c, int fidx, d
     return finish_value(c, p, v);
 }
 
+#ifdef PK_USER_VECTORS
+// VectorField.eval (field.py:250-304) for a NAMED vector field -- wind, Stokes drift, a displacement field: any VectorField that is not the
+// launch's velocity -- sampled by a translated user kernel (parcels_amd/jit.py: RQ_VEC).  The generated module calls it from its dispatch
+// function with the component field ids, the device dtype of the components (FT), the kind of their grid (KIND: 0 rectilinear, 1
+// curvilinear) and the interpolator (INTERP as in eval_uvw; interp_uv tells XFreeslip from XPartialslip) of each vector it samples.  The
+// arithmetic is eval_uvw's.  The vector is related to the launch like a scalar field in eval_scalar: only on the main grid does the search
+// read the staged coordinate tables and share the main grid's hints (that search sets the particle's `ei` there, which the hints mirror),
+// and only with the main field's own time array the staged time table; c.ht is the velocity's and stays.  The lane's cache of staggered
+// C-grid values holds the launch's U, V, W: never used here.  (Float32 coordinate arrays -- TYPED -- keep the host path.)
+template <class FT, int KIND, int INTERP>
+PK_DEV void eval_vec(const KArgs& a, const Coords& mc, PCtx& c, int fU, int fV, int fW, int interp_uv, bool want_w, double t, double z,
+                     double y, double x, bool pos_f32, double& u, double& v, double& w) {
+    const DField& U = kfield(a, fU);
+    const DField& V = kfield(a, fV);
+    const DGrid& g = kgrid(a, U.grid);
+    const bool on_main = U.grid == a.main_grid;
+    const double* time = (on_main && U.time == kfield(a, a.main_field).time) ? mc.time : U.time;
+    GPos p;
+    u = v = w = 0.0;
+    c.u32 = c.v32 = false;
+    const int klo = c.klo++;
+    if (U.has_time_interval) {
+        const int li = twe_listed_index(a, c.it, klo);
+        if (li >= 0) {  // (see eval_uvw)
+            twe_justify(a, li, t, U.tlen);
+            c.state = PK_ERROROUTSIDETIMEINTERVAL;
+            return;
+        }
+    }
+    if (!time_search(U, time, t, on_main ? c.ht : 0, p)) {
+        c.state = PK_ERROROUTSIDETIMEINTERVAL;
+        twe_note_all(a, c.it, klo);
+        return;
+    }
+    Coords vc = mc;  // (pointers and bounds in registers; on another grid nothing of it is read)
+    vc.cc.fvals = nullptr;
+    const Coords* pc = on_main ? &vc : nullptr;
+    const bool use_guess = take_first_eval(c, U.grid) ? (a.prm.have_guess0 != 0) : true;
+    int32_t ei = ei_get(c, U.grid);
+    grid_search<KIND, false>(g, pc, z, y, x, pos_f32, &ei, c, use_guess, p);
+    ei_set(c, U.grid, ei);
+    const int flags = oob_flags(p);
+    double uu = 0, vv = 0, ww = 0;
+    if (!(flags & 1)) {
+        const DField* W = (want_w && fW >= 0) ? &kfield(a, fW) : nullptr;
+        if (INTERP == 1) {
+            cgrid_velocity<FT, KIND, false>(g, pc, U, V, W, p, y, pos_f32, uu, vv, ww, c.u32, c.v32);
+        } else if (INTERP == 2) {
+            const bool freeslip = interp_uv == 2;
+            slip_velocity<FT>(g, U, V, W, p, y, pos_f32, freeslip ? 1.0 : 0.5, freeslip ? 0.0 : 0.5, a.prm.force_lenz, uu, vv, ww, c.u32, c.v32);
+        } else {  // XLinear_Velocity.interp (_xinterpolators.py:169-190), as in eval_uvw
+            const Corners k = make_corners(U, p);
+            bool u32 = false, v32 = false;
+            uu = xlinear<FT>(U, k, p, &u32);
+            PK_FIELD_FENCE();
+            vv = same_layout(U, V) ? xlinear<FT>(V, k, p, &v32) : xlinear<FT>(V, make_corners(V, p), p, &v32);
+            PK_FIELD_FENCE();
+            if (W) ww = same_layout(U, *W) ? xlinear<FT>(*W, k, p) : xlinear<FT>(*W, p);
+            if (g.spherical) {
+                double conv;
+                if (pos_f32) conv = (double)((float)g.deg2m * cosf((float)y * DEG2RADF));
+                else conv = g.deg2m * cos_lat(y * DEG2RAD);
+                if (u32) uu = pos_f32 ? (double)((float)uu / (float)conv) : (double)(float)(uu / conv);
+                else uu /= conv;
+                if (v32) vv = (double)((float)vv / (float)g.deg2m);
+                else vv /= g.deg2m;
+            }
+            c.u32 = u32;
+            c.v32 = v32;
+        }
+    }
+    u = finish_value(c, flags, uu);
+    v = finish_value(c, flags, vv);
+    w = finish_value(c, flags, ww);
+}
+#endif  // PK_USER_VECTORS
+
 // ---- counter-based RNG for the stochastic kernels --------------------------------------------------------
 // The reference draws from NumPy's global MT19937 stream (_advectiondiffusion.py:37-38), which no parallel
 // engine can reproduce.  Here: Philox4x32-10, key = (seed, kernel slot), counter = (particle_id, bits of the

@@ -39,7 +39,7 @@ PK_DEV double psub(bool pf, double a, double b) { return pf ? (double)((float)a 
 PK_DEV double pstore(bool pf, double v) { return pf ? (double)(float)v : v; }
 
 // what the current stage wants sampled
-enum { RQ_UV = 0, RQ_UVW = 1, RQ_SCALAR = 2 };
+enum { RQ_UV = 0, RQ_UVW = 1, RQ_SCALAR = 2, RQ_VEC = 3 };  // RQ_VEC: the fidx-th named vector field of a generated module (PK_USER_VECTORS)
 struct Request {
     int kind, fidx;
     double t, z, y, x;
@@ -94,6 +94,12 @@ constexpr double b50 = 16.0 / 135.0, b51 = 0.0, b52 = 6656.0 / 12825.0, b53 = 28
 // runs the statements up to the first field sample (and names it in rq), stage k those after the k-th sample (its values are in
 // L.r[3..5], where consume() leaves the latest sample), the last stage returns true.
 PK_DEV bool user_prepare(const KArgs& a, int uk, int stage, int kslot, PCtx& c, PState& p, KLocal& L, Request& rq);
+#endif
+#ifdef PK_USER_VECTORS
+// The named vector fields the module's kernels sample (`fieldset.Wind[particles]`): one case per vector, each a call of eval_vec (pk_device.h)
+// with the vector's component ids, dtype, grid kind and interpolator as the host resolved them on the engine (jit.py: compile_kernel_list).
+PK_DEV void user_eval_vec(const KArgs& a, const Coords& mc, PCtx& c, int j, double t, double z, double y, double x, bool pos_f32, double& u,
+                          double& v, double& w);
 #endif
 // prepare(): returns true when the kernel is finished (after writing its result into p / c), otherwise fills rq.
 PK_DEV bool prepare(const KArgs& a, int kid, int stage, int kslot, PCtx& c, PState& p, KLocal& L, Request& rq) {
@@ -580,6 +586,10 @@ __global__ void __launch_bounds__(wg_size(KIND, LDS), (KIND == 1 || INTERP != 0)
                             c.zpos_f32 = rq.zf32;
                             if (rq.kind == RQ_SCALAR) {
                                 u = eval_scalar<FT, TYPED>(a, mc, c, rq.fidx, rq.t, rq.z, rq.y, rq.x, rq.f32, (MEMO && rq.reuse) ? &memo : nullptr);
+#ifdef PK_USER_VECTORS
+                            } else if (rq.kind == RQ_VEC) {
+                                user_eval_vec(a, mc, c, rq.fidx, rq.t, rq.z, rq.y, rq.x, rq.f32, u, v, w);
+#endif
                             } else {
                                 const bool keep = MEMO && (kid == PK_KERNEL_ADVECTIONDIFFUSION_M1 || kid == PK_KERNEL_ADVECTIONDIFFUSION_EM);
                                 eval_uvw<FT, KIND, INTERP, TYPED>(a, mc, c, rq.kind == RQ_UVW, rq.t, rq.z, rq.y, rq.x, rq.f32, u, v, w, keep ? &memo : nullptr);

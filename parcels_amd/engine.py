@@ -109,6 +109,7 @@ class DeviceEngine:
         # neighbour_probe: pk_grid_desc.neighbour_probe (0 automatic, 1 always, -1 never; include/parcels_hip.h)
         self.neighbour_probe = int(neighbour_probe)
         self.fieldset = fieldset
+        self.attached_structured = True  # pk_eval_attached also samples structured grids with the particles' `ei` (field.py: _attached_guess)
         self.device = int(device)
         self.ctx = _hip.Context(self.device)
         self.lib = self.ctx.lib
@@ -1157,7 +1158,12 @@ class DeviceEngine:
             prm.fW = -1
         if ei is not None:
             ei = np.ascontiguousarray(ei, dtype=np.int32).copy()
-            self.ctx.check(self.lib.pk_eval_attached(self.ctx.handle, C.byref(prm), what, int(np.any(ei)), m, _ptr(t), _ptr(z), _ptr(y), _ptr(x), _ptr(ei),
+            g = (f.U if isinstance(f, VectorField) else f).grid
+            if isinstance(g, UxGrid) or "X" not in g.axes:
+                guessed = int(np.any(ei))  # uxgrid.py:113
+            else:  # np.any(xi) over the unravelled guesses (index_search.py:269)
+                guessed = int(np.any(np.mod(ei.astype(np.int64), max(g.xdim, 1)) != 0))
+            self.ctx.check(self.lib.pk_eval_attached(self.ctx.handle, C.byref(prm), what, guessed, m, _ptr(t), _ptr(z), _ptr(y), _ptr(x), _ptr(ei),
                                                      _ptr(u), _ptr(v), _ptr(w), _ptr(st)), "pk_eval_attached")
             self.last_sample_ei = ei
         else:

@@ -310,15 +310,17 @@ def _eval_key(field, key):
 
 
 def _attached_guess(particles, eng, field):
-    """A sample WITH the particles on a UxGrid starts its face search from their `ei` (field.py:173-176, uxgrid.py:113-118): a point found
-    in its guessed face keeps float64 barycentric coordinates, one found through the hash float32-rounded ones -- which a node-registered
-    field shows in its value.  -> the `ei` of the selected rows on the field's grid, or None (no particles; a structured grid, whose
-    search gives the same cell coordinates with and without a guess here)."""
+    """A sample WITH the particles starts its search from their `ei` (field.py:173-176, uxgrid.py:113-118, index_search.py:269-285): on a
+    UxGrid and on a curvilinear grid a point found in its guessed cell keeps the float64 cell coordinates of the point-in-cell test, one
+    found through the hash float32-rounded ones -- which shows in the value.  -> the `ei` of the selected rows on the field's grid, or None
+    (no particles; a rectilinear grid, whose search gives the same cell coordinates with and without a guess)."""
     from .hostkernels import HostParticles
     from .uxgrid import UxGrid
 
-    if not isinstance(particles, HostParticles) or not isinstance(field.grid, UxGrid) or len(particles._rows) == 0:
+    if not isinstance(particles, HostParticles) or len(particles._rows) == 0:
         return None
+    if not isinstance(field.grid, UxGrid) and not (getattr(field.grid, "is_curvilinear", False) and getattr(eng, "attached_structured", False)):
+        return None  # (attached_structured: the engine's pk_eval_attached takes structured grids -- stand-in engines search unguessed)
     return np.ascontiguousarray(particles._data["ei"][particles._rows, eng.grids.index(field.grid)], dtype=np.int32)
 
 

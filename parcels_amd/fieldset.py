@@ -2,6 +2,8 @@
 
 from __future__ import annotations
 
+import warnings
+
 import numpy as np
 
 from .dataset import Dataset
@@ -9,7 +11,11 @@ from .field import Field, StructuredModelData, VectorField
 from .interpolators import XConstantField, XLinear
 from .sgrid import FaceNodePadding, Padding, SGrid2DMetadata
 
-__all__ = ["FieldSet"]
+__all__ = ["FieldSet", "FieldSetWarning"]
+
+
+class FieldSetWarning(UserWarning):  # _core/warnings.py:4-9
+    """A FieldSet was put together in a way that may not do what the user expects."""
 
 
 def _constant_field_model(mesh):
@@ -79,6 +85,44 @@ class FieldSet:
         if name in ctx:
             return ctx[name]
         raise AttributeError(f"FieldSet has no attribute '{name}'")
+
+    def __add__(self, other):
+        """fieldset.py:110-116: the FieldSet over the models of both (``fs_currents + fs_stokes``, ``fieldset += ...``), contexts merged.
+        The models -- and with them the Field objects and the constant-field models -- are shared with the operands, like in the
+        reference, and from here on they belong to the SUM: a field's ``igrid`` and its link to its FieldSet (which engine evaluates it,
+        whose device copy an ``interp_method`` assignment invalidates) are the sum's.  Do not use an operand after adding it; keep the
+        sum (``fieldset += other`` does): an operand that is asked for a device copy afterwards raises RuntimeError.  The sum gets its
+        own device copy when it is first used."""
+        if not isinstance(other, FieldSet):
+            return NotImplemented
+        common_fields = set(self.fields) & set(other.fields)  # assert_compatible_fieldsets, fieldset.py:332-355
+        if common_fields:
+            raise ValueError(f"Cannot add FieldSets that have field names in common. Duplicate field names are: {sorted(common_fields)}")
+        common_context = set(self.context) & set(other.context)
+        if common_context:
+            raise ValueError("Cannot add FieldSets that have context value names in common. Duplicate context value names are: "
+                             f"{sorted(common_context)}")
+        combined = FieldSet(self.models + other.models)
+        combined.__dict__["context"] = {**self.context, **other.context}
+        combined._constant_models = {**other._constant_models, **self._constant_models}
+        if "_window_slots" in self.__dict__:
+            combined.__dict__["_window_slots"] = self.__dict__["_window_slots"]
+        # FieldSet.__init__ -> _warn_if_fields_use_different_meshes (:77, :358-377); meshes compare by kind and radius like the reference's
+        meshes = {}
+        for f in combined.fields.values():
+            mesh = (f.U if isinstance(f, VectorField) else f).grid._mesh
+            meshes.setdefault((type(mesh).__name__, mesh.radius), mesh)
+        if len(meshes) > 1:
+            warnings.warn(f"FieldSet has multiple different meshes: {set(meshes.values())}. This may lead to unexpected behavior during execution.",
+                          FieldSetWarning, stacklevel=2)
+        for operand in (self, other):  # their fields are the sum's now: evaluating through an operand would run on the wrong engine
+            operand.__dict__["_absorbed"] = True
+            operand.__dict__["_engine"] = None
+        return combined
+
+    def _refuse_if_absorbed(self):
+        if self.__dict__.get("_absorbed"):
+            raise RuntimeError("this FieldSet was added to another one (fs_a + fs_b): its fields belong to the sum now -- use the sum")
 
     @property
     def time_interval(self):
@@ -172,6 +216,7 @@ class FieldSet:
     def _engine_or_create(self, device: int | None = None):
         from .engine import DeviceEngine
 
+        self._refuse_if_absorbed()
         if self._engine is None or (device is not None and self._engine.device != device):
             self.__dict__["_engine"] = DeviceEngine(self, device=0 if device is None else device, nslots=self.__dict__.get("_window_slots"))
         return self._engine
@@ -199,6 +244,7 @@ class FieldSet:
         device-resident time levels per field (the analogue of FieldSet.to_windowed_arrays, fieldset.py:142-173)."""
         from .engine import DeviceEngine
 
+        self._refuse_if_absorbed()
         if nslots is None:
             nslots = self.__dict__.get("_window_slots")
         self.__dict__["_engine"] = DeviceEngine(self, device=device, nslots=nslots)

@@ -27,8 +27,15 @@ grids, without the particles (``fieldset.T[t, z, y, x]``: state and ``ei`` are r
 write-through proxy that is read when an operation consumes it (a sample later in the statement may change it); tests on the whole set
 (``if len(inds) == 0: return``, ``if np.any(mask): ...``) are dropped when everything they guard stays inside that selection.  What the
 reference's loop decides for the whole SET stays out: a kernel that stores ``StatusCode.Success`` (kernel.py:190-193 keeps such
-particles running while any other particle is).  tools/survey_user_kernels.py: 66 of the 86 kernels of the reference's own tests and
+particles running while any other particle is).  tools/survey_user_kernels.py: 68 of the 89 kernels of the reference's own tests and
 tutorials compile.
+
+VECTOR FIELDS UNDER OTHER NAMES than UV / UVW -- `fieldset.Wind[particles]`, `fieldset.UVstokes[t, z, y1, x1, particles]` -- are sampled like
+UV: the translator only records the name (request kind RQ_VEC, index into the module's list of such names); ``compile_kernel_list`` looks
+each name up on the engine (component field ids, their device dtype, the kind of their grid, the interpolator) and the module gets a
+dispatch function ``user_eval_vec`` whose cases instantiate ``eval_vec`` (csrc/pk_device.h) with those values.  Such a module runs in the
+kernel-list interpreter of a structured fieldset only; on a UxGrid, in the CROCO sigma loop and with float32 coordinate arrays the list keeps
+the host path (``NotTranslatable("vector field '<name>': ...")``).
 
 On a CROCO fieldset the module carries the sigma loop (csrc/pk_sigma.h, ``_TEMPLATE_SIGMA``) instead of the structured interpreter: next to
 AdvectionRK2_3D_CROCO / SampleFieldCroco tokens, and for any kernel that calls ``convert_z_to_sigma_croco(fieldset, t, z, y, x, particles)``
@@ -178,8 +185,11 @@ _LIBM = {"sin": ("sin", 1), "cos": ("cos", 1), "tan": ("tan", 1), "arcsin": ("as
 
 
 class _Translator(ast.NodeVisitor):
-    def __init__(self, func, pclass, fieldset, var_slot, field_ids, next_dt_f32=False, slot_prefix=""):
+    def __init__(self, func, pclass, fieldset, var_slot, field_ids, next_dt_f32=False, slot_prefix="", vectors=None):
         self.func, self.fieldset, self.field_ids = func, fieldset, field_ids
+        # names of the vector fields other than UV / UVW that the MODULE samples, in order of first use (shared by the kernels of one list):
+        # a sample of vectors[j] is the request (RQ_VEC, j), which the module's dispatch function serves (compile_kernel_list)
+        self.vectors = vectors if vectors is not None else []
         self.slot_prefix = slot_prefix
         self.var_slot = var_slot  # user Variable name -> (extra column index, dtype tag)
         self.vars = {v.name: np.dtype(v.dtype) for v in pclass.variables}
@@ -203,7 +213,7 @@ class _Translator(ast.NodeVisitor):
         self.decl: list[str] = []  # members of PkUserLocals
         self.stages: list[list[str]] = [[]]
         self.touched: set[str] = set()
-        self.sampled: list = []  # ('UV' | 'UVW' | scalar field id) of every sample, in order
+        self.sampled: list = []  # ('UV' | 'UVW' | name of another vector field | scalar field id) of every sample, in order
         self.views: dict[str, _View] = {}  # locals bound to a selection of the particles
         self.index_locals: dict[str, _V] = {}  # locals bound to np.where(cond) / np.flatnonzero(cond): usable as particles[<local>] only
         self._kids: list[list[_V]] = []  # operands of the expression being translated (their domains combine into the result's)
@@ -486,11 +496,14 @@ class _Translator(ast.NodeVisitor):
             raise NotTranslatable(f"fieldset has no field '{name}'")
         vector = hasattr(fld, "U")
         if vector:
-            if name not in ("UV", "UVW"):
-                raise NotTranslatable(f"vector field '{name}'")
             if fld is not self.fieldset.fields.get(name):
                 raise NotTranslatable("vector field alias")
-            kind, n, fid = ("RQ_UVW", 3, 0) if name == "UVW" else ("RQ_UV", 2, 0)
+            if name in ("UV", "UVW"):
+                kind, n, fid = ("RQ_UVW", 3, 0) if name == "UVW" else ("RQ_UV", 2, 0)
+            else:  # wind, Stokes drift, ...: nothing of the field is resolved here (what it is on the engine: compile_kernel_list)
+                if name not in self.vectors:
+                    self.vectors.append(name)
+                kind, n, fid = "RQ_VEC", (3 if getattr(fld, "W", None) is not None else 2), self.vectors.index(name)
         else:
             if name in ("U", "V", "W"):
                 raise NotTranslatable("sampling a velocity component by itself (the reference warns: host path)")
@@ -1021,7 +1034,19 @@ class _Translator(ast.NodeVisitor):
                 t = st.targets[0]
                 if isinstance(t, ast.Tuple):
                     if not self.is_sample(st.value):
-                        raise NotTranslatable("tuple assignment of something other than a vector sample")
+                        # x1, y1 = (particles.x + u1 * h, particles.y + v1 * h): new temporaries bound to local names -- every value is
+                        # computed before the first name is bound, and a binding takes a fresh slot, so the order cannot show
+                        ok = (isinstance(st.value, (ast.Tuple, ast.List)) and len(st.value.elts) == len(t.elts)
+                              and all(isinstance(el, ast.Name) and el.id not in (self.pname, self.fname) for el in t.elts)
+                              and all(isinstance(v, (ast.BinOp, ast.UnaryOp, ast.Call, ast.Constant, ast.Compare)) and not self.is_sample(v)
+                                      for v in st.value.elts)
+                              and len({el.id for el in t.elts}) == len(t.elts))
+                        if not ok:
+                            raise NotTranslatable("tuple assignment of something other than a vector sample")
+                        values = [self.expr(v) for v in st.value.elts]
+                        for el, value in zip(t.elts, values):
+                            self.assign(self.target(el), value)
+                        continue
                     comps = self.sample(st.value)
                     if not isinstance(comps, list) or len(comps) != len(t.elts):
                         raise NotTranslatable("vector sample unpacked into the wrong number of names")
@@ -1143,6 +1168,7 @@ class _Translator(ast.NodeVisitor):
 class UserKernelSource:
     def __init__(self, name, decl, stages, touched, sampled=(), detached=False, counter=None, sigma=False):
         self.name, self.decl, self.stages, self.touched, self.sampled = name, decl, stages, touched, list(sampled)
+        # (sampled: 'UV' | 'UVW' | the name of another vector field | a scalar field id, one per sample, in order)
         self.sigma = sigma  # calls convert_z_to_sigma_croco: only the CROCO sigma loop serves its conversion requests
         self.detached = detached  # samples without the particles: restores PCtx::state / ei, which the dedicated kernels keep elsewhere
         # kernels that sample for a sub-selection of the particles: a lane outside it goes straight on to the statements behind the sample,
@@ -1161,10 +1187,11 @@ class UserKernelSource:
         return "\n".join(out)
 
 
-def translate(func, pclass, fieldset, var_slot, field_ids, next_dt_f32=False, slot_prefix="") -> UserKernelSource:
-    """Python kernel -> stage-machine source.  var_slot: {user Variable name: (extra column index, dtype tag 'f32' | 'f64')}."""
+def translate(func, pclass, fieldset, var_slot, field_ids, next_dt_f32=False, slot_prefix="", vectors=None) -> UserKernelSource:
+    """Python kernel -> stage-machine source.  var_slot: {user Variable name: (extra column index, dtype tag 'f32' | 'f64')}.
+    vectors: the list of named vector fields the kernels of one module sample, extended here (_Translator.vectors)."""
     try:
-        tr = _Translator(func, pclass, fieldset, var_slot, field_ids, next_dt_f32, slot_prefix)
+        tr = _Translator(func, pclass, fieldset, var_slot, field_ids, next_dt_f32, slot_prefix, vectors)
     except (OSError, TypeError, SyntaxError, IndentationError) as e:
         raise NotTranslatable(f"source of {getattr(func, '__name__', func)!r} is not available: {e}") from None
     tr.run()
@@ -1189,7 +1216,7 @@ def candidate_variables(func, pclass):
 
 _TEMPLATE = """// generated by parcels_amd/jit.py -- user kernels: {names}
 #define PK_USER_KERNELS 1
-#ifndef PK_MIN_WAVES
+{vec_define}#ifndef PK_MIN_WAVES
 #define PK_MIN_WAVES 2
 #endif
 #include <stdint.h>
@@ -1206,7 +1233,7 @@ PK_DEV bool user_prepare(const KArgs& a, int uk, int stage, int kslot, PCtx& c, 
         default: c.state = PK_ERROR; return true;
     }}
 }}
-}}  // namespace pk
+{vec_dispatch}}}  // namespace pk
 extern "C" void pk_user_launch(const void* kargs, int32_t prog, int32_t key, int32_t lds, uint64_t lds_bytes, void* stream) {{
     using namespace pk;
     const KArgs& a = *(const KArgs*)kargs;
@@ -1323,11 +1350,13 @@ def cache_dir() -> str:
 class UserProgram:
     """One compiled module: the kernel-list interpreter of ONE variant with up to PK_MAX_USER_KERNELS user kernels in it."""
 
-    def __init__(self, sources: list[UserKernelSource], key: int, lds: int, fast: int = 0, particles_f32: bool = False):
+    def __init__(self, sources: list[UserKernelSource], key: int, lds: int, fast: int = 0, particles_f32: bool = False, vectors=()):
         """key / lds: the interpreter variant (pk_generic_variant; key PK_USER_KEY_UX: the step loop of a UxGrid, csrc/pk_ux.h; keys
         PK_USER_KEY_SIGMA .. + 7: the CROCO sigma loop, csrc/pk_sigma.h, whose LDS size is the launch's and not part of the module).
         fast: 1 / 2 = also carry the dedicated A-grid kernel (2-D / 3-D) with the user kernels riding along -- only for modules whose
-        kernels sample no field and leave next_dt alone."""
+        kernels sample no field and leave next_dt alone.
+        vectors: the named vector fields the kernels sample, request index j -> (name, fU, fV, fW or -1, 'float' | 'double', grid kind 0 | 1,
+        interp_method.kind 0 .. 3) as resolved on the engine; they become the cases of the module's dispatch function (user_eval_vec)."""
         if not (1 <= len(sources) <= PK_MAX_USER_KERNELS):
             raise NotTranslatable(f"1 .. {PK_MAX_USER_KERNELS} user kernels per kernel list")
         self.sources = list(sources)
@@ -1346,7 +1375,11 @@ class UserProgram:
         sampled = [x for src in sources for x in src.sampled]
         self.sample_fids = sorted({x for x in sampled if isinstance(x, int)})
         self.sample_flags = (2 if "UV" in sampled else 0) | (4 if "UVW" in sampled else 0)  # PK_USER_SAMPLES_UV / _UVW
-        rides = fast and not self.ux and not self.sigma and all("next_dt" not in src.touched and not src.detached for src in sources) and len(self.sample_fids) <= 4
+        self.vectors = [tuple(v) for v in vectors]
+        if self.vectors and (self.ux or self.sigma):
+            raise NotTranslatable(f"vector field '{self.vectors[0][0]}': only the structured kernel-list interpreter samples named vector fields")
+        # (a module that samples a named vector field never rides: the dedicated kernels evaluate the launch's velocity and its layout only)
+        rides = fast and not self.vectors and not self.ux and not self.sigma and all("next_dt" not in src.touched and not src.detached for src in sources) and len(self.sample_fids) <= 4
         self.flags = (1 | self.sample_flags) if rides else self.sample_flags  # PK_USER_RIDE: the module carries the dedicated kernel
         fast_launch = ""
         if self.flags & 1:
@@ -1376,7 +1409,8 @@ class UserProgram:
                                                  interp=v & 1)
         else:
             self.source = _TEMPLATE.format(names=names, decl=decl, cases=cases, key=key, lds=lds, ft=ft, kind=kind, interp=interp,
-                                           ldsb="true" if lds else "false", fast_launch=fast_launch)
+                                           ldsb="true" if lds else "false", fast_launch=fast_launch,
+                                           vec_define="#define PK_USER_VECTORS 1\n" if self.vectors else "", vec_dispatch=self._vec_dispatch())
         # (measured on C2 with a sampling kernel riding in the dedicated A-grid kernel, tools/bench_user_kernels.py: 4 waves per SIMD 12.6 ms,
         # 3 waves 13.8 ms, 2 waves 12.5 ms -- the library's own occupancy target stays; PARCELS_AMD_JIT_FAST_WAVES overrides for A/B runs)
         # A dedicated kernel that carries user kernels keeps the correctly rounded quotients and full-range sines / cosines of the general
@@ -1388,6 +1422,18 @@ class UserProgram:
         self.digest = hashlib.sha256((self.source + " ".join(self.defines) + _csrc_hash()).encode()).hexdigest()[:20]
         self.path = os.path.join(cache_dir(), f"user_{self.digest}.so")
         self._lib = None
+
+    def _vec_dispatch(self) -> str:
+        """user_eval_vec of the module: one instantiation of eval_vec (csrc/pk_device.h) per named vector field, its values as literals."""
+        if not self.vectors:
+            return ""
+        out = ["PK_DEV void user_eval_vec(const KArgs& a, const Coords& mc, PCtx& c, int j, double t, double z, double y, double x, bool pos_f32, "
+               "double& u,", "                          double& v, double& w) {", "    switch (j) {"]
+        for j, (name, fu, fv, fw, ft, kind, interp) in enumerate(self.vectors):
+            out.append(f"        case {j}: eval_vec<{ft}, {int(kind)}, {min(int(interp), 2)}>(a, mc, c, {int(fu)}, {int(fv)}, {int(fw)}, {int(interp)}, "
+                       f"{'true' if fw >= 0 else 'false'}, t, z, y, x, pos_f32, u, v, w); break;  // {name}")
+        out += ["        default: u = v = w = 0.0; c.state = PK_ERROR; break;", "    }", "}"]
+        return "\n".join(out) + "\n"
 
     _failed: dict = {}  # digest -> compiler message: a module that did not compile is not compiled again by every pset.execute
 
@@ -1454,11 +1500,11 @@ def compile_kernel_list(functions, builtin_id, pclass, fieldset, engine, samples
         raise NotTranslatable(f"more than {_hip.PK_MAX_EXTRA} user Variables touched by device kernels (PK_MAX_EXTRA)")
     var_slot = {vn: (k, _ty_of_dtype(names[vn].dtype)) for k, vn in enumerate(dev_vars)}
     next_dt_f32 = "next_dt" in names and np.dtype(names["next_dt"].dtype) != np.float64
-    sources, ids, j = [], [], 0
+    sources, ids, j, vnames = [], [], 0, []
     for f in functions:
         kid = builtin_id(f)
         if kid is None:
-            sources.append(translate(f, pclass, fieldset, var_slot, engine.field_ids, next_dt_f32, slot_prefix=f"k{j}_"))
+            sources.append(translate(f, pclass, fieldset, var_slot, engine.field_ids, next_dt_f32, slot_prefix=f"k{j}_", vectors=vnames))
             kid = PK_KERNEL_USER0 + j
             j += 1
         ids.append(kid)
@@ -1477,9 +1523,35 @@ def compile_kernel_list(functions, builtin_id, pclass, fieldset, engine, samples
     cf = (C.c_int32 * 4)(*(fids + [0] * 4)[:4])
     engine.ctx.check(engine.lib.pk_generic_variant(engine.ctx.handle, C.byref(prm), sflags, min(len(fids), 4), cf, C.byref(key), C.byref(lds), C.byref(typed),
                                                    C.byref(fast)), "pk_generic_variant")
+    vectors = []
+    for vn in vnames:  # what each named vector field is on THIS engine: the table the module's dispatch function is generated from
+        why = None
+        if key.value == PK_USER_KEY_UX:
+            why = "the step loop of a UxGrid samples no named vector fields"
+        elif PK_USER_KEY_SIGMA <= key.value < PK_USER_KEY_SIGMA + 8:
+            why = "the CROCO sigma loop samples no named vector fields"
+        elif typed.value:
+            why = "float32 coordinate arrays (NumPy dtype propagation of the typed program)"
+        vf = fieldset.fields[vn]
+        comps = [c for c in (vf.U, vf.V, getattr(vf, "W", None)) if c is not None]
+        ikind = getattr(getattr(vf, "interp_method", None), "kind", None)
+        if why is None and ikind not in (0, 1, 2, 3):
+            why = f"its interpolator {type(getattr(vf, 'interp_method', None)).__name__} has no device code"
+        if why is None and any(c.name not in engine.field_ids for c in comps):
+            why = "a component is not a field of the device copy"
+        if why is None and len({engine.field_host[c.name].dtype for c in comps}) != 1:
+            why = "its components differ in dtype on the device"
+        if why is None and any(c.grid is not vf.U.grid for c in comps):
+            why = "its components live on different grids"
+        if why is not None:
+            raise NotTranslatable(f"vector field '{vn}': {why}")
+        ft = "float" if engine.field_host[vf.U.name].dtype == np.float32 else "double"
+        fw = engine.field_ids[vf.W.name] if getattr(vf, "W", None) is not None else -1
+        vectors.append((vn, engine.field_ids[vf.U.name], engine.field_ids[vf.V.name], fw, ft, 1 if vf.U.grid.is_curvilinear else 0, int(ikind)))
     if typed.value:
         raise NotTranslatable("float32 coordinate arrays (NumPy dtype propagation of the typed program)")
-    prog = UserProgram(sources, key.value, lds.value, fast=(fast.value if len(fids) <= 4 else 0), particles_f32=np.dtype(names["x"].dtype) == np.float32)
+    prog = UserProgram(sources, key.value, lds.value, fast=(fast.value if len(fids) <= 4 and not vectors else 0),
+                       particles_f32=np.dtype(names["x"].dtype) == np.float32, vectors=vectors)
     prog.launcher()  # builds (or finds in the cache) and loads the module
     return ids, prog, dev_vars
 
