@@ -2316,6 +2316,10 @@ int32_t pk_execute_begin(pk_ctx* ctx, const pk_exec_params* prm) {
     int use_lds = 0;
     int32_t rc = launch_args(ctx, prm, a, lds_bytes, use_lds);
     if (rc) return rc;
+    // A continued launch says "guessed" for the particles that have stepped; one that paused before its first step still has its first
+    // evaluation ahead (pk_kernels.h: first_eval), and that one is guessed iff the call's batch held a guess
+    if (prm->reset_state) ctx->call_have_guess0 = prm->have_guess0;
+    else if (!prm->body_only) a.prm.have_guess0 = ctx->call_have_guess0;
     rc = upload_descriptors(ctx, a);
     if (rc) return rc;
     bool need_kh = false, has_user = false;

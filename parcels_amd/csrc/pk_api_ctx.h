@@ -152,6 +152,7 @@ struct pk_ctx {
     hipDeviceProp_t prop;
     // an advection launch in flight (pk_execute_begin .. pk_execute_end)
     bool in_flight = false;
+    int32_t call_have_guess0 = 0;  // have_guess0 of the call's first launch (reset_state): what a continued launch inherits
     int fl_launches = 0;
     int fl_program = 0;
     // the last advection launch wrote into the second column set, which now is `dev`; `alt` still holds what it read

@@ -526,7 +526,9 @@ __global__ void __launch_bounds__(wg_size(KIND, LDS), (KIND == 1 || INTERP != 0)
             c.klo = 0;
             c.hz = c.hy = c.hx = c.ht = 0;
             c.hyx_valid = false;
-            c.first_eval = prm.reset_state ? 0xFu : 0u;
+            // (a particle that paused before its first step -- releases spread over more than the resident window of a ring of levels --
+            // has its first evaluation ahead of it in a continued launch, where prm.have_guess0 is the call's: pk_execute_begin)
+            c.first_eval = (prm.reset_state || (!body && it == 0u)) ? 0xFu : 0u;
             c.u32 = c.v32 = false;
             PState p;
             p.t = P.t[i];

@@ -976,6 +976,9 @@ class DeviceEngine:
         if span is not None and known:
             horizon = (-np.inf, float(t_live) + span) if call.sign > 0 else (float(t_live) - span, np.inf)
         sort_now = 0 if (reset and call.skip_first_sort) else call.sort_by_cell
+        # have_guess0 of a continued launch (reset == 0): the particles that have stepped search guessed whatever is passed, and for a
+        # particle that paused before its first step pk_execute_begin puts the value of the call's reset launch in its place (kept in the
+        # context: a continued launch always follows the reset launch of its own call) -- the 1 passed here is never read
         prm = self.make_params(call.kernel_ids, reset_state=reset, have_guess0=(call.have_guess0 if reset else 1), sort_by_cell=sort_now,
                                horizon=horizon, max_iters=cap, twe_keys=keys, **call.params)
         if sort_now:

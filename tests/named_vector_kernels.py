@@ -47,6 +47,11 @@ def WindDetached(particles, fieldset):
     particles.dy += vw * fieldset.windage * particles.dt
 
 
+def NoSample(particles, fieldset):
+    """Samples nothing: what a list with a detached sample is compared with."""
+    particles.dx += 0.0
+
+
 def DeleteParticle(particles, fieldset):
     """Delete every particle that carries an error code."""
     particles[particles.state >= 50].state = StatusCode.Delete

@@ -49,7 +49,8 @@ def _second_grid(names, *, lon, lat, time_s, scale, seed, offset=0.0, mesh="sphe
 def all_cases() -> dict:
     """name -> spec: `currents` (a case dict of oracle/cases.py; named vectors on its grid in `vectors`), optionally `second` (another
     dataset with `vectors` of its own, added with FieldSet + FieldSet), `kernels` (names: built-in ones or those of named_vector_kernels),
-    `variables` [(name, dtype)], `context`."""
+    `variables` [(name, dtype)], `context`; `interp` {vector: 'cgrid' | 'free' | 'partial'} (also inside `second`, which may have a `depth` and
+    2-D `lon` / `lat`); release times in `currents["t0"]` (zero when absent)."""
     out = {}
     wind = {"Wind": ("UWind", "VWind")}
     for order, kl in (("adv_wind", ["AdvectionRK2", "WindMidpoint"]), ("wind_adv", ["WindMidpoint", "AdvectionRK2"])):
@@ -98,6 +99,58 @@ def all_cases() -> dict:
         kl = ["AdvectionRK2", "WindMidpoint"]
         c = _same_grid_vector(_agrid(f"nv_k_{slip}slip", kl), ("UWind", "VWind"), scale=8.0, seed=19, land=True)
         out[c["name"]] = dict(currents=c, vectors=wind, interp={"Wind": slip}, kernels=kl, context={"windage": 0.03})
+    # l: g with releases three quarters of a step apart.  In the iteration that finds the early releases at 3 h and the late ones at 3.75 h,
+    # the midpoint sample of WindMidpoint asks for 3.5 h and for 4.25 h: only the late ones are past the wind's last level (4 h), and the
+    # reference gives the whole view the code (field.py:31-44).  The early releases stop at 3 h although both of their own samples of that
+    # step lie inside the axis; a per-particle rule would carry them on to 4 h.
+    kl = ["AdvectionRK2", "WindMidpoint"]
+    c = _agrid("nv_l_partial_time_end", kl)
+    c["t0"] = np.where(np.arange(65) % 3 == 0, 0.0, 2700.0)
+    s = _second_grid(("UWind", "VWind"), lon=(0.0, 360.0), lat=(-80.0, 80.0), time_s=np.arange(3) * 7200.0, scale=8.0, seed=16)
+    s["vectors"] = wind
+    out[c["name"]] = dict(currents=c, vectors={}, second=s, kernels=kl, context={"windage": 0.03})
+    # m: two named vectors in one list -- j's C-grid wind on the curvilinear main grid and b's Stokes drift on a second, rectilinear grid
+    kl = ["AdvectionRK4", "WindMidpoint", "StokesEuler"]
+    c = oc.curv_cgrid_case("nv_m_two_vectors", mesh="spherical", kernels=kl, seed=8, nx=14, ny=11, nz=3, nt=3, npart=65, field_dtype=np.float64,
+                           with_w=False, dt=1800.0, runtime=8 * 1800.0, vel=0.3)
+    c = _same_grid_vector(c, ("UWind", "VWind"), scale=5.0, seed=18, like=("U", "V"))
+    s = _second_grid(("Ustokes", "Vstokes"), lon=(-60.0, 80.0), lat=(0.0, 85.0), time_s=np.arange(4) * 50000.0, scale=0.2, seed=12)
+    s["vectors"] = {"UVstokes": ("Ustokes", "Vstokes")}
+    out[c["name"]] = dict(currents=c, vectors=wind, interp={"Wind": "cgrid"}, second=s, kernels=kl, context={"windage": 0.03})
+    # n: a flat mesh; the Stokes drift (XLinear_Velocity) on a second, CURVILINEAR grid inside the currents' rectilinear one, a steady
+    # eastward drift that carries the particles released near its eastern edge out of it
+    kl = ["AdvectionRK2", "StokesEuler", "DeleteParticle"]
+    c = oc.rect_agrid_case("nv_n_second_curvilinear", mesh="flat", kernels=kl, seed=5, nx=12, ny=9, nz=3, nt=3, npart=130, dt=1800.0, runtime=8 * 1800.0,
+                           vel=0.2, margin=0.3, level_dt=86400.0)
+    lon2, lat2 = oc.curvilinear_grid(9, 8, mesh="flat")
+    lon2, lat2 = lon2 + 1.5e5, lat2 + 0.5e5
+    rng = np.random.default_rng(21)
+    ci, cj = rng.uniform(0.15, 0.85, 130) * 8, rng.uniform(0.15, 0.85, 130) * 7
+    ci[::10] = rng.uniform(7.6, 7.98, 13)  # in the easternmost cells
+    i0, j0 = ci.astype(int), cj.astype(int)
+    fi, fj = ci - i0, cj - j0
+    for key, a in (("x", lon2), ("y", lat2)):
+        c[key] = a[j0, i0] * (1 - fi) * (1 - fj) + a[j0, i0 + 1] * fi * (1 - fj) + a[j0 + 1, i0] * (1 - fi) * fj + a[j0 + 1, i0 + 1] * fi * fj
+    shp = (3, 1, 8, 9)
+    s = dict(mesh="flat", lon=lon2, lat=lat2, depth=None, time_s=np.arange(3) * 20000.0, x_pad="low", y_pad="low",
+             fields={"Ustokes": oc.smooth_random_field(rng, shp, 0.05) + 0.4, "Vstokes": oc.smooth_random_field(rng, shp, 0.05)},
+             field_dims={"Ustokes": NODE2D, "Vstokes": NODE2D}, vectors={"UVstokes": ("Ustokes", "Vstokes")})
+    out[c["name"]] = dict(currents=c, vectors={}, second=s, kernels=kl, context={})
+    # o: 257 particles (a block of 256 lanes and one more) with DeleteParticle; f's westerly wind carries one particle of the first, one of
+    # a middle and the one of the last wavefront over the wind grid's eastern edge, each on another step
+    kl = ["AdvectionRK2", "WindMidpoint", "DeleteParticle"]
+    c = _agrid("nv_o_blocks", kl, npart=257, vel=0.05)
+    for row, gap in ((3, 0.004), (130, 0.035), (256, 0.053)):  # (the windage moves a particle 0.009 degrees a step here)
+        c["x"][row], c["y"][row] = 270.0 - gap, 10.0
+    s = _second_grid(("UWind", "VWind"), lon=(90.0, 270.0), lat=(-60.0, 60.0), time_s=np.arange(3) * 86400.0, scale=1.0, seed=15, offset=9.0)
+    s["vectors"] = wind
+    out[c["name"]] = dict(currents=c, vectors={}, second=s, kernels=kl, context={"windage": 0.03})
+    # p: the detached sample (no particles in the key: no state change, no `ei` update) of a wind on a second, rectilinear grid
+    kl = ["AdvectionRK2", "WindDetached"]
+    c = _agrid("nv_p_detached", kl)
+    s = _second_grid(("UWind", "VWind"), lon=(0.0, 360.0), lat=(-80.0, 80.0), time_s=np.arange(5) * 7200.0, scale=8.0, seed=22)
+    s["vectors"] = wind
+    out[c["name"]] = dict(currents=c, vectors={}, second=s, kernels=kl, context={"windage": 0.03})
     return out
 
 
@@ -111,9 +164,9 @@ def save_fixture(path, out, err, meta=None):
     np.savez_compressed(path, **arrs)
 
 
-def load_fixture(name):
+def load_fixture(name, path=None):
     """-> (final columns of the reference's run, name of the error it raised or None)"""
-    z = np.load(fixture_path(name), allow_pickle=False)
+    z = np.load(path or fixture_path(name), allow_pickle=False)
     return {k[5:]: z[k] for k in z.files if k.startswith("out__")}, json.loads(str(z["meta"]))["err"]
 
 
@@ -152,15 +205,24 @@ def _pa_fieldset_of(ds_case, vectors):
     return fs
 
 
+def _interp_method(how):
+    import parcels_amd as pa
+
+    return {"cgrid": pa.CGrid_Velocity, "free": pa.XFreeslip, "partial": pa.XPartialslip}[how]()
+
+
 def build_fieldset(spec):
     """The FieldSet of a case; a second dataset is added the documented way, `fs_currents + fs_second`."""
     import parcels_amd as pa
 
     fs = _pa_fieldset_of(spec["currents"], spec["vectors"])
     for vname, how in spec.get("interp", {}).items():
-        fs.fields[vname].interp_method = {"cgrid": pa.CGrid_Velocity, "free": pa.XFreeslip, "partial": pa.XPartialslip}[how]()
+        fs.fields[vname].interp_method = _interp_method(how)
     if spec.get("second"):
-        fs = fs + _pa_fieldset_of(spec["second"], spec["second"]["vectors"])
+        fs2 = _pa_fieldset_of(spec["second"], spec["second"]["vectors"])
+        for vname, how in spec["second"].get("interp", {}).items():
+            fs2.fields[vname].interp_method = _interp_method(how)
+        fs = fs + fs2
     for k, v in spec["context"].items():
         fs.add_context(k, v)
     return fs
@@ -181,8 +243,8 @@ def build_pset(spec, fs):
     P = pa.get_default_particle(np.dtype(c["spatial_dtype"]).type)
     for vn, dt in spec.get("variables", ()):
         P = P.add_variable(pa.Variable(vn, dtype=np.dtype(dt).type, initial=0))
-    n = len(c["x"])
-    return pa.ParticleSet(fs, pclass=P, x=np.asarray(c["x"]), y=np.asarray(c["y"]), z=np.asarray(c["z"]), t=np.zeros(n))
+    t0 = np.zeros(len(c["x"])) if c.get("t0") is None else np.asarray(c["t0"], dtype=np.float64)  # (release times: zero unless the case staggers them)
+    return pa.ParticleSet(fs, pclass=P, x=np.asarray(c["x"]), y=np.asarray(c["y"]), z=np.asarray(c["z"]), t=t0)
 
 
 ERRORS = ("FieldOutOfBoundError", "FieldOutOfBoundSurfaceError", "FieldInterpolationError", "GridSearchingError", "OutsideTimeInterval", "GeneralError")

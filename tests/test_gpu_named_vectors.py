@@ -127,6 +127,65 @@ def test_k_wind_with_a_slip_interpolator(gpu, slip, kind):
     assert not np.array_equal(got["x"], other["x"])  # (the literal interp_uv tells the two apart)
 
 
+def test_l_time_axis_ends_for_some_particles_of_a_view(gpu):
+    """releases 2700 s apart, dt 3600 s: in the iteration with the early releases at 10800 s and the late ones at 13500 s the midpoint sample
+    (12600 s / 15300 s) is past the wind's last level (14400 s) for the late ones only -- the reference gives the whole view the code.  The
+    early releases stop at 10800 s, one step before a per-particle rule would stop them (at 14400 s): the t values tell the rules apart"""
+    pset, got = _check("nv_l_partial_time_end")
+    early = np.arange(65) % 3 == 0
+    assert np.all(got["state"] == pa.StatusCode.ErrorOutsideTimeInterval)
+    assert np.all(got["t"][early] == 10800.0) and np.all(got["t"][~early] == 13500.0)
+    ref = nu.load_fixture("nv_l_partial_time_end")[0]
+    assert np.all(ref["t"][early] == 10800.0) and np.all(ref["t"][~early] == 13500.0)
+
+
+def test_m_two_vectors_in_one_list(gpu):
+    pset, got = _check("nv_m_two_vectors")
+    prog = pset._kernel.user_program
+    assert got["ei"].shape == (65, 2) and np.ptp(got["ei"][:, 0]) > 0 and np.ptp(got["ei"][:, 1]) > 0
+    assert not np.array_equal(got["ei"], np.zeros_like(got["ei"]))
+    assert [v[0] for v in prog.vectors] == ["Wind", "UVstokes"] and prog.vectors[0][5] == 1 and prog.vectors[1][5] == 0
+    assert "case 0: eval_vec<double, 1, 1>(" in prog.source and "case 1: eval_vec<double, 0, 0>(" in prog.source
+    moved = _run("nv_j_cgrid_wind")[1]  # (the same currents and wind without the Stokes drift)
+    assert not np.array_equal(got["x"], moved["x"])
+
+
+def test_n_vector_on_a_second_curvilinear_grid_of_a_flat_mesh(gpu):
+    pset, got = _check("nv_n_second_curvilinear")
+    v = pset._kernel.user_program.vectors[0]
+    assert v[0] == "UVstokes" and v[5] == 1 and v[6] == 0 and "eval_vec<double, 1, 0>(" in pset._kernel.user_program.source
+    assert pset.fieldset.UVstokes.igrid == 1 and not pset.fieldset.U.grid.is_curvilinear
+    assert 100 < len(got["x"]) < 130 and np.all(got["state"] < 50) and np.any(got["ei"][:, 1] != 0)
+
+
+def test_o_deletions_in_the_first_a_middle_and_the_last_wavefront(gpu):
+    pset, got = _check("nv_o_blocks")
+    assert np.array_equal(got["particle_id"], np.array([i for i in range(257) if i not in (3, 130, 256)]))
+    spec = dict(SPECS["nv_o_blocks"])
+    gone = []
+    for steps in (2, 5, 8):  # each of the three leaves on a step of its own
+        spec["currents"] = dict(SPECS["nv_o_blocks"]["currents"], runtime=steps * 3600.0)
+        ids = nu.run_case(spec)[1]["particle_id"]
+        gone.append(sorted(set(range(257)) - set(ids.tolist())))
+    assert gone == [[3], [3, 130], [3, 130, 256]]
+
+
+def test_p_detached_sample(gpu):
+    """`fieldset.Wind[t, z, y, x]` without the particles in the key: the wind moves them, and neither `ei` of the wind's grid nor the state
+    is touched -- a list with only the detached kernel leaves both as a list that samples nothing does"""
+    pset, got = _check("nv_p_detached")
+    assert np.all(got["ei"][:, 1] == 0) and np.any(got["ei"][:, 0] != 0)
+    plain = _run("nv_h_stream")  # (not the same wind: only to see that an attached sample does move the second grid's ei)
+    assert np.any(plain[1]["ei"][:, 1] != 0)
+    spec = SPECS["nv_p_detached"]
+    only = nu.run_case(dict(spec, kernels=["WindDetached"]))
+    nothing = nu.run_case(dict(spec, kernels=["NoSample"]))
+    assert only[0]._kernel.jit_report.startswith("compiled") and only[2] is None and nothing[2] is None
+    for c in ("ei", "state", "t", "particle_id"):
+        assert np.array_equal(only[1][c], nothing[1][c]), c
+    assert not np.array_equal(only[1]["x"], nothing[1]["x"])
+
+
 def _report_of(fs, kernels, spatial=np.float64, **where):
     pset = pa.ParticleSet(fs, pclass=pa.get_default_particle(spatial), **where)
     with warnings.catch_warnings():
