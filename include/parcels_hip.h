@@ -712,6 +712,27 @@ int32_t pk_particles_connectivity(pk_ctx* ctx, int32_t grid_id, int32_t levels, 
                                   int64_t n_dest, int32_t path, int64_t* dense_out, int64_t* keys_out, int64_t* counts_out, int64_t max_pairs,
                                   pk_connectivity_info_t* info);
 
+/* ---- the counter-based random stream of user kernels (csrc/pk_random.h, csrc/pk_random.hip) ------------------------------------------------
+ * The reference's stochastic kernels call np.random.normal (_advectiondiffusion.py:37-38): NumPy's global MT19937 stream, which no parallel
+ * engine reproduces.  `pa.random` (parcels_amd/random.py) is a stateless Philox4x32-10 stream instead; this call fills its variates for
+ * many rows at once: `pa.random.uniform(0.5, 1.5, pset)` outside a kernel, on the device-resident columns.
+ *   stream: key (seed, slot, draw), counter (id, bits of t + 0.0) -- the layout at the head of csrc/pk_random.h.  slot >= -1, draw >= 0.
+ *   rows: ids == t == NULL: the bound particles -- particle_id and t are read where they are, n must be their number, the values are written
+ *     in HOST row order (through the row permutation of the cell sort); nothing is written to the particle columns, no launch may be in
+ *     flight.  Otherwise ids and t are n int64 / float64 on the host, copied to the device for the call.
+ *   dist / out (host memory): PK_RANDOM_WORDS 4 * n uint32, the raw words w0 .. w3 of every row; PK_RANDOM_RANDOM u1; PK_RANDOM_UNIFORM
+ *     p0 + (p1 - p0) * u1; PK_RANDOM_STANDARD_NORMAL z; PK_RANDOM_NORMAL p0 + p1 * z; PK_RANDOM_EXPONENTIAL p0 * (-log u1): n float64;
+ *     PK_RANDOM_INTEGERS ilow + ((w0 * span) >> 32), 1 <= span <= 2^32 (checked): n int64.  No fused multiply-add anywhere. */
+#define PK_RANDOM_WORDS 0
+#define PK_RANDOM_RANDOM 1
+#define PK_RANDOM_UNIFORM 2
+#define PK_RANDOM_STANDARD_NORMAL 3
+#define PK_RANDOM_NORMAL 4
+#define PK_RANDOM_EXPONENTIAL 5
+#define PK_RANDOM_INTEGERS 6
+int32_t pk_random_fill(pk_ctx* ctx, int32_t dist, uint64_t seed, int32_t slot, int32_t draw, double p0, double p1, int64_t ilow, uint64_t span,
+                       const int64_t* ids, const double* t, int64_t n, void* out);
+
 /* achieved copy bandwidth probe (device-to-device float4 copy), GB/s; used as a measured roofline denominator */
 int32_t pk_measure_copy_bandwidth(pk_ctx* ctx, int64_t bytes, int32_t iters, double* gbps);
 

@@ -325,6 +325,7 @@ ABI_SYMBOLS = [
     "pk_particles_density",
     "pk_particles_cells",
     "pk_particles_connectivity",
+    "pk_random_fill",
     "pk_measure_copy_bandwidth",
     "pk_set_option",
     "pk_upload_stats",
@@ -452,6 +453,8 @@ def load():
     lib.pk_particles_cells.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
     lib.pk_particles_connectivity.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                               C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ConnectivityInfo)]
+    lib.pk_random_fill.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int64, C.c_uint64, C.c_void_p,
+                                   C.c_void_p, C.c_int64, C.c_void_p]
     if lib.pk_abi_version() != PK_ABI_VERSION:
         raise HipLibraryError(f"ABI version mismatch: library {lib.pk_abi_version()}, binding {PK_ABI_VERSION}")
     _lib = lib

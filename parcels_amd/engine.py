@@ -1305,6 +1305,34 @@ def _engine_density(self, data, igrid, levels=False, weight_var=None, weight_hos
 DeviceEngine.density = _engine_density
 
 
+def _engine_random_fill(self, dist, seed, slot, draw, p0=0.0, p1=0.0, ilow=0, span=1, ids=None, t=None):
+    """Variates of the `pa.random` stream (seed, slot, draw) computed on the device (pk_random_fill; parcels_amd/random.py has the codes of
+    `dist`).  ids / t None: for the bound rows -- the caller made them current (make_current_for_reading) --, read where they are, returned in
+    host row order; else for the int64 / float64 arrays given.  -> float64 [n], int64 [n] (integers) or uint32 [n, 4] (the raw words)."""
+    from . import random as _random
+
+    if (ids is None) != (t is None):
+        raise ValueError("random_fill: ids and t go together")
+    if ids is None:
+        bound = self._bound
+        n = len(bound.raw("particle_id") if isinstance(bound, LazyColumns) else bound["particle_id"])
+    else:
+        ids, t = np.ascontiguousarray(ids, dtype=np.int64), np.ascontiguousarray(t, dtype=np.float64)
+        if ids.ndim != 1 or ids.shape != t.shape:
+            raise ValueError(f"random_fill: ids and t must be 1-d arrays of one length. Got {ids.shape} and {t.shape}")
+        n = ids.shape[0]
+    if dist == _random.PK_RANDOM_WORDS:
+        out = np.empty((n, 4), np.uint32)
+    else:
+        out = np.empty(n, np.int64 if dist == _random.PK_RANDOM_INTEGERS else np.float64)
+    self.ctx.check(self.lib.pk_random_fill(self.ctx.handle, int(dist), int(seed) & 0xFFFFFFFFFFFFFFFF, int(slot), int(draw), float(p0), float(p1), int(ilow),
+                                           int(span), _ptr(ids), _ptr(t), n, _ptr(out)), "pk_random_fill")
+    return out
+
+
+DeviceEngine.random_fill = _engine_random_fill
+
+
 _LABEL_DTYPES = {np.dtype(np.int32): _hip.PK_DENSITY_I32, np.dtype(np.int64): _hip.PK_DENSITY_I64}
 CONNECTIVITY_LDS_BINS = 8192  # DENS_LDS_BINS of csrc/pk_density_cell.h: the keys a workgroup-private histogram holds
 _CONNECTIVITY_PATHS = {"lds": _hip.PK_CONN_LDS, "global": _hip.PK_CONN_GLOBAL, "sparse": _hip.PK_CONN_SPARSE}

@@ -86,8 +86,11 @@ class _Column(np.lib.mixins.NDArrayOperatorsMixin):
 class HostParticles:
     """The ``particles`` argument of a Python kernel: a selection of rows of the particle set's columns."""
 
-    def __init__(self, data: dict, rows, by_mask=False):
+    def __init__(self, data: dict, rows, by_mask=False, rng=None):
         object.__setattr__(self, "_data", data)
+        # what `pa.random` draws with in this kernel invocation (random.DrawContext: seed, kernel position, draws made so far); every
+        # selection made from this view shares it, so the draw index counts the calls whatever selection each was for
+        object.__setattr__(self, "_rng", rng)
         object.__setattr__(self, "_rows", np.asarray(rows, dtype=np.int64))
         # len() in the reference is `len(self._index)` (particlesetview.py:83-84), and what a kernel receives is a BOOLEAN mask over the whole
         # set -- as is every selection made from it, by mask or by integer indices (:44-74: `new_index[sel] = True`): len(particles) and
@@ -115,10 +118,10 @@ class HostParticles:
         sub = np.asarray(sub) if isinstance(sub, (list, np.ndarray)) else sub
         if isinstance(sub, np.ndarray) and sub.dtype == bool and sub.shape[0] != len(self._rows):
             if sub.shape[0] == len(self._data["particle_id"]):  # a mask over the WHOLE set selects from it, whatever this selection was
-                return HostParticles(self._data, np.flatnonzero(sub), by_mask=self._by_mask)  # (particlesetview.py:48-52: `new_index = arr`)
+                return HostParticles(self._data, np.flatnonzero(sub), by_mask=self._by_mask, rng=self._rng)  # (particlesetview.py:48-52: `new_index = arr`)
             raise IndexError(f"boolean index of length {sub.shape[0]} for a selection of {len(self._rows)} particles")
         rows = self._rows[sub]
-        return HostParticles(self._data, np.atleast_1d(rows), by_mask=self._by_mask)
+        return HostParticles(self._data, np.atleast_1d(rows), by_mask=self._by_mask, rng=self._rng)
 
     def __len__(self):
         return len(self._data["particle_id"]) if self._by_mask else len(self._rows)
@@ -145,6 +148,7 @@ def execute_hosted(kernel, pset, endtime, dt):
     """Kernel.execute (kernel.py:174-247) for a kernel list that contains Python functions.  Host columns in, host columns out
     (the caller re-uploads); returns the statistics dict of a launch."""
     from . import _hip, kernels as _k
+    from .random import DrawContext
     import ctypes as C
 
     engine = None  # created when a built-in kernel of the list needs the device (a list of Python functions alone never does)
@@ -182,7 +186,7 @@ def execute_hosted(kernel, pset, endtime, dt):
     for slot, f in enumerate(kernel._kernels):
         kid = _k.kernel_id(f)
         if kid is None:
-            segments.append(("py", f))
+            segments.append(("py", f, slot))
         elif segments and segments[-1][0] == "dev":
             segments[-1][1].append(kid)
             segments[-1][2].append(slot)
@@ -210,10 +214,11 @@ def execute_hosted(kernel, pset, endtime, dt):
                     device_segment(seg[1], samples, ev)  # the device runs its own Repeat loop per kernel
                     d = pset._data
                 else:
-                    seg[1](HostParticles(d, rows, by_mask=True), fs)
+                    # (a draw context per invocation: `pa.random` counts the draws of ONE call of the function, at the kernel's position)
+                    seg[1](HostParticles(d, rows, by_mask=True, rng=DrawContext(pset.seed, seg[2])), fs)
                     rep = d["state"] == int(StatusCode.Repeat)
                     while rep.any():
-                        seg[1](HostParticles(d, np.flatnonzero(rep), by_mask=True), fs)
+                        seg[1](HostParticles(d, np.flatnonzero(rep), by_mask=True, rng=DrawContext(pset.seed, seg[2])), fs)
                         rep = d["state"] == int(StatusCode.Repeat)
         upd = ev & np.isin(d["state"], (int(StatusCode.Evaluate), int(StatusCode.Success)))  # :219-222
         if upd.any():  # _position_update (:108-120), storage-dtype arithmetic of the columns

@@ -8,9 +8,18 @@ module translates the function's AST into one more kernel of the fused step loop
 statements up to a field sample, the sample, the statements after it), compiles the kernel-list interpreter with it for the one program
 variant the FieldSet needs (``hipcc``, ~5 s, cached on disk by content hash) and registers the module with the library
 (``pk_set_user_program``); the kernel list then runs as ONE launch, built-in and user kernels alike, the particle columns never leave
-the GPU.  Anything outside the class (``NotTranslatable``: control flow, reductions, ``len(particles)``, random numbers, transcendental
+the GPU.  Anything outside the class (``NotTranslatable``: control flow, reductions, ``len(particles)``, ``np.random``, transcendental
 functions, more than PK_MAX_EXTRA touched Variables, ...) keeps running through ``hostkernels.py`` -- the
 reference's loop on the host columns.
+
+RANDOM NUMBERS compile when they come from ``pa.random`` (parcels_amd/random.py): ``pa.random.random(particles)``, ``uniform``,
+``standard_normal``, ``normal``, ``exponential``, ``integers`` -- spelled ``pa.random.x``, ``parcels_amd.random.x`` or through
+``from parcels_amd import random as prandom`` -- are recognised by identity and become an inline call of csrc/pk_random.h over the
+launch's seed, the kernel's position in the list, ``p.id`` and ``p.t``: no request, no stage.  The draw index is the call site's ordinal in
+evaluation order, which equals the host path's call counter only when every call executes in every invocation -- a draw inside a block
+whose whole-set test is dropped (``if np.any(mask): ...``) is NotTranslatable.  The result is an array on the selection of the last
+argument; parameter arrays must live on that selection.  A kernel repeated at the same ``t`` (RK45 Repeat) draws the same numbers again,
+as the built-in stochastic kernels do.  ``np.random.*`` draws from NumPy's global stream, which no parallel engine reproduces: host path.
 
 NumPy's semantics are reproduced statically, per expression: every sub-expression carries its NumPy dtype (NEP 50: Python scalars
 are weak), an operation is computed in ``np.result_type`` of its operands (``float32 + float32`` is a float add, ``int32 + float32``
@@ -225,6 +234,8 @@ class _Translator(ast.NodeVisitor):
         self.detached = False  # some sample is taken without the particles (state and `ei` untouched)
         self.sigma = False  # the kernel calls convert_z_to_sigma_croco: its module carries the CROCO sigma loop (csrc/pk_sigma.h)
         self.aliases: set[str] = set()  # locals bound to a bare `particles.<var>`: a write-through view on the host, not a temporary
+        self.draws = 0  # `pa.random` calls translated so far: the draw index of the next one (the host path counts the calls it makes)
+        self.dropped_if = 0  # depth of blocks whose whole-set test was dropped: the host may skip them, so no draw may sit there
         self.nslot = 0
 
     # ---- helpers -------------------------------------------------------------------------------------------------------------
@@ -738,11 +749,53 @@ class _Translator(ast.NodeVisitor):
             return "abs"
         return None
 
+    def draw(self, node, name, nparam):
+        """`pa.random.<name>(<parameters>, particles)` -> an inline call of csrc/pk_random.h: a float64 (integers: int64) array on the selection of
+        the last argument.  Python evaluates the parameters, then the selection, then makes the call: the draw index is taken last."""
+        who = f"pa.random.{name}"
+        if self.dropped_if:
+            raise NotTranslatable(f"{who} inside a block whose whole-set test is dropped (`if np.any(mask): ...`): the host path skips the block when "
+                                  "the selection is empty, and every later draw of the invocation would take another index")
+        if node.keywords:
+            raise NotTranslatable(f"{who} with keyword arguments (stream= goes with a ParticleSet, outside a kernel)")
+        if len(node.args) != nparam + 1:
+            raise NotTranslatable(f"{who} takes {nparam} parameter(s) and the particles. Got {len(node.args)} arguments")
+        if not self.is_selection(node.args[-1]):
+            raise NotTranslatable(f"{who}: the last argument must be the kernel's particles or a selection of them")
+        depth = len(self._kids)
+        self._kids.append([])
+        try:
+            params = [self.expr(a) for a in node.args[:-1]]
+        finally:
+            del self._kids[depth:]
+        view = self.view_of(node.args[-1])
+        for v in params:
+            if v.array and v.dom != view.dom:
+                raise NotTranslatable(f"{who}: a parameter array over another selection of the particles than the one drawn for")
+        index, self.draws = self.draws, self.draws + 1
+        stream = f"a.prm.seed, kslot, {index}, p.id, p.t"
+        if name == "integers":
+            if any(v.array or v.const is None or v.ty not in ("wi", "i32", "i64") for v in params):
+                raise NotTranslatable(f"{who}: low and high must be integer constants of the run (the span is checked before the launch)")
+            low, span = int(params[0].const), int(params[1].const) - int(params[0].const)
+            if not (1 <= span <= 2**32) or not (-2**63 <= low < 2**63):
+                raise NotTranslatable(f"{who}: high - low must lie in [1, 2**32] (the host path raises the ValueError)")
+            return _V(f"random_integers({stream}, (int64_t){low & 0xFFFFFFFFFFFFFFFF}ULL, {span}ULL)", "i64", array=True, dom=view.dom, explicit=True)
+        if any(v.ty in ("b", "wb") for v in params):
+            raise NotTranslatable(f"{who}: a boolean parameter")
+        args = "".join(f", {_cast(v, 'f64')}" if v.ty not in _WEAK else f", ((double)({v.code}))" for v in params)
+        return _V(f"random_{name}({stream}{args})", "f64", array=True, dom=view.dom, explicit=True)
+
     def e_Call(self, node):
+        from . import random as _random
         from .kernels import convert_z_to_sigma_croco
 
-        if self.callee(node.func) is convert_z_to_sigma_croco:
+        fn = self.callee(node.func)
+        if fn is convert_z_to_sigma_croco:
             return self.conversion(node)
+        drawn = next((v for f, v in _random._FUNCTIONS.items() if f is fn), None)
+        if drawn is not None:
+            return self.draw(node, *drawn)
         name = self.np_func(node)
         if name is None or node.keywords:
             raise NotTranslatable("call of something other than a supported numpy function")
@@ -1098,10 +1151,12 @@ class _Translator(ast.NodeVisitor):
                         continue
                     if not when_empty and sel is not None:
                         self.confined.append(sel)
+                        self.dropped_if += 1
                         try:
                             self.run_body(st.body, top=False)
                         finally:
                             self.confined.pop()
+                            self.dropped_if -= 1
                         continue
                 raise NotTranslatable("`if` on something other than a constant of the run (elementwise code has no control flow)")
             if isinstance(st, ast.AugAssign):
@@ -1226,6 +1281,7 @@ struct PkUserLocals {{
 }};
 }}
 #include "pk_kernels.h"
+#include "pk_random.h"
 namespace pk {{
 PK_DEV bool user_prepare(const KArgs& a, int uk, int stage, int kslot, PCtx& c, PState& p, KLocal& L, Request& rq) {{
     switch (uk) {{
@@ -1266,6 +1322,7 @@ struct PkUserLocals {{
 }};
 }}
 #include "pk_ux.h"
+#include "pk_random.h"
 namespace pk {{
 PK_DEV bool user_prepare(const KArgs& a, int uk, int stage, int kslot, PCtx& c, PState& p, KLocal& L, Request& rq) {{
     switch (uk) {{
@@ -1301,6 +1358,7 @@ struct PkUserLocals {{
 }};
 }}
 #include "pk_sigma.h"
+#include "pk_random.h"
 namespace pk {{
 PK_DEV bool user_prepare(const KArgs& a, int uk, int stage, int kslot, PCtx& c, PState& p, KLocal& L, Request& rq) {{
     switch (uk) {{
