@@ -38,6 +38,12 @@ typedef struct pk_ctx pk_ctx;
 /* dtype tags */
 #define PK_F32 0
 #define PK_F64 1
+/* raw dtypes of a CF-packed level (pk_pack_desc.raw_dtype) */
+#define PK_I8 2
+#define PK_U8 3
+#define PK_I16 4
+#define PK_U16 5
+#define PK_I32 6
 
 /* StatusCode (statuscodes.py:19-34) */
 #define PK_SUCCESS 0
@@ -135,6 +141,11 @@ const char* pk_last_error(const pk_ctx* ctx); /* ctx may be NULL: error of the l
  *   "fast_grid"        workgroups of the persistent launch of the level-pair-cache kernel, whose wavefronts claim chunks of 64 rows until none is
  *                      left (csrc/pk_kernels.h: fast_claim): 0 (default) as many as are resident at once, v > 0 at most v (tests and
  *                      sweeps: results do not depend on it)
+ *   "unpack_chunk_values"  packed integer levels (pk_field_upload_level_packed / _group_level_packed) only: the most values per component
+ *                      of one staged chunk -- 0 (default) what fits a staging chunk (the whole level for a blocking upload), v > 0 rounded
+ *                      down to a multiple of 16, at least 16 (tests cross chunk boundaries at tiny sizes; results do not depend on it)
+ *   "unpack_timing"    0 (default); 1 = HIP events around the DMA and the decode kernel of every such chunk (pk_unpack_stats reads them; a
+ *                      measurement switch: every 256 chunks the host waits for the copy stream to read them)
  * Environment variables PK_NO_FAST, PK_NO_FAST_CGRID, PK_NO_VELOCITY_PAIRS, PK_NO_SPECIAL, PK_NO_CELL_CACHE, PK_NO_HASH_DIR, PK_NO_CELL_TABLE, PK_SORT_HORIZONTAL give the initial
  * values. */
 int32_t pk_set_option(pk_ctx* ctx, const char* name, int32_t value);
@@ -145,6 +156,12 @@ int32_t pk_set_option(pk_ctx* ctx, const char* name, int32_t value);
  * out4[3] the number of staging threads.  The reference's counterpart is the time WindowedArray spends materialising levels
  * (src/parcels/_core/_windowed_array.py:56-97); it keeps no such counter. */
 int32_t pk_upload_stats(pk_ctx* ctx, double* out4);
+
+/* Accounting of the packed integer levels, cumulative since pk_init: out4[0] levels that took pk_field_upload_level_packed /
+ * _group_level_packed (a group level counts once), out4[1] their raw bytes, and with option "unpack_timing" out4[2] milliseconds of the
+ * chunks' DMAs, out4[3] milliseconds of their decode kernels (HIP events on the copy stream; the call waits for that stream when events
+ * are outstanding, it commits nothing). */
+int32_t pk_unpack_stats(pk_ctx* ctx, double* out4);
 
 /* Host-only self-test of the staging fills behind pk_field_upload_group_level (float / double, 2 / 3 planes, AVX2 body and scalar
  * tail, one thread and the pool) against the plain loop: 0 = all equal.  Needs no device. */
@@ -288,6 +305,37 @@ int32_t pk_field_sync(pk_ctx* ctx); /* wait for the copy stream and commit every
 int32_t pk_field_evict_outside(pk_ctx* ctx, int32_t field_id, int32_t lo_level, int32_t hi_level);
 /* which committed level each ring slot currently holds (-1 = empty/pending); `levels` has room for nslots ints */
 int32_t pk_field_slots(pk_ctx* ctx, int32_t field_id, int32_t* levels, int32_t* nslots);
+
+/* ---- CF-packed integer levels: unpacked on the device (csrc/pk_unpack.hip) ------------------------------
+ * What xarray's CF decoding gives the reference's fields (xr.open_dataset: _FillValue / missing_value -> NaN, raw * scale_factor +
+ * add_offset in the float dtype of xarray/coding/variables.py: _choose_float_dtype), and the NaN -> 0 of model.py:135-143, done by a
+ * decode kernel on the copy stream instead of NumPy passes on the host: the raw integers cross PCIe (1/2 .. 1/8 of the bytes) and the
+ * kernel writes the field's final layout.  Per value: a fill value gives NaN; else (compute)raw * scale, then + offset, two separately
+ * rounded operations in compute_dtype (never an FMA: the bits of parcels_amd/sources.py: cf_unpack); NaN -> 0 with nan_to_zero; then the
+ * exact widening to the field's dtype when that is float64 and compute_dtype float32. */
+typedef struct pk_pack_desc {
+    int32_t raw_dtype;     /* PK_I8 | PK_U8 | PK_I16 | PK_U16 | PK_I32                                              */
+    int32_t compute_dtype; /* PK_F32 | PK_F64: the dtype the two roundings happen in; not wider than the field's    */
+    int32_t has_scale, has_offset; /* the attribute is present (an absent one is no operation, not * 1 / + 0)       */
+    double scale, offset;  /* already cast to compute_dtype (a float32 attribute is exact in a double)              */
+    int32_t nfill;         /* 0..4 fill values                                                                      */
+    int32_t nan_to_zero;   /* the model's fill_nan                                                                  */
+    int64_t fill[4];       /* one the raw dtype cannot hold never matches                                           */
+} pk_pack_desc;
+/* pk_field_upload_level for a packed level: `raw` holds nz*ny*nx values of desc->raw_dtype, C order, native byte order.  Slot
+ * bookkeeping, eviction and `async` exactly as pk_field_upload_level; with async the raw bytes go through the pinned staging ring (so
+ * pk_upload_stats counts raw bytes, each plane of a chunk padded to 16) and the decode of a chunk follows its DMA on the copy stream.
+ * Fails with a message for a compute_dtype wider than the field's dtype.  A field of a packed group may be uploaded alone (element-wise
+ * strided stores); the group call below writes whole structs. */
+int32_t pk_field_upload_level_packed(pk_ctx* ctx, int32_t field_id, int32_t level, const void* raw, const pk_pack_desc* desc, int32_t async);
+/* pk_field_upload_group_level for packed levels: raw[k] / descs[k] belong to the k-th component in creation order; ONE decode launch per
+ * chunk writes the {U,V[,W]} structs.  The components have their own scale, offset and fill values but must share raw_dtype and
+ * compute_dtype, and a group has at most 3 of them: anything else fails with a message (the caller unpacks on the host). */
+int32_t pk_field_upload_group_level_packed(pk_ctx* ctx, int32_t leader_field_id, int32_t level, const void* const* raw,
+                                           const pk_pack_desc* descs, int32_t ncomp, int32_t async);
+/* A committed level back on the host as the plain (nz, ny, nx) array of the field's dtype, de-interleaved for a field of a packed group;
+ * fails with a message when the level is not resident (a pending one is not: pk_field_sync first).  For tests and debugging. */
+int32_t pk_field_download_level(pk_ctx* ctx, int32_t field_id, int32_t level, void* out);
 
 /* ---- particles: the SoA dict of ParticleSet (particle.py:182-222) -------------------------------- */
 typedef struct pk_particles_desc {

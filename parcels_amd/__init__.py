@@ -56,7 +56,7 @@ from .particlefile import ParticleFile, read_particlefile
 from .compat_v3 import particlefile_to_v3_zarr
 from .particleset import ParticleSet, ParticleSetWarning
 from .sgrid import FaceNodePadding, Padding, SGrid2DMetadata
-from .sources import LevelSource, NetCDFLevels, NpyLevels, ZarrLevels, read_netcdf_variable
+from .sources import LevelSource, NetCDFLevels, NpyLevels, PackedArrayLevels, ZarrLevels, read_netcdf_variable
 from .statuscodes import (
     AllParcelsErrorCodes,
     FieldInterpolationError,

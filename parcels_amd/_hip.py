@@ -19,6 +19,7 @@ PK_USER_RIDE, PK_USER_SAMPLES_UV, PK_USER_SAMPLES_UVW, PK_USER_UX, PK_USER_KEY_U
 # ... and of a module that carries the CROCO sigma loop: keys PK_USER_KEY_SIGMA + (float32 fields ? 4 : 0) + (curvilinear ? 2 : 0) + interp_uv
 PK_USER_SIGMA, PK_USER_KEY_SIGMA = 16, 16
 PK_F32, PK_F64 = 0, 1
+PK_I8, PK_U8, PK_I16, PK_U16, PK_I32 = 2, 3, 4, 5, 6  # raw dtypes of a CF-packed level (pk_pack_desc.raw_dtype)
 PK_MAX_GRIDS, PK_MAX_FIELDS, PK_MAX_KERNELS, PK_NUM_STATE_CODES = 4, 64, 8, 80
 PK_MAX_EXTRA = 8
 PK_MAX_TWE = 1024
@@ -151,6 +152,20 @@ class FieldDesc(C.Structure):
     ]
 
 
+class PackDesc(C.Structure):  # pk_pack_desc
+    _fields_ = [
+        ("raw_dtype", C.c_int32),
+        ("compute_dtype", C.c_int32),
+        ("has_scale", C.c_int32),
+        ("has_offset", C.c_int32),
+        ("scale", C.c_double),
+        ("offset", C.c_double),
+        ("nfill", C.c_int32),
+        ("nan_to_zero", C.c_int32),
+        ("fill", C.c_int64 * 4),
+    ]
+
+
 class ParticlesDesc(C.Structure):
     _fields_ = [
         ("n", C.c_int64),
@@ -278,6 +293,9 @@ ABI_SYMBOLS = [
     "pk_field_create",
     "pk_field_upload_level",
     "pk_field_upload_group_level",
+    "pk_field_upload_level_packed",
+    "pk_field_upload_group_level_packed",
+    "pk_field_download_level",
     "pk_field_sync",
     "pk_field_slots",
     "pk_field_evict_outside",
@@ -329,6 +347,7 @@ ABI_SYMBOLS = [
     "pk_measure_copy_bandwidth",
     "pk_set_option",
     "pk_upload_stats",
+    "pk_unpack_stats",
     "pk_host_stage_selftest",
     "pk_particles_snapshot_filtered",
     "pk_comm_unique_id",
@@ -453,6 +472,10 @@ def load():
     lib.pk_particles_cells.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
     lib.pk_particles_connectivity.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                               C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ConnectivityInfo)]
+    lib.pk_field_upload_level_packed.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(PackDesc), C.c_int32]
+    lib.pk_field_upload_group_level_packed.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(PackDesc), C.c_int32, C.c_int32]
+    lib.pk_field_download_level.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.pk_unpack_stats.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.pk_random_fill.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int64, C.c_uint64, C.c_void_p,
                                    C.c_void_p, C.c_int64, C.c_void_p]
     if lib.pk_abi_version() != PK_ABI_VERSION:
@@ -501,6 +524,12 @@ class Context:
         out = (C.c_double * 4)()
         self.check(self.lib.pk_upload_stats(self.handle, out), "pk_upload_stats")
         return {"stage_fill_s": out[0], "stage_wait_s": out[1], "stage_bytes": out[2], "stage_threads": int(out[3])}
+
+    def unpack_stats(self) -> dict:
+        """Accounting of the packed integer levels since pk_init (include/parcels_hip.h: pk_unpack_stats)."""
+        out = (C.c_double * 4)()
+        self.check(self.lib.pk_unpack_stats(self.handle, out), "pk_unpack_stats")
+        return {"levels": int(out[0]), "raw_bytes": out[1], "dma_ms": out[2], "decode_ms": out[3]}
 
     def copy_bandwidth(self, nbytes: int = 1 << 30, iters: int = 10) -> float:
         g = C.c_double()

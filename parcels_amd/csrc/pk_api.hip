@@ -207,12 +207,12 @@ __global__ void __launch_bounds__(256) copy_kernel(const float4* __restrict__ sr
 // pageable -> pinned staging: a ring of PK_STAGE_BUFFERS fixed-size pinned chunks (allocated once; pinning a whole 4 GB level costs
 // ~1 s).  The host fills chunk k+1 (pk_host_stage.cpp: persistent thread pool, AVX2 interleave, non-temporal stores) while chunk k
 // is on the wire; a third chunk keeps the DMA queue from draining while the fill of the next one is being handed to the pool.
-constexpr size_t PK_STAGE_CHUNK_BYTES = (size_t)256 << 20;
 using pkhost::parallel_interleave;
 using pkhost::parallel_memcpy;
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+namespace pkapi {
 // the next staging chunk, free of its previous DMA (blocks on that DMA's event; the wait is accounted in stage_wait_s)
-static int32_t stage_acquire(pk_ctx* ctx, int* out) {
+int32_t stage_acquire(pk_ctx* ctx, int* out) {
     const int k = ctx->stage_next;
     ctx->stage_next = (k + 1) % PK_STAGE_BUFFERS;
     if (!ctx->stage[k]) {
@@ -227,12 +227,13 @@ static int32_t stage_acquire(pk_ctx* ctx, int* out) {
     *out = k;
     return 0;
 }
-static int32_t stage_submit(pk_ctx* ctx, int k, void* dst, size_t bytes) {
+int32_t stage_submit(pk_ctx* ctx, int k, void* dst, size_t bytes) {
     PK_HIP(ctx, hipMemcpyAsync(dst, ctx->stage[k], bytes, hipMemcpyHostToDevice, ctx->copy));
     PK_HIP(ctx, hipEventRecord(ctx->stage_ev[k], ctx->copy));
     ctx->stage_bytes_total += (double)bytes;
     return 0;
 }
+}  // namespace pkapi
 
 // DGrid::cell_tab: one record per cell, written by the device functions the search would otherwise run on every cache miss
 // (identical instruction sequences, so the values are the ones the per-miss computation produces)
@@ -434,6 +435,11 @@ int32_t pk_set_option(pk_ctx* ctx, const char* name, int32_t value) {
         if (value < 0) return ctx->fail("pk_set_option: fast_grid is 0 (planned) or the largest number of workgroups of the persistent A-grid launch");
         ctx->fast_grid = value;
     }
+    else if (n == "unpack_chunk_values") {
+        if (value < 0) return ctx->fail("pk_set_option: unpack_chunk_values is 0 (what fits a staging chunk) or the most values per staged chunk of a packed level");
+        ctx->unpack_chunk_values = value == 0 ? 0 : std::max(16, value / 16 * 16);
+    }
+    else if (n == "unpack_timing") ctx->unpack_timing = value != 0;
     else return ctx->fail("pk_set_option: unknown option '" + n + "'");
     return 0;
 }
@@ -477,6 +483,9 @@ int32_t pk_destroy(pk_ctx* ctx) {
         if (sn.done) (void)hipEventDestroy(sn.done);
     }
     if (ctx->d_pack_tmp) (void)hipFree(ctx->d_pack_tmp);
+    if (ctx->d_unpack_tmp) (void)hipFree(ctx->d_unpack_tmp);
+    for (hipEvent_t e : ctx->unpack_ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->unpack_ev_free) (void)hipEventDestroy(e);
     if (ctx->tab_a.d) (void)hipFree(ctx->tab_a.d);
     if (ctx->tab_c.d) (void)hipFree(ctx->tab_c.d);
     if (ctx->d_ct2) (void)hipFree(ctx->d_ct2);

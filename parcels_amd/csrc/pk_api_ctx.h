@@ -90,6 +90,7 @@ constexpr bool col_bits_in_table_order() {
 static_assert(col_bits_in_table_order(), "the table lists the columns in the bit order of the PK_COL_* masks (parcels_hip.h)");
 
 constexpr int PK_STAGE_BUFFERS = 3;  // pinned staging chunks of the level stream (see stage_acquire)
+constexpr size_t PK_STAGE_CHUNK_BYTES = (size_t)256 << 20;  // the most one of them holds
 
 // device scratch of the write filter (pk_api.hip: select_flags): flag per host row, exclusive scan of the flags
 struct PkSelect {
@@ -136,6 +137,15 @@ struct pk_ctx {
     size_t sort_tmp_bytes = 0;
     void* d_pack_tmp = nullptr;  // device staging of one field level before it is interleaved into a packed group
     size_t pack_tmp_bytes = 0;
+    // packed integer levels (pk_unpack.hip): device staging of the raw planes of one chunk -- the copy stream is ordered, so the decode of
+    // chunk k has read it before the DMA of chunk k + 1 lands -- and the knobs / counters of that path
+    void* d_unpack_tmp = nullptr;
+    size_t unpack_tmp_bytes = 0;
+    int64_t unpack_chunk_values = 0;  // option "unpack_chunk_values": cap of the values per staged chunk, 0 = what fits a staging chunk
+    int unpack_timing = 0;            // option "unpack_timing": HIP events around every chunk's DMA and decode (pk_unpack_stats)
+    std::vector<hipEvent_t> unpack_ev;      // three per timed chunk, not yet read: before the DMA, between DMA and decode, after the decode
+    std::vector<hipEvent_t> unpack_ev_free;
+    double unpack_dma_ms = 0, unpack_decode_ms = 0, unpack_levels = 0, unpack_raw_bytes = 0;
     // scratch
     DCounters* d_counters = nullptr;
     // device copy of the grid / field descriptors the kernels read through KArgs::grids / fields (pk_device.h), and its pinned source
@@ -293,6 +303,10 @@ void swap_column_sets(pk_ctx* ctx);
 void scatter_rows(pk_ctx* ctx, const ColRef& c, void* dst, int64_t n);
 int32_t select_flags(pk_ctx* ctx, double t, int apply_filter, int64_t* n_sel);
 void select_column(pk_ctx* ctx, const ColRef& c, void* dst);
+
+// pk_api.hip: the pinned staging ring of the level stream
+int32_t stage_acquire(pk_ctx* ctx, int* out);
+int32_t stage_submit(pk_ctx* ctx, int k, void* dst, size_t bytes);
 
 // pk_api.hip: the launch planner
 bool ctx_is_typed(const pk_ctx* ctx);

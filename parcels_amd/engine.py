@@ -70,6 +70,37 @@ class _LazyLevels:
             a = np.nan_to_num(a, nan=0.0)
         return np.ascontiguousarray(a, dtype=self.dtype)
 
+    @property
+    def packing(self):
+        """The source's ``Packing`` (parcels_amd.sources.cf_packing) when the device can unpack its levels into this field's dtype."""
+        pk = getattr(self.src, "packing", None)
+        if pk is None or not hasattr(self.src, "read_level_packed") or np.dtype(pk.compute_dtype).itemsize > self.dtype.itemsize:
+            return None
+        return pk
+
+    def packed(self, level):
+        """``(raw, Packing)``: the raw integers of the level for the device to unpack (csrc/pk_unpack.hip) -- or None: this level (or every
+        level of this source) is unpacked on the host by ``__getitem__``."""
+        pk = self.packing
+        raw = self.src.read_level_packed(int(level)) if pk is not None else None
+        if raw is None:
+            return None
+        raw = np.ascontiguousarray(raw, dtype=pk.raw_dtype)
+        if tuple(raw.shape) != self.shape[1:]:
+            raise ValueError(f"packed level {level} of {type(self.src).__name__} has shape {raw.shape}, expected {self.shape[1:]}")
+        return raw, pk
+
+    def pack_desc(self, pk):
+        d = _hip.PackDesc()
+        d.raw_dtype = {"int8": _hip.PK_I8, "uint8": _hip.PK_U8, "int16": _hip.PK_I16, "uint16": _hip.PK_U16, "int32": _hip.PK_I32}[np.dtype(pk.raw_dtype).name]
+        d.compute_dtype = _hip.PK_F64 if np.dtype(pk.compute_dtype) == np.float64 else _hip.PK_F32
+        d.has_scale, d.has_offset = int(pk.scale is not None), int(pk.offset is not None)
+        d.scale, d.offset = pk.scale or 0.0, pk.offset or 0.0
+        d.nfill, d.nan_to_zero = len(pk.fills), int(self.fill_nan)
+        for k, v in enumerate(pk.fills):
+            d.fill[k] = int(v)
+        return d
+
 
 def _timed(total, key, fn, *args):
     """fn(*args), its wall time added to total[key]"""
@@ -125,11 +156,13 @@ class DeviceEngine:
         self.field_ids: dict[str, int] = {}
         self.field_host: dict[str, np.ndarray] = {}
         self.field_nslots: dict[str, int] = {}
+        # what crossed PCIe for the particle columns: calls and column counts (tests and bench.py's `repeat_execute` leg read it); and the
+        # field levels of level sources: unpacked from raw integers on the device (levels_packed) or converted on the host (levels_unpacked)
+        self.transfers = {"h2d_full": 0, "h2d_columns": 0, "d2h_full": 0, "d2h_columns": 0, "columns_up": 0, "columns_down": 0,
+                          "levels_packed": 0, "levels_unpacked": 0}
         self._plan_and_create_fields(nslots, memory_fraction)
         self._bound_sig = None
         self._bound = None
-        # what crossed PCIe for the particle columns: calls and column counts (tests and bench.py's `repeat_execute` leg read it)
-        self.transfers = {"h2d_full": 0, "h2d_columns": 0, "d2h_full": 0, "d2h_columns": 0, "columns_up": 0, "columns_down": 0}
         self.comm = None  # (rank, world) once the context has joined an RCCL communicator (comm_init)
         self.comm_stats = {"gathers": 0, "allreduces": 0}
         self.comm_last_counts = None
@@ -348,13 +381,45 @@ class DeviceEngine:
                     self._upload(f.name, lv, asynchronous=False)
         self.windowed = any(self.field_nslots[f.name] < self.field_host[f.name].shape[0] for f in self.scalar_fields)
 
+    def _packed_levels(self, members, level):
+        """``[(raw, Packing), ...]`` when this level of every member can be unpacked on the device in one call (CF-packed integers of one
+        raw and one compute dtype, parcels_amd.sources; PARCELS_AMD_DEVICE_UNPACK=0 switches the path off), else None.  Per level: a
+        source may decline a single one."""
+        if os.environ.get("PARCELS_AMD_DEVICE_UNPACK", "1") == "0" or len(members) > 3:
+            return None
+        hosts = [self.field_host[m] for m in members]
+        pks = [h.packing if isinstance(h, _LazyLevels) else None for h in hosts]
+        if any(p is None or p.raw_dtype != pks[0].raw_dtype or p.compute_dtype != pks[0].compute_dtype for p in pks):
+            return None
+        got = []
+        for h in hosts:
+            g = h.packed(level)
+            if g is None:
+                return None
+            got.append(g)
+        return got
+
     def _upload(self, name, level, asynchronous):
         leader = self.pack_leader_of.get(name)
+        members = self.pack_groups[leader] if leader is not None else [name]
+        if leader is not None and leader != name:
+            return  # travels with its group leader
+        packed = self._packed_levels(members, level)
+        counts = getattr(self, "transfers", None)
+        if counts is not None and isinstance(self.field_host[name], _LazyLevels):
+            counts["levels_packed" if packed else "levels_unpacked"] += len(members)
+        if packed:  # raw integers to the DMA, unpacked on the copy stream straight into the slot (one launch writes a group's structs)
+            descs = (_hip.PackDesc * len(members))(*[self.field_host[m].pack_desc(pk) for m, (_, pk) in zip(members, packed)])
+            if leader is None:
+                rc = self.lib.pk_field_upload_level_packed(self.ctx.handle, self.field_ids[name], int(level), _ptr(packed[0][0]), descs, int(asynchronous))
+            else:
+                ptrs = (C.c_void_p * len(members))(*[raw.ctypes.data for raw, _ in packed])
+                rc = self.lib.pk_field_upload_group_level_packed(self.ctx.handle, self.field_ids[leader], int(level), ptrs, descs, len(members),
+                                                                 int(asynchronous))
+            self.ctx.check(rc, f"pk_field_upload_level_packed({'+'.join(members)}, {level})")
+            return
         if leader is not None:
-            if leader != name:
-                return  # travels with its group leader
             # packed {U,V,W} group: one call, interleaved by the host threads that stage the level for the DMA anyway
-            members = self.pack_groups[leader]
             lvls = [self.field_host[m][level] for m in members]
             ptrs = (C.c_void_p * len(members))(*[l.ctypes.data for l in lvls])
             self.ctx.check(

@@ -19,9 +19,17 @@ A level source is anything with
 * ``NetCDFLevels`` -- one variable of a NetCDF-4 (HDF5: contiguous or chunked, deflate / shuffle / fletcher32) or classic NetCDF-3
   file, or of a list of such files that continue each other in time (one file per day / month, as models write them); CF packing
   (scale_factor, add_offset, _FillValue, missing_value) is undone.  The reader is parcels_amd/hdf5.py: no netCDF4 / h5py needed.
+* ``PackedArrayLevels`` -- a CF-packed integer array held in memory, with its scale / offset / fill values.
 * ``ZarrLevels`` -- one array of a zarr v2 or v3 directory store on a local filesystem, chunked with ONE time level per chunk along
   the first axis (chunks may split z / y / x), compressor null, zstd, lz4, gzip or blosc (lz4 / zstd / zlib inner codec, byte
   shuffle) -- the formats pyarrow's codecs can decode; no zarr / numcodecs installation is needed.
+
+A source of CF-packed integers (int8 / uint8 / int16 / uint16 / int32 with scale_factor, add_offset, _FillValue / missing_value) also has
+
+    .packing                -> Packing | None   what the device needs to unpack a raw level (``cf_packing``)
+    .read_level_packed(k)   -> the raw integers of level k, C-contiguous, native byte order -- or None: this level takes the host path
+
+and the engine then hands the raw level to the DMA and unpacks it on the GPU (csrc/pk_unpack.hip), with the bits ``read_level`` gives.
 """
 
 from __future__ import annotations
@@ -30,10 +38,12 @@ import glob
 import json
 import os
 import struct
+from collections import namedtuple
 
 import numpy as np
 
-__all__ = ["LevelSource", "NetCDFLevels", "NpyLevels", "ZarrLevels", "is_level_source", "read_netcdf_variable"]
+__all__ = ["LevelSource", "NetCDFLevels", "NpyLevels", "PackedArrayLevels", "Packing", "ZarrLevels", "cf_packing", "is_level_source",
+           "read_netcdf_variable", "unpack_reference"]
 
 
 class LevelSource:
@@ -53,6 +63,15 @@ class LevelSource:
 
     def read_level(self, k: int) -> np.ndarray:  # pragma: no cover - interface
         raise NotImplementedError
+
+    @property
+    def packing(self):
+        """``Packing`` when the levels are CF-packed integers the device can unpack, else None."""
+        return None
+
+    def read_level_packed(self, k: int):
+        """The raw integers of level ``k`` (shape[1:], C-contiguous, native byte order), or None: the level is read with ``read_level``."""
+        return None
 
     def level(self, k: int, dtype=None) -> np.ndarray:
         """Level ``k`` ready for the upload: C-contiguous, target dtype, NaN -> 0."""
@@ -142,6 +161,103 @@ def cf_unpack(a: np.ndarray, attrs: dict, fill_dtype=None) -> np.ndarray:
     return out
 
 
+# What the device needs to unpack a level (csrc/pk_unpack.h): the raw and the compute dtype, scale and offset ALREADY cast to the compute
+# dtype (Python floats: a float32 value is exact in one; None = the attribute is absent), and the fill values the raw dtype can hold
+Packing = namedtuple("Packing", "raw_dtype compute_dtype scale offset fills")
+_PACKED_RAW = tuple(np.dtype(t) for t in (np.int8, np.uint8, np.int16, np.uint16, np.int32))
+
+
+def cf_packing(raw_dtype, attrs):
+    """``Packing`` of a variable of ``raw_dtype`` with the CF attributes ``attrs``, by the rules of ``cf_unpack`` (one
+    ``_choose_float_dtype``: the two cannot disagree on the dtype) -- or None where the device cannot do the job and ``cf_unpack`` does it:
+    a raw dtype other than int8 / uint8 / int16 / uint16 / int32, more than 4 distinct fill values, no packing attribute at all, a scale /
+    offset that is not finite or with which a raw value overflows the compute dtype (``nan_to_num`` then rewrites infinities on the host)."""
+    dt = np.dtype(raw_dtype).newbyteorder("=")
+    if dt not in _PACKED_RAW:
+        return None
+    sf, ao = attrs.get("scale_factor"), attrs.get("add_offset")
+    fv = [np.asarray(attrs[k]).ravel() for k in ("_FillValue", "missing_value") if k in attrs]
+    if sf is None and ao is None and not fv:
+        return None
+    compute = np.dtype(_choose_float_dtype(dt, sf, ao))
+    with np.errstate(over="ignore"):
+        scale = None if sf is None else float(np.asarray(sf, dtype=compute).ravel()[0])
+        offset = None if ao is None else float(np.asarray(ao, dtype=compute).ravel()[0])
+    info = np.iinfo(dt)
+    bound = float(max(-info.min, info.max)) * abs(1.0 if scale is None else scale) + abs(0.0 if offset is None else offset)
+    if not bound < float(np.finfo(compute).max):  # (also NaN)
+        return None
+    given = []
+    for v in fv:
+        if v.dtype.kind not in "iuf":
+            return None
+        for x in v:
+            if v.dtype.kind == "f" and np.isnan(x):
+                continue  # isnan of an integer array: matches nothing
+            x = int(x) if float(x).is_integer() else float(x)
+            if x not in given:
+                given.append(x)
+    if len(given) > 4:
+        return None
+    fills = tuple(x for x in given if isinstance(x, int) and info.min <= x <= info.max)  # the others can never match
+    return Packing(dt, compute, scale, offset, fills)
+
+
+def unpack_reference(raw, packing, out_dtype, fill_nan):
+    """What the device does to a raw level (csrc/pk_unpack.h), in NumPy: fill values -> NaN; ``raw.astype(compute) * scale``, then
+    ``+ offset`` -- two separately rounded operations in the compute dtype; NaN -> 0 with ``fill_nan``; the cast to ``out_dtype``.  Equal
+    bit for bit to ``np.ascontiguousarray(nan_to_num(cf_unpack(raw, attrs)), dtype=out_dtype)``, the host path."""
+    raw = np.asarray(raw)
+    c = np.dtype(packing.compute_dtype)
+    mask = np.zeros(raw.shape, dtype=bool)
+    for f in packing.fills:
+        mask |= raw == raw.dtype.type(f)
+    v = raw.astype(c)
+    if packing.scale is not None:
+        v = v * c.type(packing.scale)
+    if packing.offset is not None:
+        v = v + c.type(packing.offset)
+    v[mask] = np.nan
+    if fill_nan:
+        v[np.isnan(v)] = 0
+    return np.ascontiguousarray(v, dtype=out_dtype)
+
+
+class PackedArrayLevels(LevelSource):
+    """``PackedArrayLevels(raw, scale_factor=np.float32(0.001), add_offset=np.float32(2), fill_values=(-32767,))``: a CF-packed integer
+    array of shape (t, z, y, x) held in memory (or an ``np.memmap``).  ``read_level`` is ``cf_unpack`` on the slice, the dtype follows its
+    rule (give float32 attributes as ``np.float32``: a Python float is a float64 attribute); on the device the raw integers are uploaded and
+    unpacked there."""
+
+    def __init__(self, raw, scale_factor=None, add_offset=None, fill_values=(), fill_nan=True):
+        if getattr(raw, "ndim", None) != 4 or raw.dtype.kind not in "iu":
+            raise ValueError("PackedArrayLevels: an integer array of shape (t, z, y, x) is required")
+        self.raw = raw
+        self.attrs = {}
+        if scale_factor is not None:
+            self.attrs["scale_factor"] = scale_factor
+        if add_offset is not None:
+            self.attrs["add_offset"] = add_offset
+        if len(np.atleast_1d(fill_values)):
+            self.attrs["_FillValue"] = np.atleast_1d(fill_values)
+        self.shape = tuple(int(v) for v in raw.shape)
+        self.dtype = np.dtype(cf_unpack(np.zeros(1, raw.dtype), self.attrs).dtype)
+        self.fill_nan = fill_nan
+        self._packing = cf_packing(raw.dtype, self.attrs)
+
+    @property
+    def packing(self):
+        return self._packing
+
+    def read_level(self, k):
+        return cf_unpack(np.asarray(self.raw[int(k)]), self.attrs)
+
+    def read_level_packed(self, k):
+        if self._packing is None:
+            return None
+        return np.ascontiguousarray(self.raw[int(k)], dtype=self._packing.raw_dtype)
+
+
 def _open_netcdf(path):
     """HDF5File (NetCDF-4) or NetCDF3File (classic) by the magic number."""
     from . import hdf5
@@ -199,6 +315,11 @@ class NetCDFLevels(LevelSource):
         probe = cf_unpack(np.zeros(1, self._vdtype), self.attrs)
         self.dtype = np.dtype(np.float32 if probe.dtype == np.float32 else np.float64)
         self.fill_nan = fill_nan
+        self._packing = cf_packing(self._vdtype, self.attrs)
+
+    @property
+    def packing(self):
+        return self._packing
 
     @staticmethod
     def _has_t(shp, dims):
@@ -217,13 +338,20 @@ class NetCDFLevels(LevelSource):
         d = f.dataset(self.variable)
         return tuple(d.shape), np.dtype(d.dtype).newbyteorder("="), d.attrs
 
-    def read_level(self, k):
+    def _read_raw(self, k):
         fi = int(np.searchsorted(self._offsets, k, side="right") - 1)
         local = int(k - self._offsets[fi])
         f = self._file(fi)
         first = local if self._dims.startswith("t") else None
-        a = f.read(self.variable, first) if hasattr(f, "vars") else f.dataset(self.variable).read(first)
-        return cf_unpack(a, self.attrs).reshape(self.shape[1:])
+        return f.read(self.variable, first) if hasattr(f, "vars") else f.dataset(self.variable).read(first)
+
+    def read_level(self, k):
+        return cf_unpack(self._read_raw(k), self.attrs).reshape(self.shape[1:])
+
+    def read_level_packed(self, k):
+        if self._packing is None:
+            return None
+        return np.ascontiguousarray(self._read_raw(k), dtype=self._packing.raw_dtype).reshape(self.shape[1:])
 
     def close(self):
         for k, f in enumerate(self._files):
@@ -342,6 +470,11 @@ class ZarrLevels(LevelSource):
             raise ValueError(f"expected a (time, [z,] [y,] x) array, got shape {self.zshape}")
         self.shape = (self.zshape[0],) + (1,) * (3 - len(rest)) + tuple(rest)
         self.fill_nan = fill_nan
+        self._packing = cf_packing(self.zdtype, self.attrs)
+
+    @property
+    def packing(self):
+        return self._packing
 
     def _decode(self, raw: bytes) -> bytes:
         c = self.compressor
@@ -364,7 +497,8 @@ class ZarrLevels(LevelSource):
             return zlib.decompress(raw) if cid == "zlib" else zlib.decompress(raw, 31)
         raise ValueError(f"unsupported zarr compressor {cid!r}")
 
-    def read_level(self, k):
+    def _read_raw(self, k):
+        """The stored values of level k and the mask of its `missing` cells (None: none)."""
         rest_shape, rest_chunks = self.zshape[1:], self.chunks[1:]
         out = np.empty(rest_shape, dtype=self.zdtype)
         missing = None  # cells of unwritten chunks of an INTEGER array whose fill value is null / "NaN": NaN after unpacking
@@ -385,6 +519,18 @@ class ZarrLevels(LevelSource):
             buf = self._decode(open(path, "rb").read())
             chunk = np.frombuffer(buf, dtype=self.zdtype, count=int(np.prod(rest_chunks))).reshape(rest_chunks)
             out[sl] = chunk[tuple(slice(0, s.stop - s.start) for s in sl)]
+        return out, missing
+
+    def read_level_packed(self, k):
+        if self._packing is None:
+            return None
+        out, missing = self._read_raw(k)
+        if missing is not None:  # NaN where no raw value says so: this level is unpacked on the host
+            return None
+        return np.ascontiguousarray(out, dtype=self._packing.raw_dtype).reshape(self.shape[1:])
+
+    def read_level(self, k):
+        out, missing = self._read_raw(k)
         out = cf_unpack(out, self.attrs)
         if missing is not None:
             out = out.astype(self.dtype, copy=False)
