@@ -214,7 +214,9 @@ typedef struct pk_grid_desc {
                                 probe instead of ~10; on a mesh WITH coincident nodes the table order is kept, and so it is on
                                 a mesh with a cell whose point-in-cell test is numerically unreliable (a parallelogram to
                                 rounding that still takes the quadratic branch of index_search.py:122-177 -- flat meshes in
-                                metres), because such a cell "contains" points of its neighbours.
+                                metres), because such a cell "contains" points of its neighbours; and so it is on a mesh
+                                with a node strictly inside a cell it is not a corner of (a mesh that covers a region twice
+                                without repeating a node, e.g. a zonal mesh spanning more than 360 degrees).
                                 1 = always probe the neighbour first, -1 = never.                                        */
     double h_bbox[6]; /* xmin,xmax,ymin,ymax,zmin,zmax of the hash grid                             */
 } pk_grid_desc;

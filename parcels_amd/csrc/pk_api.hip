@@ -340,6 +340,47 @@ __global__ void illconditioned_cell_kernel(const pk::DGrid g, int* flag) {
     if (fabs(aa) >= 1e-12 && fabs(aa) < 1e-9 * scale) atomicOr(flag, 1);
 }
 
+// A mesh can cover a region twice without repeating a node: a zonal mesh that spans more than 360 degrees in columns that do not line
+// up with the first ones, say.  Two cells then hold the same point and, as on a mesh with coincident nodes, only the reference's table
+// order decides between them, which the neighbour probe does not ask.  Such a mesh has a node strictly inside a cell it is not a corner
+// of -- strictly by the probe's own margin.  One thread per node walks the faces of the node's hash cell the way a query at the node
+// does (curvilinear_search), with the node's own table coordinates.  Runs before the cell table and the directory exist.
+__global__ void node_in_foreign_cell_kernel(const pk::DGrid g, int* flag) {
+    using namespace pk;
+    const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (node >= (int64_t)g.ny * g.nx) return;
+    const double* r = g.node_tab + node * 5;
+    QPoint q;
+    q.x = r[0];
+    q.y = r[1];
+    q.qX = g.spherical ? r[2] : r[0];
+    q.qY = g.spherical ? r[3] : r[1];
+    q.qZ = g.spherical ? r[4] : 0.0;
+    if (!(isfinite(q.x) && isfinite(q.y) && isfinite(q.qX) && isfinite(q.qY) && isfinite(q.qZ))) return;  // masked
+    const int nj = (int)(node / g.nx), ni = (int)(node % g.nx);
+    const uint32_t code = morton_code(g, q);
+    int64_t lo = 0, hi = g.h_nkeys;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (g.h_keys[mid] < code) lo = mid + 1; else hi = mid;
+    }
+    if (lo >= g.h_nkeys || g.h_keys[lo] != code) return;
+    const int64_t s = g.h_starts[lo], c = g.h_counts[lo];
+    const uint32_t ncx = (uint32_t)(g.nx - 1);
+    const double m = 1e-9;  // curvilinear_search's margin
+    for (int64_t k = 0; k < c; k++) {
+        const uint32_t face = g.h_faces[s + k];
+        const int j = (int)(face / ncx), i = (int)(face % ncx);
+        if (j < 0 || j >= g.ny - 1 || i < 0 || i >= g.nx - 1) continue;
+        if ((j == nj || j == nj - 1) && (i == ni || i == ni - 1)) continue;  // one of its own four cells
+        double xs, et;
+        if (point_in_cell(g, q, j, i, xs, et) && xs > m && xs < 1 - m && et > m && et < 1 - m) {
+            atomicOr(flag, 1);
+            return;
+        }
+    }
+}
+
 template <class T>
 static int32_t upload(pk_ctx* ctx, HostGrid& g, const T* host, size_t n, const T** dev) {
     *dev = nullptr;
@@ -628,6 +669,11 @@ int32_t pk_grid_create(pk_ctx* ctx, const pk_grid_desc* desc, int32_t* grid_id) 
                 PK_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(int), ctx->compute));
                 const int64_t ncell = (int64_t)(desc->ny - 1) * desc->nx;
                 if (ncell > 0) hipLaunchKernelGGL(illconditioned_cell_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, ctx->compute, d, d_flag);
+                // ... and where no node lies inside a cell it is not a corner of (a mesh that overlaps itself without coincident nodes)
+                const int64_t nnode = (int64_t)desc->ny * desc->nx;
+                if (desc->ny >= 2 && desc->nx >= 2 && d.h_nkeys > 0)
+                    hipLaunchKernelGGL(node_in_foreign_cell_kernel, dim3((unsigned)((nnode + 255) / 256)), dim3(256), 0, ctx->compute, d, d_flag);
+                PK_HIP(ctx, hipGetLastError());
                 PK_HIP(ctx, hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->compute));
                 PK_HIP(ctx, hipStreamSynchronize(ctx->compute));
                 (void)hipFree(d_flag);
@@ -2028,6 +2074,7 @@ static int32_t fill_fastc(pk_ctx* ctx, const pk_exec_params* prm, KArgs& a, int 
     const DField& f = U.d;
     const int64_t esz = f.dtype == PK_F64 ? 8 : 4;
     if (!g.d.has_x || !g.d.has_y || f.st_x != 1 || f.nx != g.d.nx || f.ny != g.d.ny || g.d.nx < 2 || g.d.ny < 2) return 0;
+    if (g.d.xdim <= 1) return 0;  // one cell column: no search is ever guessed (pk_device.h: grid_search)
     for (int o : {g.d.off_x, g.d.off_y, g.d.off_z})
         if (o != 0 && o != 1) return 0;
     if (g.d.has_z) {

@@ -999,6 +999,9 @@ template <int KIND, bool TYPED>
 PK_DEV void grid_search(const DGrid& g, const Coords* mc, double z, double y, double x, bool pos_f32, int32_t* ei,
                         PCtx& c, bool use_guess, GPos& p) {
     const bool curv = (KIND < 0) ? (g.kind == 1) : (KIND == 1);
+    // "have a guess" is np.any(xi) over the guesses (index_search.py:269).  On a mesh one cell wide every xi is 0, so no search is
+    // guessed there, the first or a later one: always the hash query in table order and its float32 (xsi, eta).
+    if (curv && (!g.has_x || g.xdim <= 1)) use_guess = false;
     const double* depth = mc ? mc->depth : g.depth;
     const double* lat = mc ? mc->lat : g.lat;
     const double* lon = mc ? mc->lon : g.lon;

@@ -130,7 +130,7 @@ class DeviceEngine:
     exact_error_stop = True  # kernel.py:236-245: after an error every particle stops where the reference's batch loop did
 
     def __init__(self, fieldset, device: int = 0, nslots: int | None = None, memory_fraction: float = 0.6,
-                 hash_build: str | None = None, neighbour_probe: int = 0):
+                 hash_build: str | None = None, neighbour_probe: int = 0, options: dict[str, int] | None = None):
         # hash_build: "device" (default) builds the Morton table of a curvilinear grid on the GPU (csrc/pk_hashbuild.hip);
         # "host" uploads parcels_amd.spatialhash.SpatialHash's table.  A grid whose host table already exists uploads it.
         self.nslots_request = nslots  # (FieldSet.to_windowed_arrays compares it with a later request)
@@ -144,6 +144,10 @@ class DeviceEngine:
         self.device = int(device)
         self.ctx = _hip.Context(self.device)
         self.lib = self.ctx.lib
+        # options: pk_set_option switches applied before the first grid is created -- "hash_directory" and "cell_table" are read by
+        # pk_grid_create, so setting them on a finished engine is too late
+        for name, value in (options or {}).items():
+            self.ctx.set_option(name, value)
         self._keep = []  # host buffers referenced by the library during calls
         self.grids = list(fieldset.gridset)
         self.grid_ids = []
